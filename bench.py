@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio-seconds tokenized per wall-second (acoustic + semantic_m) on MI355X — BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload both|all|acoustic|semantic_m|semantic_s] [--no-cpu-baseline] [--no-verify]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload both|all|acoustic|semantic_m|semantic_s] [--full] [--dump-outputs DIR]
+                    [--no-cpu-baseline] [--no-verify]
 
 One "step" = one pass of the hot path (the reference's ``self.encoder(input_batch, attention_mask)`` call, audiotoken/core.py:276) over
 one synthetic batch of EACH tokenizer the metric names, already resident in HBM: BASELINE configs[1] — Tokenizers.acoustic, 256 clips x 10 s
 @24 kHz, 8 codebooks — followed by BASELINE configs[3]'s per-GPU share — Tokenizers.semantic_m, 64 clips x 30 s @16 kHz, 19 conformer layers,
 VQ 2048. Both encodes sit inside ONE timed region (W warm-up steps, then exactly K steps between barrier + synchronize); top-level
-``value`` = audio-seconds of both / that time = the combined figure, ``ms_per_step`` = the whole step. Per-tokenizer rates, rooflines and CPU
-baselines are the named sub-objects ``acoustic`` and ``semantic_m`` (their times come from HIP events around each encode inside the same
-region). With --workload acoustic / semantic_m the step holds that tokenizer only. With N>1 (one rank per GPU) every rank encodes its own
+``value`` = audio-seconds of both / that time = the combined figure, ``ms_per_step`` = the whole step. Per-tokenizer rates are the named
+sub-objects ``acoustic`` and ``semantic_m`` (their times come from HIP events around each encode inside the same region). With --workload
+acoustic / semantic_m the step holds that tokenizer only. With N>1 (one rank per GPU) every rank encodes its own
 shard — clips are independent, so there is no data-path collective ("weak" scaling); RCCL is used only for the start barrier, the weight
 broadcast and the max-over-ranks time.
 
@@ -17,7 +18,11 @@ Multi-GPU: `python bench.py --gpus N` with no WORLD_SIZE in the environment star
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py ...`, before this process has touched the GPU) and relays rank 0's
 JSON line; under an external `torch.distributed.run` (WORLD_SIZE set) it is simply one of the ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given (DIR/<name>.npy, float32: the
+codes / token ids the encoders returned) and prints its line; `dtype` is then the arithmetic of the tokenizer that holds most of the step.
+--full measures the rest as well: per-kernel breakdowns and rooflines, PCIe-inclusive rates, the oracle check, the CPU baseline and, with
+--workload all (the default), the decode, semantic_s and files legs. Prints ONE JSON line on rank 0 (the bench contract); with --full it
+includes
   "roofline":       the dominant kernel group of the whole step: achieved rate vs the gfx950 peak, timed with HIP events on the launch stream
   "cpu_baseline":   the CPU oracle (a port of the reference's CPU path) timed on this host on a bounded sample, per tokenizer
   "verify":         a short post-timing oracle check of the timed batches' tokens (clips checked, ids differing, unexplained)
@@ -163,6 +168,26 @@ def emit(out: dict, detail_out: str = None, full_line: bool = False):
         except OSError as e:   # a read-only checkout must not cost the run its line
             print(f"bench.py: could not write {detail_out}: {e}", file=sys.stderr)
     print(compact_line(out, written), flush=True)
+
+
+DUMP_LIMIT = 63_000_000   # bytes of array data --dump-outputs writes at most (64 MB in all with the .npy headers)
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: what the timed path handed its caller in its LAST timed step, as `out_dir/<name>.npy` in float32 (token ids are exact in float32),
+    so that two builds can be compared output for output (same arguments = same seeded inputs). Should the arrays exceed DUMP_LIMIT together, each is cut to
+    a fixed sample of its elements (flat indices drawn with numpy seed 0, ascending), written flat, with the indices as float64 in `<name>_index.npy`:
+    4 + 8 bytes per kept element, a third of the limit's worth of elements in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {name: a.detach().cpu().float().numpy() for name, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT:
+            keep = a.size * DUMP_LIMIT // (3 * total)
+            index = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), index.astype(np.float64))
+            a = a.reshape(-1)[index]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def free_port() -> int:
@@ -465,27 +490,34 @@ def run_hubert(args, rank, world, dev, dist):
     clock = {}
     elapsed, toks, per_step = timed_steps(timed_call, args.steps, args.warmup, dist, clock)
     elapsed = max_over_ranks(elapsed, dev, dist)
-    prof = tapped_breakdown(enc, lambda: enc(wav, mask), min(args.steps, 2))
+    if args.dump_outputs and args.workload == "semantic_s" and rank == 0:
+        dump_outputs(args.dump_outputs, {"semantic_s_tokens": toks})
     flops, T = hubert_flops_per_clip(N, nl)
     arith = enc.get_option("arith")
     products = {0: 1, 1: 6, 2: 3}[arith]
     assert enc.last_status() == 0, "semantic_s status word non-zero after the timed region: the timed run is invalid"
-    breakdown = {}
-    for k, (per, launches) in prof.items():
-        breakdown[k] = {"ms_per_step": round(per, 3), "launches_per_step": launches,
-                        "tflops": round(flops[k] * B / (per * 1e-3) / 1e12, 2) if per > 0 and k in flops else None, "gbs": None}
     res = {
         "value": round(world * B * secs * args.steps / elapsed, 2), "unit": "audio-s/s", "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "dtype": {0: "f32", 1: "f32 (linear layers and convs: three bf16 pieces per operand, six MFMA products, fp32 accumulate)",
                   2: "f32 (linear layers and convs: two fp16 pieces per operand, three MFMA products, fp32 accumulate)"}[arith],
         "config": {"workload": f"Tokenizers.semantic_s encode, {B} clips x {secs:g} s @16 kHz per GPU, mHuBERT-base 11 layers, k-means 1000",
                    "clips_per_gpu": B, "samples_per_clip": N, "tokens_per_clip": T, "weights": f"synthetic seed 0, family {args.weights}", "clips": "speech-like, all distinct (audiotoken_amd/synthetic.py)"},
-        "roofline": add_held_clock(roofline_of(breakdown, flops, None, B, BF16X3_GROUPS if arith else (), "semantic_s", products), clock), "breakdown": breakdown,
         "token_checksum": S.token_checksum(toks),
         "checksum_pinned": (S.token_checksum(toks) == S.PINNED_CHECKSUMS[(args.weights, "semantic_s")]) if (rank == 0 and B == 128 and N == 480000) else None,
         "total_tflops": round(sum(flops.values()) * B * args.steps / elapsed / 1e12, 2),
         "fallback_batches": fallback * args.steps, "fallback_status": fb_status, "rank_probe": probe,
     }
+    if not args.full:   # the tapped loop and roofline are --full
+        del enc
+        torch.cuda.empty_cache()
+        return res
+    prof = tapped_breakdown(enc, lambda: enc(wav, mask), min(args.steps, 2))
+    breakdown = {}
+    for k, (per, launches) in prof.items():
+        breakdown[k] = {"ms_per_step": round(per, 3), "launches_per_step": launches,
+                        "tflops": round(flops[k] * B / (per * 1e-3) / 1e12, 2) if per > 0 and k in flops else None, "gbs": None}
+    res["roofline"] = add_held_clock(roofline_of(breakdown, flops, None, B, BF16X3_GROUPS if arith else (), "semantic_s", products), clock)
+    res["breakdown"] = breakdown
     if "kmeans" in breakdown and breakdown["kmeans"]["ms_per_step"] > 0:
         km_products = {0: 1, 1: 6, 2: 3}[arith] if enc.get_option("kmeans_split") == 1 else 1   # the score GEMM on the split kernel (option kmeans_split) or the fp32 MFMA
         res["argmin"] = argmin_entry("kmeans", breakdown["kmeans"]["ms_per_step"], flops["kmeans"] * B, (4.0 * T * 768 + 2.0 * T) * B, km_products)
@@ -898,16 +930,8 @@ def report_acoustic(wl, args, rank, world, dev, dist):
     rank_ms = sum(wl["per_step_ms"]) / len(wl["per_step_ms"])
     ms = max_over_ranks(rank_ms, dev, dist)
     checksum = S.token_checksum(wl["out"])
-    prof = tapped_breakdown(enc, wl["call"], min(args.steps, 3))
     flops, T = acoustic_flops_per_clip(N, n_q)
-    nbytes = acoustic_bytes_per_clip(N, n_q)
-    breakdown = {}
-    for k, (per, launches) in prof.items():
-        breakdown[k] = {"ms_per_step": round(per, 3), "launches_per_step": launches,
-                        "tflops": round(flops[k] * B / (per * 1e-3) / 1e12, 2) if per > 0 else None,
-                        "gbs": round(nbytes[k] * B / (per * 1e-3) / 1e9, 1) if per > 0 else None}
     f16_groups = acoustic_f16x2_groups(enc)
-    dom = max(breakdown, key=lambda k: breakdown[k]["ms_per_step"])
     res = {
         "value": round(world * B * args.seconds / (ms * 1e-3), 2), "unit": "audio-s/s", "ms_per_step": round(ms, 3), "median_ms_per_step": round(median(wl["per_step_ms"]), 3),
         "rank_ms": rank_ms, "broadcast_ms": round(wl["broadcast_ms"], 1), "finalize_ms": round(wl["finalize_ms"], 1),
@@ -916,13 +940,26 @@ def report_acoustic(wl, args, rank, world, dev, dist):
         "config": {"workload": f"Tokenizers.acoustic encode, {B} clips x {args.seconds:g} s @24 kHz per GPU, num_codebooks={n_q} (BASELINE configs[1])",
                    "clips_per_gpu": B, "samples_per_clip": N, "frames_per_clip": T, "weights": f"synthetic seed 0, family {args.weights}", "clips": "speech-like, all distinct (audiotoken_amd/synthetic.py)",
                    "parallelism": f"clip-sharded x{world}, no data-path collective", **({"options": list(args.acoustic_option)} if args.acoustic_option else {})},
-        "roofline": add_held_clock(roofline_of(breakdown, flops, nbytes, B, ACOUSTIC_X3_GROUPS, "acoustic", 3 if dom in f16_groups else 6), wl), "breakdown": breakdown,
         "mfma_products_per_mac": {**{g: (3 if g in f16_groups else 6) for g in ACOUSTIC_X3_GROUPS}, "final_conv": 3 if "final_conv" in f16_groups else 1},
-        "breakdown_note": "HIP-event taps of a second short loop (taps are off in the timed region)", "token_checksum": checksum,
+        "token_checksum": checksum,
         "checksum_pinned": (checksum == S.PINNED_CHECKSUMS[(args.weights, "acoustic")]) if (rank == 0 and B == 256 and N == 240000 and n_q == 8) else None,
         "lstm_handoff_status": status, "fallback_batches": wl["fallback_batches_per_step"] * args.steps, "fallback_status": wl["fallback_status"],
         "rank_probe": wl.get("rank_probe"),
     }
+    if not args.full:   # a plain run stops at the timed region's figures; the tapped loop, roofline and PCIe-inclusive rate are --full
+        return res
+    prof = tapped_breakdown(enc, wl["call"], min(args.steps, 3))
+    nbytes = acoustic_bytes_per_clip(N, n_q)
+    breakdown = {}
+    for k, (per, launches) in prof.items():
+        breakdown[k] = {"ms_per_step": round(per, 3), "launches_per_step": launches,
+                        "tflops": round(flops[k] * B / (per * 1e-3) / 1e12, 2) if per > 0 else None,
+                        "gbs": round(nbytes[k] * B / (per * 1e-3) / 1e9, 1) if per > 0 else None}
+    dom = max(breakdown, key=lambda k: breakdown[k]["ms_per_step"])
+    res.update({
+        "roofline": add_held_clock(roofline_of(breakdown, flops, nbytes, B, ACOUSTIC_X3_GROUPS, "acoustic", 3 if dom in f16_groups else 6), wl), "breakdown": breakdown,
+        "breakdown_note": "HIP-event taps of a second short loop (taps are off in the timed region)",
+    })
     if "rvq" in breakdown and breakdown["rvq"]["ms_per_step"] > 0:
         res["argmin"] = argmin_entry("rvq", breakdown["rvq"]["ms_per_step"], flops["rvq"] * B, (4.0 * T * 128 + 2.0 * T * n_q) * B,
                                      3 if "rvq" in f16_groups else (6 if "rvq" in ACOUSTIC_X3_GROUPS else 1))
@@ -1011,6 +1048,15 @@ def run_decode(args, rank, world, dev, dist):
     if hasattr(dec, "last_status"):
         assert dec.last_status() == 0, "persistent LSTM hand-off status non-zero: the timed decode is invalid"
     elapsed = max_over_ranks(elapsed, dev, dist)
+    if args.dump_outputs and args.workload == "decode" and rank == 0:
+        dump_outputs(args.dump_outputs, {"acoustic_decode_audio": out})
+    res = {"value": round(world * B * args.seconds * args.steps / elapsed, 2), "unit": "audio-s/s", "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+           "config": {"workload": f"Tokenizers.acoustic decode, {B} clips x {args.seconds:g} s, num_codebooks={args.num_codebooks}"},
+           "checksum": float(out.double().abs().sum().item())}
+    if not args.full:   # the tapped loop and roofline are --full
+        del dec
+        torch.cuda.empty_cache()
+        return res
     prof = tapped_breakdown(dec, lambda: dec(codes), min(args.steps, 3))
     flops, nbytes = decode_work_per_clip(T, bool(dec.get_option("fused_dectail")))
     breakdown = {}
@@ -1021,11 +1067,8 @@ def run_decode(args, rank, world, dev, dist):
     # kernel groups that run as two-piece fp16 operand splits (three MFMA products per multiply-add) under the decoder's options
     split = tuple(g for opt, groups in {"up_f16x2": ("dec_up0", "dec_up1", "dec_up2"), "res_f16x2": ("dec_res0", "dec_res1", "dec_res2"),
                                         "ih_f16x2": ("lstm_ih",), "lstm_f16x2": ("lstm_rec",)}.items() if BF16X3_ACOUSTIC and dec.get_option(opt) == 1 for g in groups)
-    res = {"value": round(world * B * args.seconds * args.steps / elapsed, 2), "unit": "audio-s/s", "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-           "config": {"workload": f"Tokenizers.acoustic decode, {B} clips x {args.seconds:g} s, num_codebooks={args.num_codebooks}"},
-           "roofline": roofline_of(breakdown, flops, nbytes, B, split, "acoustic_decode", 3), "breakdown": breakdown,
-           "breakdown_note": "HIP-event taps of a second short loop (taps are off in the timed region)",
-           "checksum": float(out.double().abs().sum().item())}
+    res.update({"roofline": roofline_of(breakdown, flops, nbytes, B, split, "acoustic_decode", 3), "breakdown": breakdown,
+                "breakdown_note": "HIP-event taps of a second short loop (taps are off in the timed region)"})
     del dec
     torch.cuda.empty_cache()
     return res
@@ -1097,19 +1140,11 @@ def report_semantic(wl, args, rank, world, dev, dist):
     rank_ms = sum(wl["per_step_ms"]) / len(wl["per_step_ms"])
     ms = max_over_ranks(rank_ms, dev, dist)
     toks = wl["out"]
-    prof = tapped_breakdown(enc, wl["call"], min(args.steps, 2))
     T = toks.shape[-1]
     F = 1 + (N - 400) // 160
     flops = semantic_flops_per_clip(T, nl, F)
     arith = enc.get_option("arith")                    # 0 f32 MFMA, 1 bf16x3 (six products), 2 f16x2 (three products)
     products = {0: 1, 1: 6, 2: 3}[arith]
-    breakdown = {}
-    ln_bytes = {"layernorm": 8.0 * T * 1024 * (4 * nl) + 8.0 * T * 1024 * nl}   # LayerNorm -> pieces: 4 B in + 4 B out per element; final LN 4 + 4
-    for k, (per, launches) in prof.items():
-        breakdown[k] = {"ms_per_step": round(per, 3), "launches_per_step": launches,
-                        "tflops": round(flops[k] * B / (per * 1e-3) / 1e12, 2) if per > 0 and k in flops else None,
-                        "gbs": round(ln_bytes[k] * B / (per * 1e-3) / 1e9, 1) if per > 0 and k in ln_bytes else None}
-    flops_all = dict(flops, layernorm=0.0)
     checksum = S.token_checksum(toks)
     res = {
         "value": round(world * B * secs / (ms * 1e-3), 2), "unit": "audio-s/s", "ms_per_step": round(ms, 3),
@@ -1122,8 +1157,6 @@ def report_semantic(wl, args, rank, world, dev, dist):
                    "clips_per_gpu": B, "samples_per_clip": N, "tokens_per_clip": T, "weights": f"synthetic seed 0, family {args.weights}", "clips": "speech-like, all distinct (audiotoken_amd/synthetic.py)",
                    "parallelism": f"clip-sharded x{world}, no data-path collective",
                    "note": "BASELINE configs[3] is 512 clips over 8 GPUs = 64 per GPU; at N=1 one step is one such 64-clip micro-batch"},
-        "roofline": add_held_clock(roofline_of(breakdown, flops_all, None, B, ("ffn", "attn_proj", "conv_module") if arith else (), "semantic_m", products), wl), "breakdown": breakdown,
-        "breakdown_note": "HIP-event taps of a second short loop (taps are off in the timed region)",
         "token_checksum": checksum,
         "checksum_pinned": (checksum == S.PINNED_CHECKSUMS[(args.weights, "semantic_m")]) if (rank == 0 and B == 64 and N == 480000 and nl == 19 and not args.stress_range) else None,
         "total_tflops": round(sum(flops.values()) * B / (ms * 1e-3) / 1e12, 2),
@@ -1131,6 +1164,20 @@ def report_semantic(wl, args, rank, world, dev, dist):
         "rank_probe": wl.get("rank_probe"),
         "pinned_layers": sorted(set(getattr(enc, "pinned_layers", []))),   # conformer layers the range fallback moved to bf16x3 before the timed region (normally none)
     }
+    if not args.full:   # a plain run stops at the timed region's figures; the tapped loop, roofline and PCIe-inclusive rate are --full
+        return res
+    prof = tapped_breakdown(enc, wl["call"], min(args.steps, 2))
+    breakdown = {}
+    ln_bytes = {"layernorm": 8.0 * T * 1024 * (4 * nl) + 8.0 * T * 1024 * nl}   # LayerNorm -> pieces: 4 B in + 4 B out per element; final LN 4 + 4
+    for k, (per, launches) in prof.items():
+        breakdown[k] = {"ms_per_step": round(per, 3), "launches_per_step": launches,
+                        "tflops": round(flops[k] * B / (per * 1e-3) / 1e12, 2) if per > 0 and k in flops else None,
+                        "gbs": round(ln_bytes[k] * B / (per * 1e-3) / 1e9, 1) if per > 0 and k in ln_bytes else None}
+    flops_all = dict(flops, layernorm=0.0)
+    res.update({
+        "roofline": add_held_clock(roofline_of(breakdown, flops_all, None, B, ("ffn", "attn_proj", "conv_module") if arith else (), "semantic_m", products), wl), "breakdown": breakdown,
+        "breakdown_note": "HIP-event taps of a second short loop (taps are off in the timed region)",
+    })
     if "vq" in breakdown and breakdown["vq"]["ms_per_step"] > 0:
         vq_products = {0: 1, 1: 6, 2: 3}[arith] if enc.get_option("vq_split") == 1 else 1   # the score GEMM on the split kernel (option vq_split) or the fp32 MFMA
         res["argmin"] = argmin_entry("vq", breakdown["vq"]["ms_per_step"], flops["vq"] * B, (4.0 * T * 1024 + 2.0 * T) * B, vq_products)
@@ -1190,7 +1237,18 @@ def parse_args(argv=None):
     ap.add_argument("--shared-device", action="store_true",
                     help="rehearsal of the N > 1 path on a ONE-GPU box: every rank drives cuda:0 (needs --backend gloo: RCCL cannot put two ranks on "
                          "one device); the collectives go through host memory, the numbers are not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure too: per-kernel breakdowns and rooflines, PCIe-inclusive rates, the oracle check of the "
+                         "timed batches (unless --no-verify), the CPU baseline (unless --no-cpu-baseline) and, for --workload all, the decode, semantic_s and "
+                         "files legs. Without it a run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, rank 0's shard)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload in ("files", "selftest"):
+        ap.error(f"--dump-outputs: --workload {args.workload} has no device outputs to write")
+    return args
 
 
 def main(argv=None):
@@ -1256,8 +1314,11 @@ def main(argv=None):
         audio_s = sum(wl["audio_s"] for wl in workloads)
         value = world * audio_s * args.steps / elapsed
         ms_per_step = elapsed / args.steps * 1e3
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {wl["name"] + ("_codes" if wl["name"] == "acoustic" else "_tokens"): wl["out"] for wl in workloads})
+    # what follows beyond the headline figure runs with --full only (--workload decode / semantic_s / files name their leg explicitly)
     verify = None
-    if rank == 0 and world == 1 and not args.no_verify and workloads:
+    if args.full and rank == 0 and world == 1 and not args.no_verify and workloads:
         verify = {}
         for wl in workloads:
             try:
@@ -1269,7 +1330,7 @@ def main(argv=None):
     torch.cuda.empty_cache()
 
     dec = None
-    if args.workload in ("all", "decode"):
+    if args.workload == "decode" or (args.workload == "all" and args.full):
         try:
             dec = run_decode(args, rank, world, dev, dist)
         except Exception as e:
@@ -1284,7 +1345,7 @@ def main(argv=None):
             dist.destroy_process_group()
         return 0
     hub = hub_err = None
-    if args.workload in ("all", "semantic_s"):
+    if args.workload == "semantic_s" or (args.workload == "all" and args.full):
         try:
             hub = run_hubert(args, rank, world, dev, dist)
         except Exception as e:
@@ -1292,7 +1353,7 @@ def main(argv=None):
                 raise
             hub_err = f"{type(e).__name__}: {e}"
     files = files_err = None
-    if args.workload in ("all", "files"):
+    if args.workload == "files" or (args.workload == "all" and args.full):
         try:
             rates = {n: r["value"] / world for n, r in res.items()}
             if hub is not None:
@@ -1316,7 +1377,10 @@ def main(argv=None):
     if rank == 0:
         ac, sem = res.get("acoustic"), res.get("semantic_m")
         parts = [r for r in (ac, sem) if r is not None] or [hub]
-        dominant = max(parts, key=lambda r: r["roofline"]["avg_launch_ms"] * r["roofline"]["launches_per_step"])
+        if args.full:   # `dtype` is the arithmetic of the part that holds the step's dominant kernel group ...
+            dominant = max(parts, key=lambda r: r["roofline"]["avg_launch_ms"] * r["roofline"]["launches_per_step"])
+        else:           # ... and, without the tapped loop that finds it, of the part that holds most of the step
+            dominant = max(parts, key=lambda r: r["ms_per_step"])
         names = [n for n, r in (("acoustic", ac), ("semantic_m", sem)) if r is not None] or ["semantic_s"]
         out = {
             "metric": "audio-sec tokenized / wall-sec (" + " + ".join(names) + ")", "value": round(value, 2), "unit": "audio-s/s",
@@ -1328,7 +1392,7 @@ def main(argv=None):
                                "all of them / that time (BASELINE.json's combined metric); per-tokenizer rates in the named sub-objects",
                        "audio_s_per_step_per_gpu": sum(r["config"]["clips_per_gpu"] * r["config"]["samples_per_clip"] / (24000 if "frames_per_clip" in r["config"] else 16000) for r in parts),
                        "weights": f"synthetic seed 0, family {args.weights}", "clips": "speech-like, all distinct (audiotoken_amd/synthetic.py)", "parallelism": f"clip-sharded x{world}, no data-path collective"},
-            "roofline": dict(dominant["roofline"], workload=names[parts.index(dominant)] if dominant in parts else "semantic_s"),
+            "roofline": dict(dominant["roofline"], workload=names[parts.index(dominant)] if dominant in parts else "semantic_s") if args.full else None,
             "rccl_ranks": ranks["rccl_ranks"], "per_rank_ms": ranks["per_rank_ms"],
             "backend": args.backend if world > 1 else None,
         }
@@ -1336,11 +1400,11 @@ def main(argv=None):
             out["combined"] = {"value": out["value"], "unit": "audio-s/s", "definition": "audio-seconds of both workloads / time of the steps that hold both (= the top-level value)",
                                "same_clips_rate": round(1.0 / (1.0 / ac["value"] + 1.0 / sem["value"]), 2),
                                "same_clips_definition": "audio-seconds / wall-second when every clip goes through BOTH tokenizers: 1 / (1 / acoustic + 1 / semantic_m)"}
-        want_cpu = not args.no_cpu_baseline and world == 1
+        want_cpu = args.full and not args.no_cpu_baseline and world == 1
         if not want_cpu:
             out["cpu_baseline"] = None
             out["cpu_baseline_note"] = ("skipped: --no-cpu-baseline" if args.no_cpu_baseline else
-                                        "skipped at N>1: the CPU oracle is timed on rank 0 at N=1 only")
+                                        "skipped at N>1: the CPU oracle is timed on rank 0 at N=1 only" if world > 1 else "skipped: measured with --full")
         else:
             if ac is not None:
                 ac["cpu_baseline"] = cpu_baseline_acoustic(args.num_codebooks)

@@ -12,7 +12,7 @@ grep -i "differ\|hidden\|max err\|unexplained" $O/tests.log | cut -c1-260 | head
 unset AUDIOTOKEN_HIP_LIB
 for v in p2 p1 p2 p1; do
   if [ $v = p1 ]; then export AUDIOTOKEN_HIP_LIB=$R/tools/_lib_p1.so; else unset AUDIOTOKEN_HIP_LIB; fi
-  python3 $R/bench.py --full-line --workload semantic_m --steps 5 --warmup 2 --no-cpu-baseline --no-verify 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --full-line --workload semantic_m --steps 5 --warmup 2 --no-cpu-baseline --no-verify 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     try: d=json.loads(l)
