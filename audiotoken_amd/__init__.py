@@ -5,7 +5,7 @@
 """
 from .configs import AUDIO_EXTS, TAR_EXTS, ZIP_EXTS, Tokenizers  # noqa: F401
 
-__all__ = ["AudioToken", "Tokenizers", "AUDIO_EXTS", "TAR_EXTS", "ZIP_EXTS", "read_audio"]
+__all__ = ["AudioToken", "KMeans", "Tokenizers", "AUDIO_EXTS", "TAR_EXTS", "ZIP_EXTS", "read_audio"]
 
 
 def __getattr__(name):
@@ -13,6 +13,9 @@ def __getattr__(name):
     if name == "AudioToken":
         from .core import AudioToken
         return AudioToken
+    if name == "KMeans":
+        from .kmeans import KMeans
+        return KMeans
     if name == "read_audio":
         from .audio_io import read_audio
         return read_audio

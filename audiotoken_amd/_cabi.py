@@ -128,6 +128,18 @@ SIGNATURES = {
     "at_op_dwconv_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "at_op_vq_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "at_op_vq_argmax_refined": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "at_kmeans_device_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "at_kmeans_create": (C.c_void_p, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "at_kmeans_destroy": (None, [C.c_void_p]),
+    "at_kmeans_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    "at_kmeans_get_option": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "at_kmeans_set_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "at_kmeans_plusplus": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "at_kmeans_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "at_kmeans_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "at_kmeans_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "at_kmeans_row_d2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "at_kmeans_relocations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "at_op_gemm": (C.c_int, [C.POINTER(GemmDesc), C.c_void_p]),
     "at_required_tensors": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "at_op_gemm_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,

@@ -244,6 +244,15 @@ class AudioToken:
         assert audio_files or audio_dir, "Either audio_files or audio_dir must be provided"
         assert not (audio_files and audio_dir), "Provide either audio_files or audio_dir, not both"
         outdir = sanitize_path(outdir)
+        files = self._input_files(audio_files, audio_dir)
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dataloader_kwargs.get("shard_across_ranks", True):
+            files = self._shard_files(files)
+        self._encode_files(files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs)
+
+    @staticmethod
+    def _input_files(audio_files, audio_dir) -> List[str]:
+        """The inputs of encode_batch_files / fit_quantizer: the given files, or every file with a known extension under ``audio_dir``, sorted."""
         if audio_files is not None:
             files = [str(f) for f in audio_files]
         else:
@@ -273,24 +282,30 @@ class AudioToken:
                 dirs[:] = keep
                 files.extend(os.path.join(d, n) for n in names if n.endswith(exts) and not n.startswith("."))
             files.sort()
+        return files
+
+    def _shard_files(self, files: List[str]) -> List[str]:
+        """This rank's share of the file list under torch.distributed (collective: every rank calls it with the same list)."""
         import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dataloader_kwargs.get("shard_across_ranks", True):
-            # duration-aware: whole files by greedy LPT on their sizes (distributed.shard_by_size). Rank 0 stats the list ONCE and broadcasts the sizes (N_files
-            # stats instead of N_files x world on a shared filesystem; and every rank provably shards the same numbers)
-            import hashlib
-            from .distributed import collective_device, shard_by_size
-            digest = hashlib.sha256("\0".join(files).encode("utf-8", "surrogateescape")).hexdigest()
-            sizes = [([os.path.getsize(f) if os.path.exists(f) else 0 for f in files], digest)] if dist.get_rank() == 0 else [None]
-            # the pickled list travels on THIS rank's device under RCCL (not torch's current device: a caller that never called set_device would put every rank on cuda:0)
-            dist.broadcast_object_list(sizes, src=0, device=collective_device(torch.device(self.device), dist))
-            sizes, digest0 = sizes[0]
-            # every rank learns whether ALL ranks hold rank 0's list: a rank that differs must stop the others too, not let them encode a shard of a list it does not share
-            from .distributed import gather_scalars
-            same = len(sizes) == len(files) and digest0 == digest
-            votes = gather_scalars([1.0 if same else 0.0], torch.device(self.device), dist)
-            bad = [r for r, v in enumerate(votes) if v[0] != 1.0]
-            assert not bad, f"ranks {bad} see a different file list than rank 0: encode_batch_files needs the same audio_files / audio_dir on every rank"
-            files = [files[i] for i in shard_by_size(sizes, dist.get_rank(), dist.get_world_size())]
+        # duration-aware: whole files by greedy LPT on their sizes (distributed.shard_by_size). Rank 0 stats the list ONCE and broadcasts the sizes (N_files
+        # stats instead of N_files x world on a shared filesystem; and every rank provably shards the same numbers)
+        import hashlib
+        from .distributed import collective_device, shard_by_size
+        digest = hashlib.sha256("\0".join(files).encode("utf-8", "surrogateescape")).hexdigest()
+        sizes = [([os.path.getsize(f) if os.path.exists(f) else 0 for f in files], digest)] if dist.get_rank() == 0 else [None]
+        # the pickled list travels on THIS rank's device under RCCL (not torch's current device: a caller that never called set_device would put every rank on cuda:0)
+        dist.broadcast_object_list(sizes, src=0, device=collective_device(torch.device(self.device), dist))
+        sizes, digest0 = sizes[0]
+        # every rank learns whether ALL ranks hold rank 0's list: a rank that differs must stop the others too, not let them encode a shard of a list it does not share
+        from .distributed import gather_scalars
+        same = len(sizes) == len(files) and digest0 == digest
+        votes = gather_scalars([1.0 if same else 0.0], torch.device(self.device), dist)
+        bad = [r for r, v in enumerate(votes) if v[0] != 1.0]
+        assert not bad, f"ranks {bad} see a different file list than rank 0: encode_batch_files needs the same audio_files / audio_dir on every rank"
+        files = [files[i] for i in shard_by_size(sizes, dist.get_rank(), dist.get_world_size())]
+        return files
+
+    def _encode_files(self, files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs) -> None:
         start_time = time.time()
         on_gpu = torch.device(self.device).type == "cuda"
         copy_stream = torch.cuda.Stream(device=self.device) if on_gpu else None
@@ -397,6 +412,116 @@ class AudioToken:
             logger.error(f"encode_batch_files: layers {self.run_summary['pinned_layers']} ran on bf16x3 for part of this run (fp16 range overflow); restored to f16x2")
         if hasattr(enc, "unpin_layers"):
             enc.unpin_layers()
+
+    # code-book sizes the tokenizers' finalize() accepts (csrc/w2vbert.hip, csrc/hubert.hip): (clusters, width, LayerNorm kernel of the quantiser step)
+    _FIT_SHAPES = {Tokenizers.semantic_m: (2048, 1024, 1), Tokenizers.semantic_s: (1000, 768, 0)}
+
+    def fit_quantizer(self, path: os.PathLike, audio_dir: Optional[Union[os.PathLike, Path]] = None, audio_files: Optional[List[os.PathLike]] = None,
+                      chunk_size: int = 30, batch_size: int = 64, num_workers: int = 0, max_frames: int = 4_000_000, keep_fraction: float = 1.0,
+                      num_clusters: Optional[int] = None, max_iter: int = 150, tol: float = 1e-4, seed: int = 0, n_init: int = 1, init="k-means++",
+                      **dataloader_kwargs):
+        """Fit the semantic tokenizer's code book on a corpus (the reference's scripts/clustering/cluster_tokens.py) and write it to ``path`` in the format
+        the tokenizer loads (semantic_m: the VectorQuantize state dict, semantic_s: the joblib k-means). Frames: the encoder's hidden state with
+        ``quantize=False`` through the checked encode path (a batch that overflowed the fp16 range is re-encoded by ``verified`` before it adds frames),
+        segments cut as ``encode_batch_files`` cuts them, only each segment's valid frames (``length_tokens``), normalised by the quantiser step's own
+        LayerNorm kernel, in file / segment / frame order. ``keep_fraction`` keeps a frame by a counter-based draw keyed on (file, segment, frame);
+        ``max_frames`` caps the sample. Local to this process: no collectives, also under torch.distributed. Returns the fitted ``KMeans``."""
+        from . import _cabi
+        from .kmeans import KMeans, plusplus_uniforms, save_kmeans, save_vq  # noqa: F401
+        from . import prng
+        if self.tokenizer_name not in self._FIT_SHAPES:
+            raise ValueError(f"fit_quantizer: {self.tokenizer_name} has no semantic code book to fit (semantic_m or semantic_s)")
+        k, d, split_ln = self._FIT_SHAPES[self.tokenizer_name]
+        if num_clusters is not None and int(num_clusters) != k:
+            raise ValueError(f"fit_quantizer: {self.tokenizer_name} quantises against exactly {k} codes, not {num_clusters}")
+        if not 0.0 < float(keep_fraction) <= 1.0:
+            raise ValueError(f"fit_quantizer: keep_fraction must be in (0, 1], got {keep_fraction}")
+        if int(max_frames) < k:
+            raise ValueError(f"fit_quantizer: max_frames = {max_frames} < {k} codes")
+        assert audio_files or audio_dir, "Either audio_files or audio_dir must be provided"
+        assert not (audio_files and audio_dir), "Provide either audio_files or audio_dir, not both"
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise ValueError("fit_quantizer needs a HIP device")
+        lib = _cabi.load()
+        max_frames = int(max_frames)
+        need = max_frames * d * 4 + int(lib.at_kmeans_device_bytes(max_frames, d, k))
+        free = torch.cuda.mem_get_info(dev)[0]
+        if need > free:
+            raise ValueError(f"fit_quantizer: max_frames = {max_frames} needs {need / 2**30:.2f} GiB of device memory "
+                             f"({max_frames * d * 4 / 2**30:.2f} GiB of frames + {(need - max_frames * d * 4) / 2**30:.2f} GiB of k-means state); "
+                             f"{free / 2**30:.2f} GiB are free")
+        # the encoder without a code book (hidden state out); the same checkpoint and layer as the tokenizer
+        wkw = self._weights_kw()
+        if self.tokenizer_name == Tokenizers.semantic_m:
+            from .encoder import Wav2VecBertEncoder
+            enc = Wav2VecBertEncoder(config=self.model_config, device=self.device, quantize=False, weights=wkw)
+        else:
+            from .hubert import HubertEncoder
+            enc = HubertEncoder(config=self.model_config, device=self.device, quantize=False, weights=wkw)
+        enc.eval()
+        files = self._input_files(audio_files, audio_dir)
+        self.skipped_files = []
+
+        def skipped(name, why):
+            logger.error(f"Skipping {name}: {why}")
+            self.skipped_files.append((name, why))
+        from .feeder import DeviceFeeder
+        from .hubert import hubert_processor
+        transform = "zmuv" if self.tokenizer_name == Tokenizers.semantic_s else None
+        assert self.tokenizer_name != Tokenizers.semantic_s or self.transform_func in (None, hubert_processor)
+        feeder = DeviceFeeder(self.device, self.model_config.model_sample_rate, chunk_size, self.model_config.model_token_rate,
+                              self.model_config.pad_token, num_workers, skipped, transform=transform)
+        frames = torch.empty((max_frames, d), dtype=torch.float32, device=dev)
+        filled, truncated, batches, seen = 0, False, 0, 0
+        fb0 = getattr(enc, "fallback_batches", 0)
+        stream = torch.cuda.current_stream(dev)
+        for input_ids, masks, pointers, ev in feeder.batches(files, batch_size):
+            if ev is not None:
+                stream.wait_event(ev)
+                input_ids.record_stream(stream)
+                masks.record_stream(stream)
+            hidden = enc(input_ids, masks)
+            hidden = enc.verified(hidden, input_ids, masks)      # an fp16 range overflow: the batch is re-encoded before any frame is taken
+            batches += 1
+            B, T, _ = hidden.shape
+            rows = hidden.reshape(B * T, d)
+            y = torch.empty_like(rows)
+            ws = torch.empty(((B * T + 7) // 8 * 8) * d * 4 if split_ln else 1, dtype=torch.uint8, device=dev)
+            _cabi.check(lib.at_kmeans_layernorm(rows.data_ptr(), y.data_ptr(), B * T, d, split_ln, ws.data_ptr(), ws.numel(),
+                                                _cabi.current_stream_handle(dev)), "at_kmeans_layernorm")
+            keep = []
+            for b, p in enumerate(pointers):
+                n_valid = min(T, int(p.length_tokens))
+                seen += n_valid
+                idx = np.arange(n_valid, dtype=np.int64)
+                if keep_fraction < 1.0:
+                    u = prng.uniform01(f"fit_quantizer|{p.file_name}|{int(getattr(p, 'start_idx', 0))}", n_valid, seed)
+                    idx = idx[u < np.float32(keep_fraction)]
+                keep.append(b * T + idx)
+            sel = np.concatenate(keep) if keep else np.zeros(0, np.int64)
+            if filled + len(sel) > max_frames:
+                sel = sel[:max_frames - filled]
+                truncated = True
+            if len(sel):
+                frames[filled:filled + len(sel)] = y[torch.from_numpy(sel).to(dev)]
+                filled += len(sel)
+            if truncated:
+                break
+        if truncated:
+            logger.warning(f"fit_quantizer: the sample reached max_frames = {max_frames}; later frames were not used")
+        if filled < k:
+            raise ValueError(f"fit_quantizer: {filled} frames collected, fewer than the {k} codes to fit")
+        X = frames[:filled]
+        km = KMeans(k, init=init, n_init=n_init, max_iter=max_iter, tol=tol, seed=seed, device=self.device)
+        km.fit(X)
+        km.fit_summary_ = {"frames": filled, "frames_seen": seen, "batches": batches, "truncated": truncated,
+                           "fallback_batches": getattr(enc, "fallback_batches", 0) - fb0, "skipped_files": len(self.skipped_files)}
+        if self.tokenizer_name == Tokenizers.semantic_m:
+            save_vq(path, km.cluster_centers_)
+        else:
+            save_kmeans(path, km)
+        return km
 
     def load_decoder(self, **kwargs):
         """core.py:291-315 — only the acoustic decoder exists here (the semantic decoders are out of scope)."""

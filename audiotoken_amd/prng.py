@@ -74,6 +74,11 @@ def _bits(name: str, n: int, seed: int) -> np.ndarray:
         return _mix(stream_seed(name, seed) + idx * _GOLDEN)
 
 
+def uniform01_f64(name: str, n: int, seed: int = 0) -> np.ndarray:
+    """n float64 values in [0, 1), exact multiples of 2^-53 (the top 53 bits of each 64-bit draw)."""
+    return (_bits(name, n, seed) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
 def heavy_tailed(name: str, shape, std: float, seed: int = 0) -> np.ndarray:
     """Zero mean, standard deviation `std`, power-law tails of index 4 (the tail of Student-t with nu = 4): an approximately normal draw (the sum of
     the three 21-bit fields of one 64-bit word, centred: Irwin-Hall of order 3) times a Pareto scale u^(-1/4) — two IEEE square roots, no libm.

@@ -383,6 +383,49 @@ int at_op_vq_argmax(const float* x, const float* dots, const float* e2, int16_t*
  * 100-101,180-181), whose expanded fp32 form cancels when the centres sit in the data. */
 int at_op_vq_argmax_refined(const float* x, const float* dots, const float* e2, const float* codebook, int16_t* out, int64_t rows, int D, int C, at_stream_t stream);
 
+/* ---- k-means: fitting the semantic tokenizers' code books (csrc/kmeans.hip) ------------------------------------------------------------------------
+ * Replaces the reference's code-book fitting (scripts/clustering/cluster_tokens.py, KMeansClusterConfig audiotoken/configs.py:221-226) with full-batch
+ * Lloyd iterations on a device-resident sample X [N][D] fp32 (row-major, kept by pointer) and centres C [K][D] fp32. D % 64 == 0, 64 <= D <= 1024;
+ * 4 <= K <= 32767, K % 4 == 0 (int16 labels); K <= N < 2^31. Calls are stream-ordered and never synchronise; all scratch is allocated by create(). */
+typedef struct at_kmeans at_kmeans_t;
+
+/* Device bytes at_kmeans_create allocates for this shape (0 when the shape is invalid): size a sample against free memory with it. */
+size_t at_kmeans_device_bytes(int64_t N, int D, int K);
+/* Create a handle on `device` for N rows of D floats and K centres; NULL on failure (at_last_error). */
+at_kmeans_t* at_kmeans_create(int device, int64_t N, int D, int K);
+void at_kmeans_destroy(at_kmeans_t* h);
+/* "scheme": the E-step's score GEMM operands, 1 = two fp16 pieces (default: the rows are split once per at_kmeans_set_data), 0 = three bf16 pieces (any
+ * magnitude; the rows are split chunk by chunk in every E-step) — the fall-back after a range overflow; call at_kmeans_set_data again after changing it. */
+int at_kmeans_set_option(at_kmeans_t* h, const char* name, int value);
+/* "scheme", "chunk_rows" (rows per E-step chunk), "trials" (k-means++ local trials, 2 + int(ln K)); -1 = unknown name. */
+int at_kmeans_get_option(const at_kmeans_t* h, const char* name);
+/* Hand the rows to the handle: X device [N][D], 16-byte aligned, must stay valid and unchanged while the handle uses it. x_max_abs = max |X| sets the
+ * activation scale of the fp16 scheme (<= 32, LayerNorm-ed rows: the tokenizers' scale 16; else the power of two that puts max |X| into [2^14, 2^15)). */
+int at_kmeans_set_data(at_kmeans_t* h, const float* X, float x_max_abs, at_stream_t stream);
+/* Greedy k-means++ seeding (sklearn's _kmeans_plusplus, n_local_trials = trials = 2 + int(ln K)): uniforms device float64 [K][trials] in [0, 1);
+ * the first centre is row floor(uniforms[0][0] N); every later centre c draws candidate rows by searching uniforms[c][t] * total in the float64 inclusive
+ * scan of the current closest squared distances and keeps the candidate of the smallest potential sum_i min(d2_i, |x_i - x_cand|^2) (ties to the lower
+ * row). Writes C_out device [K][D] and picked_rows device int64 [K]. */
+int at_kmeans_plusplus(at_kmeans_t* h, const double* uniforms, int trials, float* C_out, int64_t* picked_rows, at_stream_t stream);
+/* E-step: labels device int16 [N] = the nearest centre of every row (the tokenizers' score GEMM + at_op_vq_argmax_refined: exact float64 re-evaluation of
+ * near-ties, ties to the lower index). c_max_abs = max |C| sets the centre scale (<= 0: max |X|, a bound for any mean of rows). status_dev (nullable
+ * device word, overwritten): bit 1 = the fp16 range was exceeded (repeat with option "scheme" 0), bit 2 = a row or centre holds a NaN / infinity. */
+int at_kmeans_assign(at_kmeans_t* h, const float* C, float c_max_abs, int16_t* labels, int32_t* status_dev, at_stream_t stream);
+/* M-step, bitwise reproducible (no float atomics): per-cluster float64 sums of the rows in a stable inverted-index order, the empty clusters relocated
+ * (sklearn's rule: the rows farthest from their centre, ties to the lower row, in decreasing distance to the empty clusters in increasing index order),
+ * C_new = sum / count rounded to fp32 once. counts device int32 [K] (after relocation); prev_labels nullable (then n_changed = 0); C_new must not alias
+ * C_old. stats_dev device float64 [6]: inertia = sum of |x - C_old[label]|^2, shift2 = sum |C_new - C_old|^2, n_changed, n_empty, max |C_new|, and the
+ * number of labels outside [0, K) (ignored rows). */
+int at_kmeans_update(at_kmeans_t* h, const int16_t* labels, const int16_t* prev_labels, const float* C_old, float* C_new, int32_t* counts,
+                     double* stats_dev, at_stream_t stream);
+/* The non-affine LayerNorm (eps 1e-5) of a tokenizer's quantiser step on rows x [rows][D] -> y, bit for bit the kernel that step runs: split_kernel 1 =
+ * semantic_m's (fp32 rows written with the operand pieces; D 1024; workspace >= round_up(rows, 8) * D * 4 bytes), 0 = semantic_s's plain kernel. */
+int at_kmeans_layernorm(const float* x, float* y, int64_t rows, int D, int split_kernel, void* workspace, size_t workspace_bytes, at_stream_t stream);
+/* The last update's per-row squared distances to the old centres (device float64 [N]) and its relocations (device int32 [K][3] = row, old cluster,
+ * new cluster; the first n_empty entries are valid): for tests. */
+int at_kmeans_row_d2(const at_kmeans_t* h, double* out, at_stream_t stream);
+int at_kmeans_relocations(const at_kmeans_t* h, int32_t* out, at_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
