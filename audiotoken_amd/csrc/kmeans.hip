@@ -479,7 +479,8 @@ __global__ __launch_bounds__(256) void km_pp_dist_kernel(const float* __restrict
     }
 }
 
-// one workgroup: the trials' potentials (block partials, one wave per trial, fixed order), the best candidate (ties to the lower row index) becomes centre c
+// one workgroup: the trials' potentials (block partials, one wave per trial, fixed order), the best candidate becomes centre c. Ties go to the first
+// trial, as sklearn's np.argmin over the candidates: duplicate rows give equal potentials, and the row sklearn keeps is the first drawn, not the lowest.
 __global__ __launch_bounds__(1024) void km_pp_choose_kernel(const double* __restrict__ blk_pot, int nblk, int trials, const float* __restrict__ X, int D,
                                                             int c, int* __restrict__ pp, float* __restrict__ C_out, int64_t* __restrict__ picked) {
     __shared__ double s_pot[KM_MAX_TRIALS];
@@ -496,7 +497,7 @@ __global__ __launch_bounds__(1024) void km_pp_choose_kernel(const double* __rest
     if (threadIdx.x == 0) {
         int best = 0;
         for (int j = 1; j < trials; ++j)
-            if (s_pot[j] < s_pot[best] || (s_pot[j] == s_pot[best] && pp[1 + j] < pp[1 + best])) best = j;
+            if (s_pot[j] < s_pot[best]) best = j;
         s_best = best;
     }
     __syncthreads();

@@ -404,8 +404,8 @@ int at_kmeans_get_option(const at_kmeans_t* h, const char* name);
 int at_kmeans_set_data(at_kmeans_t* h, const float* X, float x_max_abs, at_stream_t stream);
 /* Greedy k-means++ seeding (sklearn's _kmeans_plusplus, n_local_trials = trials = 2 + int(ln K)): uniforms device float64 [K][trials] in [0, 1);
  * the first centre is row floor(uniforms[0][0] N); every later centre c draws candidate rows by searching uniforms[c][t] * total in the float64 inclusive
- * scan of the current closest squared distances and keeps the candidate of the smallest potential sum_i min(d2_i, |x_i - x_cand|^2) (ties to the lower
- * row). Writes C_out device [K][D] and picked_rows device int64 [K]. */
+ * scan of the current closest squared distances and keeps the candidate of the smallest potential sum_i min(d2_i, |x_i - x_cand|^2) (ties to the first
+ * trial, as sklearn). Writes C_out device [K][D] and picked_rows device int64 [K]. */
 int at_kmeans_plusplus(at_kmeans_t* h, const double* uniforms, int trials, float* C_out, int64_t* picked_rows, at_stream_t stream);
 /* E-step: labels device int16 [N] = the nearest centre of every row (the tokenizers' score GEMM + at_op_vq_argmax_refined: exact float64 re-evaluation of
  * near-ties, ties to the lower index). c_max_abs = max |C| sets the centre scale (<= 0: max |X|, a bound for any mean of rows). status_dev (nullable

@@ -1,19 +1,40 @@
 """Float64 numpy restatement of the device k-means (audiotoken_amd/kmeans.py, csrc/kmeans.hip): greedy k-means++ with the same uniforms, Lloyd's E- and
 M-steps, sklearn's relocation of empty clusters (farthest rows first, ties to the lower row; empty clusters in increasing index order) and its tolerance
-rule. ``fp32_centres=True`` rounds every new centre to float32 once, as the device does."""
+rule. ``fp32_centres=True`` rounds every new centre to float32 once, as the device does.
+
+Degenerate data (duplicate rows, fewer distinct rows than K, all rows equal) follows sklearn where sklearn defines the outcome: k-means++ at zero potential
+searches u * 0 = 0 and so picks row 0, as sklearn's searchsorted does; trials of equal potential (duplicate rows) keep the first trial, as
+sklearn's argmin; E-step ties go to the lower centre index (sklearn's strict <). Where sklearn leaves
+the order open (its relocation takes np.argpartition of the distances), the device's documented rule holds: equal distances relocate the lower row first.
+Rows are read in blocks and widened to float64 per block, so float32 data of millions of rows needs no float64 copy."""
 from __future__ import annotations
+
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+_THREADS = 8   # row blocks of the distance passes in parallel (numpy releases the GIL inside them)
 
-def sq_dist_rows(X: np.ndarray, c: np.ndarray) -> np.ndarray:
-    d = X - c[None, :]
-    return np.einsum("ij,ij->i", d, d)
+
+def sq_dist_rows(X: np.ndarray, c: np.ndarray, block: int = 65536) -> np.ndarray:
+    c = np.asarray(c, dtype=np.float64)
+    out = np.empty(X.shape[0], dtype=np.float64)
+
+    def rows(r):
+        d = np.asarray(X[r:r + block], dtype=np.float64) - c[None, :]
+        out[r:r + block] = np.einsum("ij,ij->i", d, d)
+    if X.shape[0] <= block:
+        rows(0)
+    else:
+        with ThreadPoolExecutor(_THREADS) as pool:
+            list(pool.map(rows, range(0, X.shape[0], block)))
+    return out
 
 
 def plusplus(X: np.ndarray, uniforms: np.ndarray):
-    """Greedy k-means++ (sklearn _kmeans_plusplus) on float64 rows. Returns (picked rows, per-step smallest |scan - u total| / total over the trials)."""
-    X = np.asarray(X, dtype=np.float64)
+    """Greedy k-means++ (sklearn _kmeans_plusplus) in float64. Returns (picked rows, per-step smallest |scan - u total| / total over the trials).
+    At zero potential every search is for 0, found at row 0 whatever the rounding: its margin is infinite."""
+    X = np.asarray(X)
     n = X.shape[0]
     k, trials = uniforms.shape
     first = min(int(np.floor(uniforms[0, 0] * n)), n - 1)
@@ -27,12 +48,12 @@ def plusplus(X: np.ndarray, uniforms: np.ndarray):
         ids = np.minimum(np.searchsorted(cs, vals, side="left"), n - 1)
         # how close each search was to a boundary of the scan: a device scan that differs in the last bits can only pick another row below this
         lo = np.where(ids > 0, cs[np.maximum(ids - 1, 0)], 0.0)
-        margins.append(float(np.min(np.minimum(np.abs(cs[ids] - vals), np.abs(vals - lo)) / total)))
+        margins.append(float(np.min(np.minimum(np.abs(cs[ids] - vals), np.abs(vals - lo)) / total)) if total > 0 else np.inf)
         best_pot, best_id, best_d = None, None, None
         for cid in ids:
             d = np.minimum(closest, sq_dist_rows(X, X[cid]))
             pot = d.sum()
-            if best_pot is None or pot < best_pot or (pot == best_pot and cid < best_id):
+            if best_pot is None or pot < best_pot:   # ties to the first trial (sklearn's argmin): duplicate rows tie
                 best_pot, best_id, best_d = pot, int(cid), d
         picked.append(best_id)
         closest = best_d
@@ -53,7 +74,7 @@ def assign(X: np.ndarray, C: np.ndarray, block: int = 8192) -> np.ndarray:
         near = d <= best[:, None] + 1e-9 * np.maximum(np.abs(best)[:, None], 1.0)
         for i in np.where(near.sum(axis=1) > 1)[0]:
             cand = np.where(near[i])[0]
-            ex = np.array([np.sum((xb[i] - C[j]) ** 2) for j in cand])
+            ex = ((xb[i][None, :] - C[cand]) ** 2).sum(axis=1)
             lab[i] = cand[int(np.argmin(ex))]   # first minimum: the lower index on an exact tie
         out[r:r + block] = lab
     return out

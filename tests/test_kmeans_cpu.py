@@ -22,6 +22,61 @@ def test_restatement_matches_sklearn_lloyd():
     assert abs(km.inertia_ - ref["inertia"]) <= 1e-10 * ref["inertia"]
 
 
+class _GivenUniforms:
+    """A stand-in for sklearn's RandomState that hands _kmeans_plusplus the device's uniforms: the first centre floor(u[0, 0] N), then row c of u"""
+
+    def __init__(self, u):
+        self.u, self.c = u, 0
+
+    def choice(self, n, p=None):
+        return min(int(np.floor(self.u[0, 0] * n)), n - 1)
+
+    def uniform(self, size=None):
+        self.c += 1
+        assert size == self.u.shape[1]
+        return self.u[self.c].copy()
+
+
+def test_restatement_degenerate_data_matches_sklearn():
+    """Fewer distinct rows than K (integer rows: every distance is exact in float64, so sklearn's expanded form sees the same ties): k-means++ reaches
+    zero potential and picks row 0 from then on, the E-step gives exact ties to the lower index, and the fit ends with sklearn's partition of the rows,
+    number of distinct clusters and (up to sklearn's own rounding) inertia 0."""
+    sk = pytest.importorskip("sklearn.cluster")
+    from sklearn.cluster import _kmeans
+    rng = np.random.default_rng(7)
+    P = rng.integers(-3, 4, size=(9, 8)).astype(np.float64)
+    P[:, 0] = 8.0 * np.arange(9)
+    X = P[rng.integers(0, 9, size=400)]
+    k = 24
+    u = KM.plusplus_uniforms(k, 3)
+    picked, margins = R.plusplus(X, u)
+    _, sk_picked = _kmeans._kmeans_plusplus(X, k, np.einsum("ij,ij->i", X, X), np.ones(len(X)), _GivenUniforms(u), n_local_trials=u.shape[1])
+    assert np.array_equal(picked, sk_picked)
+    assert len(np.unique(X[picked], axis=0)) == 9 and np.all(picked[9:] == 0) and np.isinf(margins[9:]).all()
+    # all rows equal: zero potential from the second centre on
+    Z = np.zeros((50, 8))
+    z_picked, z_margins = R.plusplus(Z, u)
+    _, sk_z = _kmeans._kmeans_plusplus(Z, k, np.zeros(50), np.ones(50), _GivenUniforms(u), n_local_trials=u.shape[1])
+    assert np.array_equal(z_picked, sk_z) and np.all(z_picked[1:] == 0) and np.isinf(z_margins[1:]).all()
+    # E-step over duplicate centres: sklearn's labels (strict <, the lower index); then the whole fit. sklearn warns about finding fewer distinct
+    # clusters than K.
+    import warnings
+    C = X[picked].astype(np.float32)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        est = sk.KMeans(n_clusters=k, init=C.astype(np.float64), n_init=1, max_iter=1).fit(X)   # fitted attributes for predict(); centres replaced
+        est.cluster_centers_ = C.astype(np.float64)
+        assert np.array_equal(est.predict(X), R.assign(X, C))
+        km = sk.KMeans(n_clusters=k, init=C.astype(np.float64), n_init=1, algorithm="lloyd", max_iter=300, tol=1e-4).fit(X)
+    ref = R.lloyd(X, C, max_iter=300, tol=1e-4, fp32_centres=False)
+    assert ref["inertia"] == 0.0 and km.inertia_ <= 1e-20   # (sklearn's expanded-form inertia leaves ~1e-26)
+    assert len(np.unique(ref["labels"])) == len(np.unique(km.labels_)) == 9
+
+    def partition(lab):
+        return sorted(tuple(np.where(lab == j)[0]) for j in np.unique(lab))
+    assert partition(ref["labels"]) == partition(km.labels_) == partition(np.unique(X, axis=0, return_inverse=True)[1].ravel())
+
+
 def test_restatement_relocates_empty_clusters_like_the_rule():
     rng = np.random.default_rng(1)
     X = rng.normal(size=(200, 8))

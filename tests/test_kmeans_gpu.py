@@ -273,4 +273,6 @@ def test_predict_fewer_rows_than_clusters():
     X, _ = R.mixture(4_000, 64, 32, seed=21, spread=4.0)
     km = KM.KMeans(128, seed=2, max_iter=20, device=DEV).fit(X)
     few = X[:50]
-    assert np.array_equal(km.predict(few).astype(np.int64), km.labels_[:50].astype(np.int64))
+    pred = km.predict(few).astype(np.int64)
+    assert np.array_equal(pred, km.labels_[:50].astype(np.int64))
+    assert np.array_equal(pred, R.assign(few, km.cluster_centers_))

@@ -169,6 +169,48 @@ def test_split_gemm_vs_float64(cuda_device, M, N, K, kernel, scheme):
     assert err.max() <= 1.5e-5 * np.sqrt(K / 1024.0) * max(1.0, np.sqrt((ref ** 2).mean()))
 
 
+@pytest.mark.parametrize("K", [64, 128, 192, 320, 576, 832, 960])
+def test_split_gemm_short_and_odd_k_vs_float64(cuda_device, K):
+    """The split-operand GEMM at the k-means E-step's depths (K = D of the code rows): few K steps against the two-group kernel's 2-step activation
+    ring and 3-step weight ring (K = 64 is two steps, fewer than the ring), and K steps that are not a power of two. Both f16x2 kernels and the
+    bf16x3 kernel, ragged M (one row, 256 +- 1, a 4097-row tail tile and a persistent 256 x 256 walk), NaN-prefilled output, and 5 bit-identical
+    repeats at the largest shape."""
+    lib = _cabi.load()
+    dev = cuda_device
+    big_m = 16400   # N = 2048: 65 x 8 tiles of 256 x 256 on the XCD-ordered persistent walk
+    shapes = [(m, n) for m in (1, 255, 257, 4097) for n in (128, 384, 2048)] + [(big_m, 2048)]
+    x = prng.irwin_hall(f"sgk.x{K}", (big_m, K), 1.0, 3)
+    w = prng.irwin_hall(f"sgk.w{K}", (2048, K), 0.05, 3)
+    b = prng.irwin_hall(f"sgk.b{K}", (2048,), 0.5, 3)
+    xd, wd, bd = torch.from_numpy(x).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(b).to(dev)
+    x64, w64, b64 = x.astype(np.float64), w.astype(np.float64), b.astype(np.float64)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    for M, N in shapes:
+        ref = x64[:M] @ w64[:N].T + b64[:N]
+        bar = 1.5e-5 * np.sqrt(K / 1024.0) * max(1.0, np.sqrt((ref ** 2).mean()))
+        for kernel, scheme in [(1, 1), (2, 1), (2, 0)]:
+            np_ = 3 if scheme == 0 else 2
+            nbytes = ((M + 255) // 256 * 256 + N) * K * np_ * 2
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            reps = 5 if M == big_m else 1
+            first = None
+            for r in range(reps):
+                out = torch.full((M, N), float("nan"), dtype=torch.float32, device=dev)
+                _cabi.check(lib.at_op_gemm_split(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), out.data_ptr(), M, N, K, scheme, float(np.abs(w[:N]).max()),
+                                                 kernel, ws.data_ptr(), nbytes, status.data_ptr(), _cabi.current_stream_handle(dev)), "at_op_gemm_split")
+                torch.cuda.synchronize()
+                assert int(status.item()) == 0
+                if first is None:
+                    first = out
+                    got = out.cpu().numpy().astype(np.float64)
+                    assert np.isfinite(got).all(), f"M={M} N={N} K={K} kernel={kernel} scheme={scheme}: {int((~np.isfinite(got)).sum())} outputs not written"
+                    err = np.abs(got - ref).max()
+                    print(f"split gemm M={M} N={N} K={K} scheme={scheme} kernel={kernel}: max err {err:.2e} (bar {bar:.2e})")
+                    assert err <= bar
+                else:
+                    assert torch.equal(out, first), f"M={M} N={N} K={K} kernel={kernel} scheme={scheme}: run {r} differs from run 0"
+
+
 def test_split_gemm_xcd_order_and_soak(cuda_device):
     """A launch large enough for the 256 x 256 shape WITH the XCD-aware tile order (>= 64 m-tiles), against float64 — every tile must be
     produced exactly once — and 25 repeats that must be bit-identical: the two-group kernel's LDS-DMA ring is a hand-written
