@@ -120,9 +120,28 @@ class AudioToken:
             x = D.probe_batch(self.model_config.model_sample_rate, self.device, self.transform_func)
             self.rank_probe = D.ranks_agree_on_probe(lambda w: self.encoder(w, torch.ones_like(w)), x, dev, dist, str(self.tokenizer_name))
 
-    def encode(self, audio: Union[torch.Tensor, np.ndarray, os.PathLike, bytes, Path], chunk_size: Optional[int] = None) -> torch.Tensor:
+    def stream(self, batch: int = 1):
+        """A streaming acoustic encoder (``AcousticStream``: ``push`` / ``flush`` / ``reset``) for audio that arrives in pieces; the concatenated
+        tokens are those of one-shot ``encode``. The semantic tokenizers are not causal and have no streaming form."""
+        if self.tokenizer_name != Tokenizers.acoustic:
+            raise ValueError(f"streaming is available for Tokenizers.acoustic only (EnCodec is causal); {self.tokenizer_name} has no streaming form")
+        self.load_encoder()
+        return self.encoder.new_stream(batch)
+
+    def encode(self, audio: Union[torch.Tensor, np.ndarray, os.PathLike, bytes, Path], chunk_size: Optional[int] = None,
+               stream: bool = False) -> torch.Tensor:
         """core.py:120-185. ``(1, num_samples)`` array/tensor or a path -> tokens ``(1, K, T)`` on the CPU
-        (``(K, sum T)`` when a path is encoded with ``chunk_size`` — the reference drops the batch dim there)."""
+        (``(K, sum T)`` when a path is encoded with ``chunk_size`` — the reference drops the batch dim there).
+        ``stream=True`` with a path and ``chunk_size`` (acoustic only) pushes the chunks through ONE stream instead of encoding each as a clip of
+        its own: the result is the whole file's ``(1, K, ceil(N/320))`` in the memory of one chunk."""
+        if stream:
+            if not (isinstance(audio, (os.PathLike, Path)) and chunk_size is not None):
+                raise ValueError("stream=True needs a path and a chunk_size (arrays and whole files are encoded one-shot)")
+            from .audio_io import process_audio_chunks
+            st = self.stream(1)
+            parts = [st.push(chunk) for chunk, _ in process_audio_chunks(audio, self.model_config.model_sample_rate, chunk_size)]
+            parts.append(st.flush())
+            return torch.cat([p.cpu() for p in parts], dim=-1)
         self.load_encoder()
         if isinstance(audio, np.ndarray):
             assert audio.ndim == 2, "Audio must be 2D array"

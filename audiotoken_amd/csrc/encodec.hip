@@ -177,6 +177,10 @@ struct at_encodec {
     int sub_batch = at::sub_batch();   // clips per pass through the conv stack: bounds the workspace (option "subbatch")
     bool persistent_lstm = false;   // whole-sequence persistent LSTM (needs one resident workgroup per CU for 256 CUs)
     unsigned lstm_spin_limit = 1u << 18;   // option "lstm_spin_limit": flag polls before a persistent-LSTM workgroup gives up
+    // streaming encode: what the host knows about every state buffer it has reset or written (the state itself is device memory; this is
+    // what lets a push be refused without a device synchronisation)
+    struct StreamInfo { int B = 0; bool started = false, finished = false; };
+    std::map<const void*, StreamInfo> streams;
 };
 
 namespace {
@@ -350,11 +354,16 @@ int launch_status_combine(const unsigned* sync, const int* range_tab, unsigned* 
     return 0;
 }
 
+struct LstmCarry { const float* h_init[2]; const float* c_init[2]; float* c_final[2]; };
+
 int lstm_skip(const float* const wih[2], const float* const whh[2], const float* const bih[2], const float* const bhh[2],
               const float* x, float* xg, float* h0, float* h1, float* c, float* y, int B, int T, hipStream_t stream,
               Profiler& prof, unsigned* sync, bool persistent, int y_elu, const __bf16* const* wih_s = nullptr, __bf16* xs = nullptr,
               bool rec_x3 = false, unsigned spin_limit = 1u << 18, const piece_t* const* wih_f = nullptr, const float* wih_fs = nullptr,
-              int* range_status = nullptr, const float* whh_fs = nullptr, float* xg2 = nullptr) {
+              int* range_status = nullptr, const float* whh_fs = nullptr, float* xg2 = nullptr, const LstmCarry* carry = nullptr) {
+    // carried state (streaming encode): every route starts layer l from (h_init[l], c_init[l]) and leaves its last cell state in c_final[l]; the last
+    // h is row T - 1 of h0 / h1. The three-piece bf16 recurrence has no state variant (lstm_seq_x3.hip): such a call runs the fp32 persistent kernel.
+    if (carry && rec_x3 && !whh_fs) rec_x3 = false;
     // small batches: both layers in one pipelined launch after layer 1's projection (lstm_pipe.hip) — same arithmetic, ~half the dependent steps
     const bool pipe = xg2 && persistent && rec_x3 && whh_fs && wih_f && wih_f[0] && wih_f[1] && wih_fs && xs && lstm_pipe_eligible(B, T);
     for (int layer = 0; layer < 2; ++layer) {
@@ -389,6 +398,8 @@ int lstm_skip(const float* const wih[2], const float* const whh[2], const float*
             q.xg1 = xg; q.w_hh1 = whh[0]; q.b_hh1 = bhh[0]; q.w_ih2 = wih[1]; q.b_ih2 = bih[1]; q.w_hh2 = whh[1]; q.b_hh2 = bhh[1];
             q.h1 = h0; q.xg2 = xg2; q.h2 = h1; q.y_out = y; q.skip = x; q.sync = sync; q.B = B; q.T = T; q.y_elu = y_elu; q.spin_limit = spin_limit;
             q.ws_hh1 = whh_fs[0]; q.ws_ih2 = wih_fs[1]; q.ws_hh2 = whh_fs[1]; q.act_scale = XB_F16_ACT_SCALE;
+            if (carry)
+                for (int l = 0; l < 2; ++l) { q.h_init[l] = carry->h_init[l]; q.c_init[l] = carry->c_init[l]; q.c_final[l] = carry->c_final[l]; }
             prof.begin("lstm_rec", 1, stream);
             if (int rc = launch_lstm_pipe(q, stream)) return rc;
             prof.end(stream);
@@ -405,22 +416,26 @@ int lstm_skip(const float* const wih[2], const float* const whh[2], const float*
                 q.y_out = layer == 1 ? y + ro * kH : nullptr; q.skip = x + ro * kH; q.sync = sync;
                 q.B = (B - c0) < maxc ? (B - c0) : maxc; q.T = T; q.n_groups = 0; q.h_bytes = 0; q.y_elu = y_elu; q.spin_limit = spin_limit;
                 q.w_scale_f16 = (rec_x3 && whh_fs) ? whh_fs[layer] : 0.f;
+                if (carry) { q.h_init = carry->h_init[layer] + (long long)c0 * kH; q.c_init = carry->c_init[layer] + (long long)c0 * kH; q.c_final = carry->c_final[layer] + (long long)c0 * kH; }
                 if (int rc = rec_x3 ? launch_lstm_seq_x3(q, stream) : launch_lstm_seq(q, stream)) return rc;
             }
             prof.end(stream);
             continue;
         }
         prof.begin("lstm_rec", T, stream);
+        if (carry) AT_CHECK_HIP(hipMemcpyAsync(c, carry->c_init[layer], (size_t)B * kH * sizeof(float), hipMemcpyDeviceToDevice, stream));
         for (int t = 0; t < T; ++t) {
             GemmArgs s;
             s.X = hout + (long long)(t > 0 ? t - 1 : 0) * kH; s.x_bstride = 0; s.Tin = B; s.Cin = kH; s.ldx = T * kH;
+            if (carry && t == 0) { s.X = carry->h_init[layer]; s.ldx = kH; }   // h_{-1} = the carried h, [B][512]
             s.W = whh[layer]; s.M = B; s.N = 4 * kH; s.K = kH; s.batch = 1; s.ldc = 4 * kH;
             LstmStepArgs ls;
             ls.xg = xg; ls.b_hh = bhh[layer]; ls.c = c; ls.h_out = hout;
             ls.y_out = layer == 1 ? y : nullptr; ls.skip = x;
-            ls.T = T; ls.t = t; ls.H = kH; ls.first = t == 0; ls.y_elu = y_elu;
+            ls.T = T; ls.t = t; ls.H = kH; ls.first = t == 0 && !carry; ls.y_elu = y_elu;
             if (int rc = launch_lstm_step(s, ls, stream)) return rc;
         }
+        if (carry) AT_CHECK_HIP(hipMemcpyAsync(carry->c_final[layer], c, (size_t)B * kH * sizeof(float), hipMemcpyDeviceToDevice, stream));
         prof.end(stream);
     }
     return 0;
@@ -489,6 +504,59 @@ EncPlan make_plan(int B, int N, int sub) {
     p.off_xs = take(xs_lstm > xs_fin ? xs_lstm : xs_fin);
     p.total_floats = cur;
     return p;
+}
+
+// Streaming encode (at_encodec_encode_stream_checked). State of B streams, floats: the last kStreamCtx consumed samples [B][640], h and c of
+// the two LSTM layers [4][B][512] (h0, c0, h1, c1), the last kStreamHist rows of ELU(lstm + skip) [B][6][512] (the final conv's history).
+// A frame of the LSTM's input depends on samples back to 320 t - 478 (conv0 6, four blocks 2 each at their rate, strided convs 2, 4, 5, 8), so two
+// frames are the smallest frame-aligned context; the first two output frames of a window [context | new] are dropped.
+constexpr int kHop = 320, kStreamCtx = 2 * kHop, kStreamDrop = 2, kStreamHist = 6;
+constexpr int kStreamFirstFrames = 7;   // a stream's first push (unless final) fills the final conv's history and takes its reflected front rows from real rows
+struct StreamState {
+    float *ctx, *h[2], *c[2], *yhist;
+    StreamState(void* base, int B) {
+        ctx = yhist = h[0] = h[1] = c[0] = c[1] = nullptr;
+        if (!base) return;
+        float* f = (float*)base;
+        ctx = f; f += (size_t)B * kStreamCtx;
+        for (int l = 0; l < 2; ++l) { h[l] = f; f += (size_t)B * kH; c[l] = f; f += (size_t)B * kH; }
+        yhist = f;
+    }
+    static size_t floats(int B) { return (size_t)B * (kStreamCtx + 4 * kH + kStreamHist * kH); }
+};
+struct StreamCall { const void* state_in; void* state_out; bool started, final; };
+// The window's plan plus the mid-stream buffers. They live where the plan has room at that moment: the window itself in the (not yet
+// written) gate buffer, everything behind the conv stack in the stage buffers the conv stack has finished with; only when those are too small
+// (a tiny "subbatch" against a large B) behind the plan. So a push needs no more workspace than a one-shot encode of its window.
+struct StreamPlan {
+    EncPlan p;
+    int Tn = 0, Ty = 0, Mpf = 0, Lpf = 0;   // new frames; rows / padded rows / operand rows of the final conv's input [history | new]
+    size_t off_win = 0, off_x4n = 0, off_yw = 0, off_embw = 0, off_yp = 0, off_emb = 0;
+    size_t total_floats = 0;
+};
+StreamPlan make_stream_plan(int B, int n_new, bool started, int sub) {
+    StreamPlan sp;
+    sp.p = make_plan(B, n_new + (started ? kStreamCtx : 0), sub);
+    sp.total_floats = sp.p.total_floats;
+    sp.Tn = sp.p.L[4] - (started ? kStreamDrop : 0);
+    if (!started) return sp;
+    sp.Ty = sp.Tn + kStreamHist;
+    sp.Mpf = (sp.Ty + 255) / 256 * 256;
+    sp.Lpf = sp.Mpf + 8;
+    sp.off_win = sp.p.off_xg;   // B * (640 + n_new) floats <= B * T * 2048
+    size_t cur = 0;
+    auto take = [&](size_t n) { size_t o = cur; cur += (n + 63) / 64 * 64; return o; };
+    sp.off_x4n = take((size_t)B * sp.Tn * kH);
+    sp.off_yw = take((size_t)B * sp.Ty * kH);
+    sp.off_embw = take((size_t)B * sp.Ty * kDim);
+    sp.off_yp = take((size_t)B * sp.Lpf * kH + 64);
+    sp.off_emb = take((size_t)B * sp.Tn * kDim);
+    if (cur > sp.p.off_x4) {   // does not fit the finished stage buffers: behind the plan
+        const size_t base = sp.p.total_floats;
+        sp.off_x4n += base; sp.off_yw += base; sp.off_embw += base; sp.off_yp += base; sp.off_emb += base;
+        sp.total_floats += cur;
+    }
+    return sp;
 }
 
 struct DecPlan {
@@ -886,26 +954,45 @@ size_t at_encodec_workspace_bytes(const at_encodec_t* h, int B, int N) {
     return make_plan(B, N, h ? h->sub_batch : sub_batch()).total_floats * sizeof(float);
 }
 
+// One-shot encode (sc == nullptr) and one push of a stream (sc: N new samples behind the state sc->state_in; see StreamState / StreamPlan).
+// A push is the one-shot sequence on the window [context | new], with three differences once the stream has started: the window's first two
+// frames are dropped in front of the LSTM, the LSTM starts from the carried (h, c), and the final conv runs over [6 carried rows | new rows] and
+// keeps the new rows' outputs. The state is read from state_in and written to state_out only.
 static int encodec_encode_impl(at_encodec_t* h, const float* wav, const float* mask, int B, int N, int n_q, int16_t* codes, int* T_out,
-                               float* emb_out, void* workspace, size_t workspace_bytes, at_stream_t stream_, unsigned* status_out) {
+                               float* emb_out, void* workspace, size_t workspace_bytes, at_stream_t stream_, unsigned* status_out,
+                               const StreamCall* sc = nullptr) {
     (void)mask;  // the reference's AcousticEncoder.forward ignores attention_mask (audiotoken/encoder.py:44-52)
     AT_REQUIRE(h && h->finalized, "model not finalized");
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
     AT_REQUIRE(wav && codes && workspace, "null pointer");
+    const bool mid = sc && sc->started;   // a push behind carried context
+    const int n_new = N;
+    if (mid) N += kStreamCtx;
     AT_REQUIRE(B >= 1 && N >= 10, "need B >= 1 and N >= 10 samples");
     AT_REQUIRE(n_q >= 1 && n_q <= h->n_codebooks, "n_q out of range for the loaded codebooks");
     hipStream_t stream = (hipStream_t)stream_;
-    const EncPlan p = make_plan(B, N, h->sub_batch);
-    AT_REQUIRE(workspace_bytes >= p.total_floats * sizeof(float), "workspace too small");
+    const StreamPlan sp = sc ? make_stream_plan(B, n_new, sc->started, h->sub_batch) : StreamPlan();
+    const EncPlan p = sc ? sp.p : make_plan(B, N, h->sub_batch);
+    AT_REQUIRE(workspace_bytes >= (sc ? sp.total_floats : p.total_floats) * sizeof(float), "workspace too small");
     AT_REQUIRE(p.L[3] > 8, "clip too short for the strided convs");
     float* ws = (float*)workspace;
-    const int T = p.L[4];
-    if (T_out) *T_out = T;
+    const int T = p.L[4];                            // frames of the window
+    const int Tl = mid ? T - kStreamDrop : T;        // frames that reach the LSTM and leave the call
+    if (T_out) *T_out = Tl;
+    const StreamState sin(sc ? const_cast<void*>(sc->state_in) : nullptr, B), sout(sc ? sc->state_out : nullptr, B);
 
     float* x4 = ws + p.off_x4;
     AT_CHECK_HIP(hipMemsetAsync(ws + p.off_sync, 0, 1024 * sizeof(unsigned), stream));   // LSTM flags + the LSTM status word
     AT_CHECK_HIP(hipMemsetAsync(h->range_tab, 0, 64 * sizeof(int), stream));
+    if (sc && (mid || !sc->final)) {
+        // the window [carried context | new samples] for the conv stack, and the next context: the last 640 samples of it
+        h->prof.begin("stream_state", 1, stream);
+        float* win = mid ? ws + sp.off_win : nullptr;
+        if (int rc = launch_stream_window(mid ? sin.ctx : nullptr, mid ? kStreamCtx : 0, wav, n_new, win, sc->final ? nullptr : sout.ctx, kStreamCtx, B, stream)) return rc;
+        h->prof.end(stream);
+        if (mid) wav = win;
+    }
     for (int b0 = 0; b0 < B; b0 += p.G) {
         const int g = (B - b0) < p.G ? (B - b0) : p.G;
         static const char* kRes[4] = {"res0", "res1", "res2", "res3"};
@@ -1060,35 +1147,71 @@ static int encodec_encode_impl(at_encodec_t* h, const float* wav, const float* m
     Profiler& prof = h->prof;
     float* y = ws + p.off_y;
     unsigned* sync = reinterpret_cast<unsigned*>(ws + p.off_sync);   // zeroed at the start of the call (the conv stack's range status lives in it)
-    if (int rc = lstm_skip(h->wih, h->whh, h->bih, h->bhh, x4, ws + p.off_xg, ws + p.off_h0, ws + p.off_h1, ws + p.off_c, y, B, T, stream, prof,
+    const float* xl = x4;   // the LSTM's input [B][Tl][512]
+    LstmCarry carry;
+    if (sc) {
+        for (int l = 0; l < 2; ++l) { carry.h_init[l] = sin.h[l]; carry.c_init[l] = sin.c[l]; carry.c_final[l] = sout.c[l]; }
+        if (mid) {   // drop the window's first two frames: reflect padding has touched them
+            prof.begin("stream_state", 1, stream);
+            if (int rc = launch_copy_rows(x4 + kStreamDrop * kH, (long long)T * kH, ws + sp.off_x4n, (long long)Tl * kH, Tl, kH, B, stream)) return rc;
+            prof.end(stream);
+            xl = ws + sp.off_x4n;
+        }
+    }
+    if (int rc = lstm_skip(h->wih, h->whh, h->bih, h->bhh, xl, ws + p.off_xg, ws + p.off_h0, ws + p.off_h1, ws + p.off_c, y, B, Tl, stream, prof,
                            sync, h->persistent_lstm, 1, h->bf16x3 ? h->wih_s : nullptr, reinterpret_cast<__bf16*>(ws + p.off_xs), h->bf16x3 && h->lstm_x3, h->lstm_spin_limit,
                            (h->bf16x3 && h->ih_f16x2) ? h->wih_f : nullptr, h->wih_fs, h->range_tab + 2 * AS_LSTM_IH, h->lstm_f16x2 ? h->whh_fs : nullptr,
-                           (h->lstm_pipe && B <= kPipeMaxClips) ? ws + p.off_xg2 : nullptr))
+                           (h->lstm_pipe && B <= kPipeMaxClips) ? ws + p.off_xg2 : nullptr, sc ? &carry : nullptr))
         return rc;
-    float* emb = emb_out ? emb_out : ws + p.off_emb;
+    float* emb = emb_out ? emb_out : mid ? ws + sp.off_emb : ws + p.off_emb;
+    // the final conv's input rows yw [B][Ty][512] and its output embw [B][Ty][128]: mid-stream the 6 carried rows stand in front of the new
+    // ones (whatever the kernels reflect in front of THEM only reaches the first 6 outputs, which are not kept)
+    const float* yw = y;
+    float* embw = emb;
+    int Ty = Tl, Mpf = p.Mpf, Lpf = p.Lpf;
+    __bf16* yp = reinterpret_cast<__bf16*>(ws + p.off_xs);
+    if (mid) {
+        Ty = sp.Ty; Mpf = sp.Mpf; Lpf = sp.Lpf;
+        float* ywm = ws + sp.off_yw;
+        prof.begin("stream_state", 2, stream);
+        if (int rc = launch_copy_rows(sin.yhist, (long long)kStreamHist * kH, ywm, (long long)Ty * kH, kStreamHist, kH, B, stream)) return rc;
+        if (int rc = launch_copy_rows(y, (long long)Tl * kH, ywm + kStreamHist * kH, (long long)Ty * kH, Tl, kH, B, stream)) return rc;
+        prof.end(stream);
+        yw = ywm; embw = ws + sp.off_embw; yp = reinterpret_cast<__bf16*>(ws + sp.off_yp);
+    }
     prof.begin("final_conv", 1, stream);
-    if (h->bf16x3 && h->fin_f16x2 && h->fin_f && T > 6) {
+    if (h->bf16x3 && h->fin_f16x2 && h->fin_f && Ty > 6) {
         // y = ELU(lstm + skip) -> two fp16 pieces in windowed layout (6 reflected front rows), then the k = 7 conv as a windowed split GEMM
-        __bf16* yp = reinterpret_cast<__bf16*>(ws + p.off_xs);
         int* range_status = h->range_tab + 2 * AS_FINAL;
-        if (int rc = launch_split_windowed(y, B, T, kH, 1, 6, p.Lpf, yp, stream, XB_SCHEME_F16X2, XB_F16_ACT_SCALE, range_status)) return rc;
+        if (int rc = launch_split_windowed(yw, B, Ty, kH, 1, 6, Lpf, yp, stream, XB_SCHEME_F16X2, XB_F16_ACT_SCALE, range_status)) return rc;
         Bf16x3Args fa;
         fa.A = yp; fa.W = h->fin_f; fa.bias = h->fin.b;
-        fa.M = T; fa.Mpad = p.Mpf; fa.N = kDim; fa.K = 7 * kH;
-        fa.batch = B; fa.stride = 1; fa.cblocks = kH / 16; fa.Lp = p.Lpf;
+        fa.M = Ty; fa.Mpad = Mpf; fa.N = kDim; fa.K = 7 * kH;
+        fa.batch = B; fa.stride = 1; fa.cblocks = kH / 16; fa.Lp = Lpf;
         fa.scheme = XB_SCHEME_F16X2; fa.acc_scale = 1.0f / (XB_F16_ACT_SCALE * h->fin_fs); fa.split_scale = XB_F16_ACT_SCALE; fa.status = range_status;
-        fa.epi = XB_EPI_LINEAR; fa.C = emb; fa.ldc = kDim;
+        fa.epi = XB_EPI_LINEAR; fa.C = embw; fa.ldc = kDim;
         if (int rc = launch_gemm_bf16x3(fa, stream)) return rc;
-    } else if (int rc = conv_gemm(h->fin, y, (long long)T * kH, T, emb, (long long)T * kDim, T, B, PRO_NONE, nullptr, 0, stream)) {  // y holds ELU(lstm + skip)
+    } else if (int rc = conv_gemm(h->fin, yw, (long long)Ty * kH, Ty, embw, (long long)Ty * kDim, Ty, B, PRO_NONE, nullptr, 0, stream)) {  // y holds ELU(lstm + skip)
         return rc;
     }
     prof.end(stream);
+    if (sc) {
+        prof.begin("stream_state", (mid ? 1 : 0) + (sc->final ? 0 : 3), stream);
+        if (mid)   // keep the new rows' outputs
+            if (int rc = launch_copy_rows(embw + kStreamHist * kDim, (long long)Ty * kDim, emb, (long long)Tl * kDim, Tl, kDim, B, stream)) return rc;
+        if (!sc->final) {   // the next push's state: the last 6 conv input rows and the last h of both layers (c: written by the LSTM, context: above)
+            if (int rc = launch_copy_rows(yw + (long long)(Ty - kStreamHist) * kH, (long long)Ty * kH, sout.yhist, (long long)kStreamHist * kH, kStreamHist, kH, B, stream)) return rc;
+            if (int rc = launch_copy_rows(ws + p.off_h0 + (long long)(Tl - 1) * kH, (long long)Tl * kH, sout.h[0], kH, 1, kH, B, stream)) return rc;
+            if (int rc = launch_copy_rows(ws + p.off_h1 + (long long)(Tl - 1) * kH, (long long)Tl * kH, sout.h[1], kH, 1, kH, B, stream)) return rc;
+        }
+        prof.end(stream);
+    }
     prof.begin("rvq", 1, stream);
     const bool rf = h->rvq_f16x2 && h->cb_f;
     int rc = (h->rvq_x3 && h->bf16x3 && h->cb_s)
-                 ? launch_rvq_encode_x3(emb, (long long)B * T, T, h->codebooks, rf ? h->cb_f : h->cb_s, (long long)h->n_codebooks * kCodes * kDim, h->e2, n_q,
+                 ? launch_rvq_encode_x3(emb, (long long)B * Tl, Tl, h->codebooks, rf ? h->cb_f : h->cb_s, (long long)h->n_codebooks * kCodes * kDim, h->e2, n_q,
                                         codes, stream, rf ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, XB_F16_ACT_SCALE, h->cb_fs, h->range_tab + 2 * AS_RVQ)
-                 : launch_rvq_encode(emb, (long long)B * T, T, h->codebooks, h->e2, n_q, codes, stream);
+                 : launch_rvq_encode(emb, (long long)B * Tl, Tl, h->codebooks, h->e2, n_q, codes, stream);
     prof.end(stream);
     if (rc) return rc;
     if (status_out) return launch_status_combine(sync, h->range_tab, status_out, stream);   // LSTM hand-off + every range verdict of the call, RVQ included
@@ -1103,6 +1226,61 @@ int at_encodec_encode(at_encodec_t* h, const float* wav, const float* mask, int 
 int at_encodec_encode_checked(at_encodec_t* h, const float* wav, const float* mask, int B, int N, int n_q, int16_t* codes, int* T_out,
                               float* emb_out, void* workspace, size_t workspace_bytes, at_stream_t stream, uint32_t* status_dev) {
     return encodec_encode_impl(h, wav, mask, B, N, n_q, codes, T_out, emb_out, workspace, workspace_bytes, stream, status_dev);
+}
+
+size_t at_encodec_stream_state_bytes(const at_encodec_t* h, int B) {
+    (void)h;
+    return B >= 1 ? StreamState::floats(B) * sizeof(float) : 0;
+}
+
+int at_encodec_stream_reset(at_encodec_t* h, void* state_dev, int B, at_stream_t stream) {
+    AT_REQUIRE(h && h->finalized, "model not finalized");
+    AT_REQUIRE(state_dev && B >= 1, "at_encodec_stream_reset: null state or B < 1");
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    AT_CHECK_HIP(hipMemsetAsync(state_dev, 0, StreamState::floats(B) * sizeof(float), (hipStream_t)stream));   // h = c = 0
+    at_encodec::StreamInfo info;
+    info.B = B;
+    h->streams[state_dev] = info;
+    return 0;
+}
+
+size_t at_encodec_stream_workspace_bytes(const at_encodec_t* h, int B, int n_new) {
+    if (B <= 0 || n_new <= 0) return 0;
+    const int sub = h ? h->sub_batch : sub_batch();
+    const size_t a = make_stream_plan(B, n_new, true, sub).total_floats, b = make_stream_plan(B, n_new, false, sub).total_floats;
+    return (a > b ? a : b) * sizeof(float);
+}
+
+int at_encodec_encode_stream_checked(at_encodec_t* h, const void* state_in, void* state_out, const float* wav_new, int B, int n_new, int final,
+                                     int n_q, int16_t* codes, int* T_out, float* emb_out, void* workspace, size_t workspace_bytes,
+                                     at_stream_t stream, uint32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized, "model not finalized");
+    AT_REQUIRE(state_in && state_out, "at_encodec_encode_stream_checked: null state");
+    AT_REQUIRE(state_in != state_out, "at_encodec_encode_stream_checked: state_in and state_out must be two buffers (a failed push is repeated from state_in)");
+    AT_REQUIRE(B >= 1 && n_new >= 0, "at_encodec_encode_stream_checked: need B >= 1 and n_new >= 0");
+    const auto it = h->streams.find(state_in);
+    AT_REQUIRE(it != h->streams.end(), "at_encodec_encode_stream_checked: state_in was neither reset (at_encodec_stream_reset) nor written by a push of this handle");
+    const at_encodec::StreamInfo in = it->second;
+    AT_REQUIRE(in.B == B, "at_encodec_encode_stream_checked: the state was reset for another B");
+    AT_REQUIRE(!in.finished, "at_encodec_encode_stream_checked: push after the final push (reset the stream first)");
+    AT_REQUIRE(final || (n_new > 0 && n_new % kHop == 0), "at_encodec_encode_stream_checked: n_new must be a positive multiple of 320 unless final");
+    AT_REQUIRE(final || in.started || n_new >= kStreamFirstFrames * kHop, "at_encodec_encode_stream_checked: the first push of a stream needs at least 7 frames (2240 samples) unless final");
+    at_encodec::StreamInfo out = in;
+    out.started = true;
+    out.finished = final != 0;
+    if (n_new == 0) {   // a final push without samples: the stream ends on a frame boundary, nothing is left to emit
+        if (T_out) *T_out = 0;
+        if (status_dev) AT_CHECK_HIP(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), (hipStream_t)stream));
+        h->streams[state_out] = out;
+        return 0;
+    }
+    const StreamCall sc{state_in, state_out, in.started, final != 0};
+    int T = 0;
+    if (int rc = encodec_encode_impl(h, wav_new, nullptr, B, n_new, n_q, codes, &T, emb_out, workspace, workspace_bytes, stream, status_dev, &sc)) return rc;
+    if (T_out) *T_out = T;
+    h->streams[state_out] = out;
+    return 0;
 }
 
 namespace {

@@ -30,6 +30,11 @@ struct LstmSeqArgs {
     long long h_bytes;   // filled by the launcher
     unsigned spin_limit = 1u << 18;   // polls of a hand-off flag before a workgroup gives up (~0.1-0.3 s; normal waits are microseconds)
     float w_scale_f16 = 0.f;          // lstm_seq_x3 only: > 0 = two-piece fp16 scheme with W_hh scaled by this power of two; 0 = three bf16 pieces
+    // carried state (streaming encode), all three or none, [B][512] each: the layer starts from (h_init, c_init) instead of zeros and stores its
+    // last cell state to c_final (the last h is row T - 1 of h_out). c_final may not alias c_init.
+    const float* h_init = nullptr;
+    const float* c_init = nullptr;
+    float* c_final = nullptr;
 };
 int launch_lstm_seq(const LstmSeqArgs& a, hipStream_t stream);
 int lstm_seq_max_clips();
@@ -56,6 +61,10 @@ struct LstmPipeArgs {
     unsigned spin_limit = 1u << 18;
     float ws_hh1 = 0.f, ws_ih2 = 0.f, ws_hh2 = 0.f;   // finalize-time power-of-two scales of the three weight matrices
     float act_scale = 0.f;                            // activation scale of the projection GEMM this launch stands in for (XB_F16_ACT_SCALE)
+    // carried state per layer (roles A and B), all six or none: as LstmSeqArgs
+    const float* h_init[2] = {nullptr, nullptr};
+    const float* c_init[2] = {nullptr, nullptr};
+    float* c_final[2] = {nullptr, nullptr};
 };
 int launch_lstm_pipe(const LstmPipeArgs& a, hipStream_t stream);
 int lstm_pipe_max_clips();
@@ -169,6 +178,12 @@ int launch_seanet_dectail(const DecTailArgs& a, hipStream_t stream);
 int launch_seanet_dectail_x2(const DecTailArgs& a, hipStream_t stream);
 // Same block at 128 channels (seanet_res128.hip): x [B][L][128] -> out [B][L][128]; w3 [64][3*128], wt [128][64 + 128]
 int launch_seanet_res128(const Res64Args& a, hipStream_t stream);
+
+// Streaming encode, state gather / scatter (encodec_kernels.hip). launch_stream_window: per clip the virtual sequence v = [ctx_in (ctx_len samples) |
+// wav (n_new samples)]; win (optional) [B][ctx_len + n_new] receives v, ctx_out (optional) [B][out_len] its last out_len samples.
+int launch_stream_window(const float* ctx_in, int ctx_len, const float* wav, int n_new, float* win, float* ctx_out, int out_len, int B, hipStream_t stream);
+// dst[b][r][0..C) = src[b][r][0..C) for r < rows, b < B; clip strides in floats; C a multiple of 4, both bases 16-byte aligned
+int launch_copy_rows(const float* src, long long src_bstride, float* dst, long long dst_bstride, int rows, int C, int B, hipStream_t stream);
 
 int launch_conv0(const float* wav, const float* w, const float* bias, float* out, int B, int N, hipStream_t stream);
 int launch_lstm_step(const GemmArgs& a, const LstmStepArgs& s, hipStream_t stream);

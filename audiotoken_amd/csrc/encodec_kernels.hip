@@ -46,6 +46,50 @@ int launch_conv0(const float* wav, const float* w, const float* bias, float* out
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Streaming encode: the window [carried context | new samples] and the next context (scalar loads: n_new may be odd on the
+// final push), and a strided row copy (float4) that gathers / scatters the LSTM input, the final conv's history and the last h.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void stream_window_kernel(const float* ctx_in, int ctx_len, const float* wav, int n_new, float* win,
+                                                            float* ctx_out, int out_len, long long n_win, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int len = ctx_len + n_new;
+    const bool to_win = i < n_win;
+    const long long e = to_win ? i : i - n_win;
+    const int per = to_win ? len : out_len;
+    const int b = (int)(e / per), k = (int)(e - (long long)b * per);
+    const int pos = to_win ? k : len - out_len + k;   // position in [ctx | wav]; the launcher checks len >= out_len
+    const float v = pos < ctx_len ? ctx_in[(long long)b * ctx_len + pos] : wav[(long long)b * n_new + (pos - ctx_len)];
+    if (to_win) win[i] = v; else ctx_out[e] = v;
+}
+
+int launch_stream_window(const float* ctx_in, int ctx_len, const float* wav, int n_new, float* win, float* ctx_out, int out_len, int B, hipStream_t stream) {
+    AT_REQUIRE(wav && B >= 1 && n_new >= 1 && ctx_len >= 0 && (ctx_len == 0 || ctx_in), "stream_window: bad arguments");
+    AT_REQUIRE(!ctx_out || ctx_len + n_new >= out_len, "stream_window: fewer samples than the context holds");
+    const long long n_win = win ? (long long)B * (ctx_len + n_new) : 0, total = n_win + (ctx_out ? (long long)B * out_len : 0);
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, ctx_in, ctx_len, wav, n_new, win, ctx_out, out_len, n_win, total);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void copy_rows_kernel(const float* src, long long src_bstride, float* dst, long long dst_bstride, long long per_clip4, long long total4) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const long long b = i / per_clip4, k = i - b * per_clip4;
+    *reinterpret_cast<f4*>(dst + b * dst_bstride + k * 4) = *reinterpret_cast<const f4*>(src + b * src_bstride + k * 4);
+}
+
+int launch_copy_rows(const float* src, long long src_bstride, float* dst, long long dst_bstride, int rows, int C, int B, hipStream_t stream) {
+    AT_REQUIRE(src && dst && rows >= 1 && B >= 1 && C >= 4 && C % 4 == 0 && src_bstride % 4 == 0 && dst_bstride % 4 == 0, "copy_rows: bad arguments");
+    AT_REQUIRE((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16 == 0, "copy_rows: unaligned buffer");
+    const long long per_clip4 = (long long)rows * C / 4, total4 = per_clip4 * B;
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, src, src_bstride, dst, dst_bstride, per_clip4, total4);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------
 // LSTM step: gates[B][2048] = h_{t-1} W_hh^T + b_hh + xg[:, t, :]; pointwise cell update fused as the epilogue.
 // Gate columns are interleaved at load time (column 4*j + g, g in i,f,g,o) so that the 4 accumulator
 // registers of a lane are the 4 gates of hidden unit j of one clip.

@@ -36,6 +36,10 @@ constexpr int LP_MAX_GROUPS = 5;
 constexpr int LP_XLD = 132;                    // row stride (floats) of role X's gathered [16 clips][128 gate values]
 constexpr float LP_H_SCALE = 16384.0f;         // recurrent products: h (|h| < 1) split as h * 2^14 (lstm_seq_x3.hip)
 
+// ST = carried state (streaming encode): roles A and B stage their layer's a.h_init[layer] [B][512] at step 0 and run the recurrent product as
+// a t > 0 step does (no wait for it: written before the launch), start the cell state from a.c_init[layer] and store it to a.c_final[layer]
+// after the last step. Role X has no state. ST = false is the kernel as it was.
+template <bool ST>
 __global__ __launch_bounds__(512, 1) void lstm_pipe_kernel(LstmPipeArgs a) {
     typedef SchemeF16x2 SC;
     typedef typename SC::T PT;
@@ -87,6 +91,7 @@ __global__ __launch_bounds__(512, 1) void lstm_pipe_kernel(LstmPipeArgs a) {
     const long long own_row = (long long)(clip_ok ? clip : a.B - 1) * T;
     const f4 bv = *reinterpret_cast<const f4*>(bias + unit * 4);
     float cst = 0.f;
+    if (ST && !is_x) cst = a.c_init[is_b ? 1 : 0][(long long)(clip_ok ? clip : a.B - 1) * LP_H + unit];
     // staging source: A and X read layer 1's h, B layer 2's; A / B publish into their own layer's buffer
     float* h_own = is_b ? a.h2 : a.h1;
     const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc((void*)(is_b ? a.h2 : a.h1), 0, (int)a.h_bytes, 0x00020000);
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(512, 1) void lstm_pipe_kernel(LstmPipeArgs a) {
         if (is_b) skipv = a.skip[(own_row + t) * LP_H + unit];
         __builtin_amdgcn_sched_barrier(0);
         f4 acc = {0.f, 0.f, 0.f, 0.f};
-        const bool stage_h = is_x || t > 0;
+        const bool stage_h = ST || is_x || t > 0;
         if (role != 0 || t > 0) {
             if (wave == 0) {
                 // lanes 0..15: the 16 step counters of the chain this role follows (X needs step t of A, i.e. counter >= t + 1);
@@ -149,7 +154,15 @@ __global__ __launch_bounds__(512, 1) void lstm_pipe_kernel(LstmPipeArgs a) {
             u4 stage[NST];
             const int toff = (is_x ? t : t - 1) * (LP_H * 4);
 #pragma unroll
-            for (int j = 0; j < NST; ++j) stage[j] = __builtin_amdgcn_raw_buffer_load_b128(src, g_off[j] + toff, 0, 16);
+            for (int j = 0; j < NST; ++j) {
+                if (ST && !is_x && t == 0) {   // carried h: plain loads, written before the launch
+                    const int row = (tid >> 7) + 4 * j;
+                    const int cb = b0 + row < a.B ? b0 + row : a.B - 1;
+                    stage[j] = *reinterpret_cast<const u4*>(a.h_init[is_b ? 1 : 0] + (long long)cb * LP_H + (tid & 127) * 4);
+                } else {
+                    stage[j] = __builtin_amdgcn_raw_buffer_load_b128(src, g_off[j] + toff, 0, 16);
+                }
+            }
 #pragma unroll
             for (int j = 0; j < NST; ++j) {
                 const f4 hv = {__uint_as_float(stage[j][0]), __uint_as_float(stage[j][1]), __uint_as_float(stage[j][2]), __uint_as_float(stage[j][3])};
@@ -204,6 +217,7 @@ __global__ __launch_bounds__(512, 1) void lstm_pipe_kernel(LstmPipeArgs a) {
             const float c_new = __fadd_rn(__fmul_rn(fg, cst), __fmul_rn(ig, cg));
             const float hn = og * lstm_tanh(c_new);
             cst = c_new;
+            if (ST && t == T - 1 && clip_ok) a.c_final[is_b ? 1 : 0][(long long)clip * LP_H + unit] = c_new;
             Hx[r16][wave * 4 + q] = hn;
             if (is_b) {
                 const float yv = hn + skipv;
@@ -261,8 +275,18 @@ int launch_lstm_pipe(const LstmPipeArgs& a_in, hipStream_t stream) {
     a.xg_bytes = a.h_bytes * 4;
     AT_CHECK_HIP(hipMemsetAsync(a.sync + LP_FLAGS, 0, 3 * LP_MAX_GROUPS * LP_FLAG_STRIDE * sizeof(unsigned), stream));
     const size_t lds = (size_t)2 * LP_HP * 2;
-    { static LdsAttrFlags lds_attr; if (int rc = set_max_dynamic_lds(lds_attr, lstm_pipe_kernel, lds)) return rc; }
-    hipLaunchKernelGGL(lstm_pipe_kernel, dim3(3 * a.n_groups * LP_SLICES), dim3(512), lds, stream, a);
+    const bool st = a.h_init[0] != nullptr;
+    for (int l = 0; l < 2; ++l)
+        AT_REQUIRE(st == (a.h_init[l] != nullptr) && st == (a.c_init[l] != nullptr) && st == (a.c_final[l] != nullptr), "lstm_pipe: h_init, c_init and c_final of both layers go together");
+    if (st) {
+        static LdsAttrFlags lds_attr_st;
+        if (int rc = set_max_dynamic_lds(lds_attr_st, lstm_pipe_kernel<true>, lds)) return rc;
+        hipLaunchKernelGGL(lstm_pipe_kernel<true>, dim3(3 * a.n_groups * LP_SLICES), dim3(512), lds, stream, a);
+    } else {
+        static LdsAttrFlags lds_attr;
+        if (int rc = set_max_dynamic_lds(lds_attr, lstm_pipe_kernel<false>, lds)) return rc;
+        hipLaunchKernelGGL(lstm_pipe_kernel<false>, dim3(3 * a.n_groups * LP_SLICES), dim3(512), lds, stream, a);
+    }
     AT_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -48,6 +48,10 @@ constexpr int LS_MAX_GROUPS = 16;
 
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
+// ST = carried state (streaming encode): step 0 stages a.h_init [B][512] and runs the recurrent product as a t > 0 step does, without a flag
+// wait (h_init was written before the launch); the cell state starts from a.c_init and the last step stores it to a.c_final. ST = false is
+// the kernel as it was.
+template <bool ST>
 __global__ __launch_bounds__(256, 2) void lstm_seq_kernel(LstmSeqArgs a) {
     extern __shared__ __attribute__((aligned(16))) float Hs[];   // [16 clips][512], 16-B chunk ^= clip & 15
     __shared__ int abort_s;
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void lstm_seq_kernel(LstmSeqArgs a) {
     const int unit = slice * 16 + wave * 4 + q;
     const int col = unit * 4;
     const f4 bhh = *reinterpret_cast<const f4*>(a.b_hh + col);
-    float cst = 0.f;
+    float cst = ST ? a.c_init[(long long)(clip_ok ? clip : a.B - 1) * LS_H + unit] : 0.f;
     // h_{t-1} staging: thread -> 8 x (clip row, 16-B chunk) of the [16][512] tile: e = tid + 256*j -> row = e >> 7,
     // chunk = tid & 127. Rows beyond B are clamped (their gates are computed on a copy of the last clip, never stored).
     const __amdgpu_buffer_rsrc_t hrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.h_out, 0, (int)a.h_bytes, 0x00020000);
@@ -100,9 +104,9 @@ __global__ __launch_bounds__(256, 2) void lstm_seq_kernel(LstmSeqArgs a) {
         if (a.y_out) skipv = a.skip[(own_row + t) * LS_H + unit];
         __builtin_amdgcn_sched_barrier(0);   // keep these loads in front of the wait: their latency hides behind it
         f4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (t > 0) {
+        if (ST || t > 0) {
             // ---- wait until all 32 slices of this group have published h_{t-1} ---------------------------
-            if (wave == 0) {
+            if (wave == 0 && (!ST || t > 0)) {
                 const unsigned target = (unsigned)t;
                 unsigned spins = 0;
                 int give_up = 0;
@@ -120,12 +124,20 @@ __global__ __launch_bounds__(256, 2) void lstm_seq_kernel(LstmSeqArgs a) {
                 }
             }
             __syncthreads();       // also: every wave has finished reading the previous step's Hs
-            if (abort_s) return;   // uniform: a member of the group is not making progress (e.g. not resident)
+            if ((!ST || t > 0) && abort_s) return;   // uniform: a member of the group is not making progress (e.g. not resident)
             // ---- h_{t-1} [32][512] -> LDS: sc1 loads straight to registers, then ds_write ---------------------------
             u4 stage[8];
             const int toff = (t - 1) * (LS_H * 4);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) stage[j] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, g_off[j] + toff, 0, 16);   // aux 16 = sc1
+            for (int j = 0; j < 8; ++j) {
+                if (ST && t == 0) {   // carried h: plain loads, written before the launch
+                    const int row = (tid >> 7) + 2 * j;
+                    const int cb = b0 + row < a.B ? b0 + row : a.B - 1;
+                    stage[j] = *reinterpret_cast<const u4*>(a.h_init + (long long)cb * LS_H + (tid & 127) * 4);
+                } else {
+                    stage[j] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, g_off[j] + toff, 0, 16);   // aux 16 = sc1
+                }
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) *reinterpret_cast<u4*>(Hs + l_off[j]) = stage[j];
             __syncthreads();
@@ -151,6 +163,7 @@ __global__ __launch_bounds__(256, 2) void lstm_seq_kernel(LstmSeqArgs a) {
             const float c_new = __fadd_rn(__fmul_rn(fg, cst), __fmul_rn(ig, cg));
             hn = og * lstm_tanh(c_new);
             cst = c_new;
+            if (ST && t == T - 1 && clip_ok) a.c_final[(long long)clip * LS_H + unit] = c_new;
             if (clip_ok)
                 __hip_atomic_store(reinterpret_cast<unsigned*>(a.h_out) + (own_row + t) * LS_H + unit, __float_as_uint(hn),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through (sc1): no release fence needed
@@ -178,8 +191,8 @@ int lstm_seq_max_clips() {
         int cus = 0, per_cu = 0;
         const size_t lds = (size_t)LS_H_FLOATS * sizeof(float);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_seq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(lstm_seq_kernel), 256, lds) != hipSuccess) per_cu = 1;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_seq_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(lstm_seq_kernel<false>), 256, lds) != hipSuccess) per_cu = 1;
         int groups = (cus * (per_cu < 1 ? 1 : per_cu)) / LS_SLICES;
         groups = groups > LS_MAX_GROUPS ? LS_MAX_GROUPS : groups;
         cached[dev] = (groups < 1 ? 1 : groups) * LS_CLIPS;   // < 32 resident workgroups cannot run even one group: the status word reports it
@@ -194,9 +207,18 @@ int launch_lstm_seq(const LstmSeqArgs& a_in, hipStream_t stream) {
     a.h_bytes = (long long)a.B * a.T * LS_H * 4;
     AT_REQUIRE(a.h_bytes < (1ll << 31), "lstm_seq: h buffer exceeds the 2 GB buffer-descriptor range");
     const size_t lds = (size_t)LS_H_FLOATS * sizeof(float);
-    { static LdsAttrFlags lds_attr_0; if (int rc = set_max_dynamic_lds(lds_attr_0, lstm_seq_kernel, lds)) return rc; }
+    const bool st = a.h_init != nullptr;
+    AT_REQUIRE(st == (a.c_init != nullptr) && st == (a.c_final != nullptr), "lstm_seq: h_init, c_init and c_final go together");
     AT_CHECK_HIP(hipMemsetAsync(a.sync + LS_FLAGS, 0, LS_MAX_GROUPS * LS_SLICES * sizeof(unsigned), stream));   // flags, every launch
-    hipLaunchKernelGGL(lstm_seq_kernel, dim3(a.n_groups * LS_SLICES), dim3(256), lds, stream, a);
+    if (st) {
+        static LdsAttrFlags lds_attr_1;
+        if (int rc = set_max_dynamic_lds(lds_attr_1, lstm_seq_kernel<true>, lds)) return rc;
+        hipLaunchKernelGGL(lstm_seq_kernel<true>, dim3(a.n_groups * LS_SLICES), dim3(256), lds, stream, a);
+    } else {
+        static LdsAttrFlags lds_attr_0;
+        if (int rc = set_max_dynamic_lds(lds_attr_0, lstm_seq_kernel<false>, lds)) return rc;
+        hipLaunchKernelGGL(lstm_seq_kernel<false>, dim3(a.n_groups * LS_SLICES), dim3(256), lds, stream, a);
+    }
     AT_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -53,8 +53,11 @@ constexpr int LX_MAX_GROUPS = 16;
 __device__ __forceinline__ f4 lx_mfma(bf16x8 w, bf16x8 x, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0); }
 __device__ __forceinline__ f4 lx_mfma(f16x8 w, f16x8 x, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, x, c, 0, 0, 0); }
 
-// 8 waves, one 16-row tile each (two waves per SIMD); SC = operand scheme; w_scale / h_scale / acc_scale: the fp16 scheme's powers of two
-template <class SC>
+// 8 waves, one 16-row tile each (two waves per SIMD); SC = operand scheme; w_scale / h_scale / acc_scale: the fp16 scheme's powers of two.
+// ST = carried state (streaming encode): step 0 stages a.h_init [B][512] instead of skipping the recurrent product — the same split, product
+// order and rescale as a t > 0 step, without a flag wait (h_init was written before the launch) —, the cell state starts from a.c_init and
+// is stored to a.c_final behind the time loop. ST = false is the kernel as it was, instruction for instruction.
+template <class SC, bool ST>
 __global__ __launch_bounds__(512, 1) void lstm_seq_x3_kernel(LstmSeqArgs a, float w_scale, float h_scale, float acc_scale) {
     typedef typename SC::T PT;
     typedef typename SC::V8 V8;
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(512, 1) void lstm_seq_x3_kernel(LstmSeqArgs a, floa
     f4 bhh[NJ];
     float cst[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) cst[j] = 0.f;
+    for (int j = 0; j < NJ; ++j) cst[j] = ST ? a.c_init[(long long)(clip_ok ? clip : a.B - 1) * LX_H + unit[j]] : 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) bhh[j] = *reinterpret_cast<const f4*>(a.b_hh + unit[j] * 4);
     // h_{t-1} staging: thread -> 8 x (clip row, 16-B chunk) of the [16][512] tile: e = tid + 256*j -> row = e >> 7, chunk = tid & 127
@@ -141,9 +144,9 @@ __global__ __launch_bounds__(512, 1) void lstm_seq_x3_kernel(LstmSeqArgs a, floa
         f4 acc[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[j] = f4{0.f, 0.f, 0.f, 0.f};
-        if (t > 0) {
+        if (ST || t > 0) {
             // ---- wait until all 16 slices of this group have published h_{t-1} (protocol: lstm_seq.hip) -------------------------
-            if (wave == 0) {
+            if (wave == 0 && (!ST || t > 0)) {
                 const unsigned target = (unsigned)t;
                 unsigned spins = 0;
                 int give_up = 0;
@@ -161,14 +164,24 @@ __global__ __launch_bounds__(512, 1) void lstm_seq_x3_kernel(LstmSeqArgs a, floa
                 }
             }
             __syncthreads();       // also: every wave has finished reading the previous step's pieces
-            if (abort_s) return;   // uniform: a member of the group is not making progress
+            if ((!ST || t > 0) && abort_s) return;   // uniform: a member of the group is not making progress
             LX_STAMP(1);
             LX_STAMP(2);
             // ---- h_{t-1} [16][512] -> sc1 loads to registers -> split -> LDS pieces -----------------------------------------------
             u4 stage[NST];
             const int toff = (t - 1) * (LX_H * 4);
+            if (ST && t == 0) {   // carried h [B][512]: plain loads, written before the launch
+                const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.h_init, 0, a.B * LX_H * 4, 0x00020000);
 #pragma unroll
-            for (int j = 0; j < NST; ++j) stage[j] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, g_off[j] + toff, 0, 16);   // aux 16 = sc1
+                for (int j = 0; j < NST; ++j) {
+                    const int row = (tid >> 7) + (NTHR / 128) * j;
+                    const int cb = b0 + row < a.B ? b0 + row : a.B - 1;
+                    stage[j] = __builtin_amdgcn_raw_buffer_load_b128(irsrc, (cb * LX_H + (tid & 127) * 4) * 4, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NST; ++j) stage[j] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, g_off[j] + toff, 0, 16);   // aux 16 = sc1
+            }
 #pragma unroll
             for (int j = 0; j < NST; ++j) {
                 const f4 hv = {__uint_as_float(stage[j][0]), __uint_as_float(stage[j][1]), __uint_as_float(stage[j][2]), __uint_as_float(stage[j][3])};
@@ -261,6 +274,10 @@ __global__ __launch_bounds__(512, 1) void lstm_seq_x3_kernel(LstmSeqArgs a, floa
             }
         }
     }
+    if (ST && clip_ok) {   // the carried cell state of the next push
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) a.c_final[(long long)clip * LX_H + unit[j]] = cst[j];
+    }
 }
 
 // clips one launch can take: all workgroups must be resident (one per CU), 16 per group of 16 clips
@@ -278,11 +295,11 @@ int lstm_seq_x3_max_clips() {
     return cached[dev];
 }
 
-template <class SC>
+template <class SC, bool ST>
 static int launch_lx(const LstmSeqArgs& a, float w_scale, float h_scale, hipStream_t stream) {
     const size_t lds = (size_t)SC::NP * LX_HP * 2;
-    { static LdsAttrFlags lds_attr; if (int rc = set_max_dynamic_lds(lds_attr, lstm_seq_x3_kernel<SC>, lds)) return rc; }
-    hipLaunchKernelGGL(lstm_seq_x3_kernel<SC>, dim3(a.n_groups * LX_SLICES), dim3(512), lds, stream, a, w_scale, h_scale, 1.0f / (w_scale * h_scale));
+    { static LdsAttrFlags lds_attr; if (int rc = set_max_dynamic_lds(lds_attr, lstm_seq_x3_kernel<SC, ST>, lds)) return rc; }
+    hipLaunchKernelGGL((lstm_seq_x3_kernel<SC, ST>), dim3(a.n_groups * LX_SLICES), dim3(512), lds, stream, a, w_scale, h_scale, 1.0f / (w_scale * h_scale));
     AT_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -311,7 +328,13 @@ int launch_lstm_seq_x3(const LstmSeqArgs& a_in, hipStream_t stream) {
     a.h_bytes = (long long)a.B * a.T * LX_H * 4;
     AT_REQUIRE(a.h_bytes < (1ll << 31), "lstm_seq_x3: h buffer exceeds the 2 GB buffer-descriptor range");
     AT_CHECK_HIP(hipMemsetAsync(a.sync + LX_FLAGS, 0, LX_MAX_GROUPS * LX_FLAG_STRIDE * sizeof(unsigned), stream));   // flags, every launch
-    const int rc = a.w_scale_f16 > 0.f ? launch_lx<SchemeF16x2>(a, a.w_scale_f16, LX_H_SCALE, stream) : launch_lx<SchemeBf16x3>(a, 1.0f, 1.0f, stream);
+    const bool st = a.h_init != nullptr;
+    AT_REQUIRE(st == (a.c_init != nullptr) && st == (a.c_final != nullptr), "lstm_seq_x3: h_init, c_init and c_final go together");
+    // the three-piece bf16 kernel sits at 255 of 256 registers: the state branch would spill, so carried state exists on the fp16 scheme only
+    // (lstm_skip in encodec.hip routes a streaming call with "lstm_f16x2" = 0 to the fp32 persistent kernel)
+    AT_REQUIRE(!st || a.w_scale_f16 > 0.f, "lstm_seq_x3: carried state needs the two-piece fp16 scheme");
+    const int rc = st ? launch_lx<SchemeF16x2, true>(a, a.w_scale_f16, LX_H_SCALE, stream)
+                      : (a.w_scale_f16 > 0.f ? launch_lx<SchemeF16x2, false>(a, a.w_scale_f16, LX_H_SCALE, stream) : launch_lx<SchemeBf16x3, false>(a, 1.0f, 1.0f, stream));
 #ifdef LX_DEBUG_STAMPS
     if (rc == 0) lx_print_stamps(a.T, stream);
 #endif

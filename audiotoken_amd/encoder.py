@@ -248,6 +248,12 @@ class AcousticEncoder(torch.nn.Module):
             return codes, emb
         return codes
 
+    def new_stream(self, batch: int = 1):
+        """A stateful encoder for audio that arrives in pieces (audiotoken_amd/streaming.py): ``push`` / ``flush`` give the tokens one-shot
+        ``forward`` gives for the concatenated audio, in memory bounded by the largest push. Streams of one encoder are independent."""
+        from .streaming import AcousticStream
+        return AcousticStream(self, batch)
+
     # ---- benchmark taps (HIP events recorded by the library on the launch stream) -----------------
     def enable_profile(self, on: bool) -> None:
         self._h.enable_profile(on)

@@ -1,0 +1,164 @@
+"""Streaming acoustic encode: audio pushed in pieces, the tokens of the whole (``at_encodec_encode_stream_checked``).
+
+``AcousticEncoder.new_stream(batch)`` returns an :class:`AcousticStream`. After any sequence of ``push`` calls and one ``flush`` the
+concatenated tokens are the tokens one-shot ``encode`` gives for the concatenated audio, in memory bounded by the largest push.
+The stream holds the device state of the library (two buffers, swapped when a push succeeded) and, on the host side, the samples that
+do not fill a frame yet.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Callable, Optional
+
+import torch
+
+from . import _cabi
+from . import weights as W
+from .logger import get_logger
+
+logger = get_logger(__name__)
+
+HOP = W.ENCODEC_HOP          # 320 samples per frame
+FIRST_PUSH_FRAMES = 7        # the library's minimum for the first push of a stream (include/audiotoken_hip.h)
+
+
+class AcousticStream:
+    """``push(samples [B, n]) -> int16 [B, n_q, t]`` on the device (``t`` may be 0), ``flush() -> int16 [B, n_q, t_last]``, ``reset()``.
+
+    All ``batch`` rows advance in lockstep. A push is a transaction: the library reads one state buffer and writes the other; when the
+    device status word of the push is non-zero the push is repeated from the untouched input state on the safe kernels, exactly as
+    ``AcousticEncoder.verified`` repeats a batch (bit 1: this push on the bf16x3 kernels, counted in ``fallback_batches``, the next push on
+    f16x2 again; bit 0: the LSTM route is switched for the rest of the handle's life). Reading the status word synchronises once per push.
+
+    ``push_fn(samples [B, n], final) -> codes [B, n_q, t]`` replaces the device call (the host-side buffering is tested with a stub).
+    """
+
+    def __init__(self, encoder=None, batch: int = 1, push_fn: Optional[Callable] = None, n_q: Optional[int] = None):
+        assert batch >= 1, "batch must be >= 1"
+        self._enc = encoder
+        self.batch = int(batch)
+        self.n_q = int(n_q if n_q is not None else encoder.n_q)
+        self._push_fn = push_fn if push_fn is not None else self._device_push
+        self._state = None
+        self.keep_embeddings = False   # parity tap: when set, every library push also leaves its pre-quantiser embedding [B, t, 128] in last_embeddings
+        self.last_embeddings: Optional[torch.Tensor] = None
+        if push_fn is None:
+            lib = encoder._h.lib
+            nbytes = lib.at_encodec_stream_state_bytes(encoder._h.handle, self.batch)
+            self._state = [torch.empty(nbytes, dtype=torch.uint8, device=encoder.device) for _ in range(2)]
+        self.reset()
+
+    # ---- host side: residual buffering ------------------------------------------------------------------------------------------
+    def reset(self) -> None:
+        """Forget everything: the next push starts a new stream (h = c = 0, true left reflect padding)."""
+        self._held: Optional[torch.Tensor] = None   # [B, < 320 (or < the first push's minimum)] samples not yet consumed
+        self._started = False
+        self._finished = False
+        self.frames_emitted = 0
+        if self._state is not None:
+            enc = self._enc
+            with torch.cuda.device(enc.device):
+                rc = enc._h.lib.at_encodec_stream_reset(enc._h.handle, self._state[0].data_ptr(), self.batch, _cabi.current_stream_handle(enc.device))
+            _cabi.check(rc, "at_encodec_stream_reset")
+
+    @property
+    def fallback_batches(self) -> int:
+        return self._enc.fallback_batches if self._enc is not None else 0
+
+    def _empty(self, like: torch.Tensor) -> torch.Tensor:
+        dev = self._enc.device if self._enc is not None else like.device
+        return torch.empty((self.batch, self.n_q, 0), dtype=torch.int16, device=dev)
+
+    def _check(self, samples: torch.Tensor) -> torch.Tensor:
+        if self._finished:
+            raise RuntimeError("AcousticStream: push after flush(); call reset() to start a new stream")
+        assert samples.dim() == 2 and samples.shape[0] == self.batch, f"samples must be [{self.batch}, n]"
+        if self._enc is not None:
+            samples = samples.to(device=self._enc.device, dtype=torch.float32)
+        return samples
+
+    def push(self, samples: torch.Tensor) -> torch.Tensor:
+        samples = self._check(samples)
+        held = samples if self._held is None else torch.cat([self._held, samples], dim=1)
+        n = held.shape[1] // HOP * HOP
+        if n == 0 or (not self._started and n < FIRST_PUSH_FRAMES * HOP):
+            self._held = held
+            self.last_embeddings = None
+            return self._empty(samples)
+        codes = self._push_fn(held[:, :n].contiguous(), False)
+        self._held = held[:, n:]
+        self._started = True
+        self.frames_emitted += codes.shape[-1]
+        return codes
+
+    def flush(self) -> torch.Tensor:
+        """The last frame(s): what is held goes out with the one-shot path's right-edge padding. The stream is finished afterwards."""
+        if self._finished:
+            raise RuntimeError("AcousticStream: flush() twice; call reset() to start a new stream")
+        held = self._held
+        self._held = None
+        self._finished = True
+        if held is None or held.shape[1] == 0:
+            self.last_embeddings = None
+            return self._empty(held if held is not None else torch.empty(0))
+        codes = self._push_fn(held.contiguous(), True)
+        self.frames_emitted += codes.shape[-1]
+        return codes
+
+    # ---- device side: one transaction -------------------------------------------------------------------------------------------
+    def _call(self, x: torch.Tensor, final: bool) -> torch.Tensor:
+        enc = self._enc
+        lib = enc._h.lib
+        B, n = x.shape
+        T = -(-n // HOP)
+        codes = torch.empty((B, self.n_q, T), dtype=torch.int16, device=enc.device)
+        emb = torch.empty((B, T, W.ENCODEC_DIM), dtype=torch.float32, device=enc.device) if self.keep_embeddings else None
+        self.last_embeddings = emb
+        nbytes = lib.at_encodec_stream_workspace_bytes(enc._h.handle, B, n)
+        ws = enc._workspace(nbytes)
+        t_out = C.c_int(0)
+        with torch.cuda.device(enc.device):
+            rc = lib.at_encodec_encode_stream_checked(enc._h.handle, self._state[0].data_ptr(), self._state[1].data_ptr(), x.data_ptr(), B, n,
+                                                      1 if final else 0, self.n_q, codes.data_ptr(), C.byref(t_out), _cabi.ptr(emb), ws.data_ptr(), nbytes,
+                                                      _cabi.current_stream_handle(enc.device), enc._status.data_ptr())
+        _cabi.check(rc, "at_encodec_encode_stream_checked")
+        assert t_out.value == T, (t_out.value, T)
+        return codes
+
+    def _device_push(self, x: torch.Tensor, final: bool) -> torch.Tensor:
+        enc = self._enc
+        codes = self._call(x, final)
+        status = enc.last_status()
+        if status & 4 and not status & 2:   # a NaN / infinity in the input: no kernel choice changes that (AcousticEncoder.verified)
+            enc.nonfinite_batches += 1
+            logger.error(f"acoustic stream: a NaN or an infinity reached the quantiser (status {status}); the token ids of this push are meaningless")
+            status &= ~4
+        if status != 0:
+            if status & 1:
+                if enc.get_option("lstm_pipe") == 1 and self.batch <= 80:
+                    logger.error(f"persistent LSTM hand-off timed out (status {status}): repeating this push with the layer-by-layer persistent LSTM (option lstm_pipe=0) from now on")
+                    enc.set_option("lstm_pipe", 0)
+                else:
+                    logger.error(f"persistent LSTM hand-off timed out (status {status}): repeating this push with per-step LSTM launches (option persistent_lstm=0) from now on")
+                    enc.set_option("persistent_lstm", 0)
+            saved = {}
+            if status & 2:
+                enc.fallback_batches += 1
+                logger.error(f"an activation exceeded the fp16 range of the f16x2 kernels (status {status}): repeating THIS push from the unchanged "
+                             f"state with the bf16x3 kernels (fallback batch #{enc.fallback_batches})")
+                for opt in enc.RANGE_OPTIONS:
+                    saved[opt] = enc.get_option(opt)
+                    enc.set_option(opt, 0)
+            try:
+                codes = self._call(x, final)     # same input state: the failed call wrote the other buffer only
+                if enc.last_status() & 1 and enc.get_option("persistent_lstm") == 1:
+                    logger.error("persistent LSTM hand-off timed out again: repeating with per-step LSTM launches (option persistent_lstm=0) from now on")
+                    enc.set_option("persistent_lstm", 0)
+                    codes = self._call(x, final)
+                if enc.last_status() & ~4 != 0:
+                    raise _cabi.HipLibraryError("acoustic stream push failed twice (status non-zero on the fallback kernels)")
+            finally:
+                for opt, v in saved.items():
+                    enc.set_option(opt, v)
+        self._state.reverse()   # success: the written buffer is the next push's input
+        return codes

@@ -79,6 +79,40 @@ int at_encodec_encode_checked(at_encodec_t* h, const float* wav, const float* ma
                               int* T_out, float* emb_out, void* workspace, size_t workspace_bytes, at_stream_t stream,
                               uint32_t* status_dev);
 
+/* ---- streaming acoustic encode: the same tokens as one at_encodec_encode of the concatenated audio, in bounded memory ----------------------
+ * Every conv of the encoder is causal and the only unbounded memory is the LSTM, so a stream carries a small fixed-size state per clip:
+ * the last 640 consumed samples (two frames: a frame depends on samples back to 320 t - 478), h and c of both LSTM layers, the last 6 input
+ * rows of the final k = 7 conv. A push encodes [640 context samples | n_new new samples] with the one-shot kernels, drops the two context
+ * frames, runs the LSTM over the new frames from the carried (h, c) and the final conv over [6 carried rows | new rows]. The first push of a
+ * stream has no context: its left reflect padding is the true one.
+ *   state   device memory, at_encodec_stream_state_bytes(h, B) bytes, 16-byte aligned; B streams advance in lockstep (same n_new). The
+ *           handle keeps a host-side note per state ADDRESS (B, started, finished) — made by at_encodec_stream_reset and by every push for
+ *           its state_out — so argument errors are found without synchronising the device. A state therefore cannot be moved or copied
+ *           behind the library's back, and it belongs to the handle that reset it.
+ *   TRANSACTION RULE: a push reads state_in and writes state_out, which must be two buffers. If the status word of a push is non-zero its
+ *           codes AND state_out are invalid; state_in is untouched, so the caller changes the options (as for at_encodec_encode_checked) and
+ *           repeats the same push from the same state_in. On success the caller swaps the two buffers.
+ *   n_new   a positive multiple of 320 unless `final`; the first push of a stream needs >= 2240 samples (7 frames) unless `final`. The caller
+ *           buffers what does not fill a frame yet (AcousticStream in audiotoken_amd/streaming.py does).
+ *   final   != 0: the last samples of the stream, any n_new >= 0; the one-shot path's right-edge padding applies inside the window and
+ *           T = ceil(n_new / 320). The stream is finished: a further push from state_out is an error until at_encodec_stream_reset.
+ *   codes   device int16 [B][n_q][T], T returned through *T_out (n_new / 320, or ceil for the final push); emb_out optional [B][T][128].
+ * BIT-IDENTITY: where the one-shot call and the pushes select the same kernels (an even total length with the stage-1 / stage-2 / stage-3
+ * lengths divisible by 4 / 5 / 8, i.e. any multiple of 320, pushed in multiples of 320) codes and embeddings are bit-identical to
+ * at_encodec_encode's under the same options (profiles/stream_encode.txt; with "lstm_f16x2" = 0 a push runs the fp32 persistent recurrence).
+ * Otherwise (an odd or ragged total: the one-shot call then selects other kernels than the frame-aligned windows do) the tokens agree and the
+ * embeddings differ in the last bits, as between the kernel options of at_encodec_set_option.
+ * Argument errors (null state, state_in == state_out, a state this handle does not know, another B, n_new not a multiple of 320 without
+ * final, a first push below 2240 samples without final, a workspace below at_encodec_stream_workspace_bytes, a push after final) return
+ * non-zero with at_last_error set; nothing is launched and the device stays usable. */
+size_t at_encodec_stream_state_bytes(const at_encodec_t* h, int B);
+int at_encodec_stream_reset(at_encodec_t* h, void* state_dev, int B, at_stream_t stream);
+/* Workspace of one push of n_new samples: that of a one-shot encode of the window (B, 640 + n_new), whatever was pushed before. */
+size_t at_encodec_stream_workspace_bytes(const at_encodec_t* h, int B, int n_new);
+int at_encodec_encode_stream_checked(at_encodec_t* h, const void* state_in, void* state_out, const float* wav_new, int B, int n_new, int final,
+                                     int n_q, int16_t* codes, int* T_out, float* emb_out, void* workspace, size_t workspace_bytes,
+                                     at_stream_t stream, uint32_t* status_dev);
+
 /* Options (they select kernels or bound memory; all but the "*_x3" / "*_f16x2" ones leave the results bit-identical). The product runs the
  * defaults; the others exist as the per-batch range fallback of AcousticEncoder.verified ("*_f16x2" = 0: three bf16 pieces, fp32 exponent range), as
  * the machine fallback ("persistent_lstm" = 0) and as the A/B twins the parity tests compare against (fp32 kernels, unfused GEMM paths). Environment
