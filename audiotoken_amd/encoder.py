@@ -13,21 +13,13 @@ from typing import Dict, Optional, Union
 import numpy as np
 import torch
 
-from . import _cabi
+from . import _cabi, fallback
 from . import weights as W
+from ._handle import LibHandle, SemanticHandle
 from .configs import AcousticEncoderConfig
 from .logger import get_logger
 
 logger = get_logger(__name__)
-
-
-def _device_index(device: Union[str, torch.device]) -> int:
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(
-            f"audiotoken_amd runs on MI355X only (device 'cuda[:i]' under PyTorch-ROCm); got {device!r}. "
-            "There is no CPU path in this package.")
-    return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
 def encodec_bandwidth_to_nq(bandwidth: float) -> int:
@@ -71,46 +63,35 @@ def encodec_weights_from(weights, with_decoder: bool) -> Dict[str, np.ndarray]:
     return weights
 
 
-class _EncodecHandle:
+class _EncodecHandle(LibHandle):
     """Owns one ``at_encodec_t`` (device weights live inside the library)."""
+    FAMILY = "encodec"
 
     def __init__(self, device: Union[str, torch.device], weights: Optional[Union[str, Dict[str, np.ndarray]]],
                  with_decoder: bool):
-        self.lib = _cabi.load()
-        self.device_index = _device_index(device)
-        self.device = torch.device("cuda", self.device_index)
-        folded = fold_encodec_weights(encodec_weights_from(weights, with_decoder))
-        self.handle = self.lib.at_encodec_create(self.device_index)
-        if not self.handle:
-            raise _cabi.HipLibraryError(f"at_encodec_create failed: {_cabi.last_error()}")
-        for name, arr in folded.items():
-            if not with_decoder and name.startswith("decoder."):
-                continue
-            _cabi.set_tensor(self.lib, self.lib.at_encodec_set_tensor, self.handle, name, arr)
-        _cabi.check(self.lib.at_encodec_finalize(self.handle, 1 if with_decoder else 0), "at_encodec_finalize")
-        self.n_codebooks = self.lib.at_encodec_num_codebooks(self.handle)
+        def host_tensors():
+            folded = fold_encodec_weights(encodec_weights_from(weights, with_decoder))
+            return {k: v for k, v in folded.items() if with_decoder or not k.startswith("decoder.")}
+        self._create(device, None, host_tensors, 1 if with_decoder else 0)
 
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            self.lib.at_encodec_destroy(h)
-
-    # benchmark taps: HIP events recorded by the library on the launch stream, {group: (total ms, launches)}
-    def enable_profile(self, on: bool) -> None:
-        _cabi.check(self.lib.at_encodec_profile(self.handle, 1 if on else 0), "at_encodec_profile")
-
-    def read_profile(self) -> Dict[str, tuple]:
-        names = C.create_string_buffer(4096)
-        ms = (C.c_float * 64)()
-        ln = (C.c_int * 64)()
-        n = self.lib.at_encodec_profile_read(self.handle, names, 4096, ms, ln, 64)
-        if n < 0:
-            raise _cabi.HipLibraryError(f"at_encodec_profile_read failed: {_cabi.last_error()}")
-        keys = names.value.decode().split("\n")[:n]
-        return {k: (float(ms[i]), int(ln[i])) for i, k in enumerate(keys)}
+    def _finish_init(self) -> None:
+        self.n_codebooks = self._fn("num_codebooks")(self.handle)
 
 
-class AcousticEncoder(torch.nn.Module):
+class _EncodecCallable(LibHandle, torch.nn.Module):
+    """An encoder or a decoder over an ``_EncodecHandle`` of its own (``_h``)."""
+    FAMILY = "encodec"
+    lib = property(lambda self: self._h.lib)
+    handle = property(lambda self: self._h.handle)
+
+    def _open(self, device, weights, with_decoder: bool) -> None:
+        self._h = _EncodecHandle(device, weights, with_decoder)
+        self.device = self._h.device
+        self._init_call_state()
+        self.fallback_batches = 0    # batches `verified` repeated without the f16x2 kernels (fp16 range overflow)
+
+
+class AcousticEncoder(_EncodecCallable):
     """Drop-in for reference ``AcousticEncoder`` (audiotoken/encoder.py:29-57)."""
 
     def __init__(self, config: AcousticEncoderConfig = None, device: str = "cuda:0",
@@ -118,27 +99,11 @@ class AcousticEncoder(torch.nn.Module):
         super().__init__()
         config = config or AcousticEncoderConfig()
         self.config = config
-        self._h = _EncodecHandle(device, weights if weights is not None else config.weights, with_decoder=False)
-        self.device = self._h.device
+        self._open(device, weights if weights is not None else config.weights, with_decoder=False)
         self.n_q = encodec_bandwidth_to_nq(config.bandwidth)
         if self.n_q > self._h.n_codebooks:
             raise ValueError(f"bandwidth {config.bandwidth} needs {self.n_q} codebooks, checkpoint has {self._h.n_codebooks}")
-        self._ws: Optional[torch.Tensor] = None
-        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.fallback_batches = 0    # batches `verified` repeated on the bf16x3 kernels (fp16 range overflow)
         self.nonfinite_batches = 0   # batches whose activations held a NaN / infinity at the quantiser (status bit 2)
-
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    def set_option(self, name: str, value: int) -> None:
-        _cabi.check(self._h.lib.at_encodec_set_option(self._h.handle, name.encode(), int(value)), f"at_encodec_set_option({name})")
-
-    def get_option(self, name: str) -> int:
-        return int(self._h.lib.at_encodec_get_option(self._h.handle, name.encode()))
 
     def _sized_workspace(self, B: int, N: int):
         """Workspace for a [B, N] encode. The conv stack runs in sub-batches of `subbatch` clips (default 256, which needs
@@ -159,70 +124,20 @@ class AcousticEncoder(torch.nn.Module):
                 self._subbatch = sub
                 torch.cuda.empty_cache()
 
-    def last_status(self) -> int:
-        """0 = ok; bit 0 = a bounded wait inside the persistent LSTM kernel gave up; bit 1 = fp16 range overflow in an f16x2 kernel (stage 2-3
-        convs, LSTM input projection) (synchronises the device)."""
-        return int(self._status.item())
-
-    def range_report(self) -> Dict[str, float]:
-        """{site: largest |x * scale| its split writers saw in the LAST call}: the measured headroom of the two-piece fp16 arithmetic, which
-        overflows at 65504 (0.0: the site did not run on that scheme). Synchronises the device."""
-        return _cabi.range_report(self._h.lib, "encodec", self._h.handle)
-
+    # the f16x2 kernel groups with a range check (SEANet convs, LSTM input projection, final conv, RVQ search): off for the repeat of an overflowing batch
     RANGE_OPTIONS = ("ih_f16x2", "chain_f16x2", "res_f16x2", "rvq_f16x2", "fin_f16x2")
 
     def verified(self, codes: torch.Tensor, input_batch: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Product-path guard, called where the caller synchronises anyway (tokens leaving the device). The status word of the call that
-        produced `codes` decides:
+        produced `codes` decides (fallback.encodec_ladder):
         * bit 0, the persistent LSTM's hand-off timed out (another process on the GPU, a partitioned device: not all 256 workgroups
           resident): a property of the MACHINE — log it, switch to the per-step LSTM launches for the rest of the handle's life and repeat;
         * bit 1, an activation exceeded the fp16 range of the f16x2 kernels: a property of THIS BATCH — repeat it on the bf16x3 kernels (fp32
           exponent range), count it in ``fallback_batches`` and switch back: the next batch runs on f16x2 again (round 2 switched the
-          handle for good, so one outlier batch halved the throughput of the rest of a run)."""
-        status = self.last_status()
-        if status == 0:
-            return codes
-        if status & 4 and not status & 2:   # (with bit 1 set the infinity descends from the flagged fp16 overflow: the repeat below cures it)
-            # a NaN / infinity reached the quantiser (a non-finite sample in the waveform, as a rule): no kernel choice changes that. The reference emits
-            # arbitrary ids for such input without a diagnostic; here it is at least logged and counted. The ids are returned as they are.
-            self.nonfinite_batches += 1
-            logger.error(f"acoustic encode: a NaN or an infinity reached the quantiser (status {status}); check the input waveform. "
-                         f"The token ids of this batch are meaningless (non-finite batch #{self.nonfinite_batches})")
-            if status & ~4 == 0:
-                return codes
-        if status & 1:
-            if self.get_option("lstm_pipe") == 1 and input_batch.shape[0] <= 80:
-                # the pipelined two-layer launch (lstm_pipe.hip) needs 48 co-resident workgroups per 16 clips, the layer-by-layer one 16: try that first
-                logger.error(f"persistent LSTM hand-off timed out (status {status}): the tokens of this batch were discarded; "
-                             "re-encoding with the layer-by-layer persistent LSTM (option lstm_pipe=0) from now on")
-                self.set_option("lstm_pipe", 0)
-            else:
-                logger.error(f"persistent LSTM hand-off timed out (status {status}): the tokens of this batch were discarded; "
-                             "re-encoding with per-step LSTM launches (option persistent_lstm=0) from now on")
-                self.set_option("persistent_lstm", 0)
-        saved = {}
-        if status & 2:
-            self.fallback_batches += 1
-            logger.error(f"an activation exceeded the fp16 range of the f16x2 kernels (SEANet convs, LSTM input projection, final conv, RVQ search; status {status}): "
-                         f"the tokens of this batch were discarded; re-encoding THIS batch with the bf16x3 kernels (fallback batch #{self.fallback_batches})")
-            for opt in self.RANGE_OPTIONS:
-                saved[opt] = self.get_option(opt)
-                self.set_option(opt, 0)
-        try:
-            codes = self.forward(input_batch, attention_mask)
-            if self.last_status() & 1 and self.get_option("persistent_lstm") == 1:   # the layer-by-layer persistent launch timed out as well
-                logger.error("persistent LSTM hand-off timed out again: re-encoding with per-step LSTM launches (option persistent_lstm=0) from now on")
-                self.set_option("persistent_lstm", 0)
-                codes = self.forward(input_batch, attention_mask)
-            if self.last_status() & 4:          # still non-finite on the safe kernels: it came with the input, not from the fp16 range
-                self.nonfinite_batches += 1
-                logger.error(f"a NaN or an infinity reached the quantiser on the fallback kernels too (non-finite batch #{self.nonfinite_batches}): check the input waveform")
-            if self.last_status() & ~4 != 0:   # (bit 2, non-finite input, is not something a repeat can clear)
-                raise _cabi.HipLibraryError("acoustic encode failed twice (status non-zero on the fallback kernels)")
-        finally:
-            for opt, v in saved.items():
-                self.set_option(opt, v)
-        return codes
+          handle for good, so one outlier batch halved the throughput of the rest of a run);
+        * bit 2, a NaN / infinity reached the quantiser: counted in ``nonfinite_batches`` and logged, the ids are returned as they are."""
+        return fallback.encodec_ladder(self, codes, lambda: self.forward(input_batch, attention_mask), input_batch.shape[0],
+                                       self.RANGE_OPTIONS, "acoustic encode")
 
     @torch.no_grad()
     def forward(self, input_batch: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
@@ -253,13 +168,6 @@ class AcousticEncoder(torch.nn.Module):
         ``forward`` gives for the concatenated audio, in memory bounded by the largest push. Streams of one encoder are independent."""
         from .streaming import AcousticStream
         return AcousticStream(self, batch)
-
-    # ---- benchmark taps (HIP events recorded by the library on the launch stream) -----------------
-    def enable_profile(self, on: bool) -> None:
-        self._h.enable_profile(on)
-
-    def read_profile(self) -> Dict[str, tuple]:
-        return self._h.read_profile()
 
 
 # ======================================================================================================
@@ -301,8 +209,9 @@ def load_w2vbert_checkpoint(model_dir: str, quantizer_path: Optional[str]) -> Di
     return w
 
 
-class Wav2VecBertEncoder(torch.nn.Module):
+class Wav2VecBertEncoder(SemanticHandle, torch.nn.Module):
     """Drop-in for reference ``Wav2VecBertEncoder`` with ``quantize=True`` (audiotoken/encoder.py:111-186)."""
+    FAMILY, LAYER_NOUN = "w2vbert", "conformer"
 
     def __init__(self, config=None, device: str = "cuda:0", quantize: bool = True,
                  weights: Optional[Union[str, Dict[str, np.ndarray]]] = None, packed=None):
@@ -314,26 +223,14 @@ class Wav2VecBertEncoder(torch.nn.Module):
         self.config = config
         self.quantize = quantize
         self.output_layer = config.output_layer
-        self.lib = _cabi.load()
-        self.device_index = _device_index(device)
-        self.device = torch.device("cuda", self.device_index)
-        if packed is not None:
-            self.handle = self.lib.at_w2vbert_create(self.device_index)
-            if not self.handle:
-                raise _cabi.HipLibraryError(f"at_w2vbert_create failed: {_cabi.last_error()}")
-            _cabi.import_packed(self.lib, "w2vbert", self.handle, packed[0], packed[1].to(self.device))
-            self._finish_init()
-            return
-        if weights is None:
-            weights = config.weights
+        self._create(device, packed, lambda: self._host_tensors(weights if weights is not None else config.weights))
+
+    def _host_tensors(self, weights) -> Dict[str, np.ndarray]:
         if weights is None:
             logger.warning("No Wav2Vec2-BERT checkpoint given (weights=/AUDIOTOKEN_W2VBERT_WEIGHTS): synthetic weights, seed 0")
             weights = W.synth_w2vbert_weights(n_layers=self.output_layer, seed=0, with_vq=True)
         elif isinstance(weights, (str, bytes)):
-            weights = load_w2vbert_checkpoint(weights, config.quantizer_path)
-        self.handle = self.lib.at_w2vbert_create(self.device_index)
-        if not self.handle:
-            raise _cabi.HipLibraryError(f"at_w2vbert_create failed: {_cabi.last_error()}")
+            weights = load_w2vbert_checkpoint(weights, self.config.quantizer_path)
         tensors = dict(frontend_tables())
         for k, v in weights.items():
             if k.startswith("encoder.layers."):
@@ -345,115 +242,14 @@ class Wav2VecBertEncoder(torch.nn.Module):
         if "vq._codebook.embed" in tensors:
             e = torch.from_numpy(np.ascontiguousarray(tensors["vq._codebook.embed"], dtype=np.float32)).reshape(-1, 1024)
             tensors["vq._codebook.e2"] = (e ** 2).sum(-1).numpy()   # y2 of vector_quantize_pytorch's cdist
-        for name, arr in tensors.items():
-            _cabi.set_tensor(self.lib, self.lib.at_w2vbert_set_tensor, self.handle, name, arr)
-        _cabi.check(self.lib.at_w2vbert_finalize(self.handle), "at_w2vbert_finalize")
-        self._finish_init()
-
-    def export_packed(self):
-        """(meta bytes, uint8 device blob): this finalized model for ``Wav2VecBertEncoder(packed=...)`` on the other ranks of a node."""
-        return _cabi.export_packed(self.lib, "w2vbert", self.handle, self.device)
-
-    def _finish_init(self) -> None:
-        self.n_layers = self.lib.at_w2vbert_num_layers(self.handle)
-        if self.n_layers < self.output_layer:
-            raise ValueError(f"checkpoint has {self.n_layers} conformer layers, output_layer={self.output_layer} needs that many")
-        self._ws: Optional[torch.Tensor] = None
-        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.fallback_batches = 0    # batches `verified` repeated (fp16 range overflow)
-        self.pinned_layers = []      # conformer layers `verified` moved to bf16x3 for good (their activations do not fit the fp16 range)
-        self.layer_overflows = {}    # {layer: batches on which it overflowed}: a layer is pinned from the PIN_AFTER-th such batch on
-        self.nonfinite_batches = 0
-
-    def __del__(self):
-        h = self.__dict__.pop("handle", None)
-        if h:
-            self.lib.at_w2vbert_destroy(h)
-
-    ARITH = {"f32": 0, "bf16x3": 1, "f16x2": 2}
-    # Range fallback policy: a layer's FIRST overflowing batch is repeated with that layer on bf16x3 and the layer goes back to f16x2 (the outlier may have
-    # come with the input: one loud or clipped file must not slow down — or change the rounding of — the rest of a run); from its PIN_AFTER-th overflowing batch
-    # on the layer stays on bf16x3 (an activation outlier that is a property of the checkpoint would repeat every batch otherwise). AudioToken unpins at the
-    # end of encode_batch_files and records what happened in `run_summary`.
-    PIN_AFTER = 2
-
-    def set_option(self, name: str, value) -> None:
-        """"arith": "f32" | "bf16x3" | "f16x2" (or 0/1/2) — arithmetic of the linear layers (include/audiotoken_hip.h)."""
-        if isinstance(value, str):
-            value = self.ARITH[value]
-        _cabi.check(self.lib.at_w2vbert_set_option(self.handle, name.encode(), int(value)), f"at_w2vbert_set_option({name})")
-
-    def get_option(self, name: str) -> int:
-        return int(self.lib.at_w2vbert_get_option(self.handle, name.encode()))
-
-    def last_status(self) -> int:
-        """0 = ok; bit 1 (2) = an activation overflowed the fp16 range of the f16x2 arithmetic (synchronises the device)."""
-        return int(self._status.item())
-
-    def range_report(self) -> Dict[str, float]:
-        """{site: largest |x * scale| its split writers saw in the LAST call, over all layers}; the f16x2 arithmetic overflows at 65504."""
-        return _cabi.range_report(self.lib, "w2vbert", self.handle)
+        return tensors
 
     def verified(self, tokens: torch.Tensor, input_batch: torch.Tensor, mask: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
         """Product-path guard, called where the caller synchronises anyway: if the call that produced `tokens` reported an fp16 range
         overflow, log it, find the conformer layer that caused it, move THAT layer to the bf16x3 arithmetic (full fp32 exponent range) and repeat this
         batch (``fallback_batches``); every other layer stays on f16x2. The layer returns to f16x2 after the batch unless it is its PIN_AFTER-th overflowing
-        batch (then it stays: ``pinned_layers``)."""
-        status = self.last_status()
-        if status == 0:
-            return tokens
-        if status & 4 and not status & 2:   # (with bit 1 set the infinity descends from the flagged fp16 overflow: the repeat below cures it)
-            # a NaN / infinity reached the quantiser (a non-finite sample in the waveform, as a rule): no kernel choice changes that. The reference emits
-            # arbitrary ids for such input without a diagnostic; here it is at least logged and counted. The ids are returned as they are.
-            self.nonfinite_batches += 1
-            logger.error(f"semantic_m encode: a NaN or an infinity reached the quantiser (status {status}); check the input waveform. "
-                         f"The token ids of this batch are meaningless (non-finite batch #{self.nonfinite_batches})")
-            if status & ~4 == 0:
-                return tokens
-        self.fallback_batches += 1
-        # Which layer? Every layer has its own row of range flags; an overflow turns into infinities that all later layers flag too, so the FIRST flagged
-        # layer is the cause. That layer alone is moved to bf16x3 (full fp32 exponent range); it stays there once it has overflowed on PIN_AFTER batches
-        # (an activation outlier of the checkpoint: the next batch would overflow at the same place). The other layers keep f16x2, so a model with one such
-        # layer pays ~1 / n_layers of the bf16x3 price instead of a repeat of every batch. Up to three layers are found this way per batch; beyond that the
-        # whole batch is repeated on bf16x3 as in round 3.
-        transient = []    # layers moved for THIS batch only (their first overflow): restored below
-        try:
-            for _ in range(3):
-                bad = [l for l, f in enumerate(self.layer_status()) if f & 2]
-                if not bad:
-                    break
-                layer = bad[0]
-                self.layer_overflows[layer] = self.layer_overflows.get(layer, 0) + 1
-                pin = self.layer_overflows[layer] >= self.PIN_AFTER
-                (self.pinned_layers if pin else transient).append(layer)
-                logger.error(f"semantic_m encode reported status {status}: an activation of conformer layer {layer} exceeded the fp16 range of the f16x2 "
-                             f"arithmetic (batch #{self.layer_overflows[layer]} on which it did). The tokens of this batch were discarded; layer {layer} runs on "
-                             f"bf16x3 (option layer_arith:{layer} = 1) " + ("from now on" if pin else "for this batch") +
-                             f", this batch is re-encoded (fallback batch #{self.fallback_batches})")
-                self.set_option(f"layer_arith:{layer}", 1)
-                tokens = self.forward(input_batch, mask, **kw)
-                status = self.last_status()
-                if not status & 2:
-                    if status & 4:
-                        self.nonfinite_batches += 1
-                        logger.error(f"a NaN or an infinity reached the quantiser with layer {layer} on bf16x3 too (non-finite batch #{self.nonfinite_batches}): check the input waveform")
-                    return tokens
-        finally:
-            for layer in transient:
-                self.set_option(f"layer_arith:{layer}", -1)
-        logger.error(f"semantic_m encode still reports status {status}: re-encoding THIS batch with arith=bf16x3 for every layer")
-        saved = self.get_option("arith")
-        self.set_option("arith", "bf16x3")
-        try:
-            tokens = self.forward(input_batch, mask, **kw)
-            if self.last_status() & 4:          # still non-finite on the safe kernels: it came with the input, not from the fp16 range
-                self.nonfinite_batches += 1
-                logger.error(f"a NaN or an infinity reached the quantiser on the fallback kernels too (non-finite batch #{self.nonfinite_batches}): check the input waveform")
-            if self.last_status() & ~4 != 0:   # (bit 2, non-finite input, is not something a repeat can clear)
-                raise _cabi.HipLibraryError("semantic_m encode failed twice (status non-zero with bf16x3 arithmetic)")
-        finally:
-            self.set_option("arith", saved)
-        return tokens
+        batch (then it stays: ``pinned_layers``). The policy is fallback.semantic_ladder."""
+        return fallback.semantic_ladder(self, tokens, lambda: self.forward(input_batch, mask, **kw), 0, self.LAYER_NOUN, "semantic_m encode")
 
     def site_scales(self) -> Dict[str, list]:
         """{site: [scale per conformer layer]} — the power of two each split site multiplies its activations by (16, or the provable scale of a
@@ -466,27 +262,6 @@ class Wav2VecBertEncoder(torch.nn.Module):
             raise _cabi.HipLibraryError(f"at_w2vbert_site_scales failed: {_cabi.last_error()}")
         keys = names.value.decode().split("\n")[:ns]
         return {k: [float(buf[l * ns + i]) for l in range(n // ns)] for i, k in enumerate(keys)}
-
-    def layer_status(self):
-        """Per conformer layer, the OR of its split sites' status flags in the LAST call (bit 1 = fp16 range overflow in that layer). Synchronises."""
-        buf = (C.c_int32 * 64)()
-        n = self.lib.at_w2vbert_layer_status(self.handle, buf, 64)
-        if n < 0:
-            raise _cabi.HipLibraryError(f"at_w2vbert_layer_status failed: {_cabi.last_error()}")
-        return [int(buf[i]) for i in range(n)]
-
-    def unpin_layers(self) -> None:
-        """Return every layer the range fallback moved to bf16x3 to the handle's arithmetic."""
-        for layer in set(self.pinned_layers):
-            self.set_option(f"layer_arith:{layer}", -1)
-        self.pinned_layers = []
-        self.layer_overflows = {}
-
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     @torch.no_grad()
     def forward(self, input_batch: torch.Tensor, mask: Optional[torch.Tensor] = None, pad_to_multiple_of: int = 2,
@@ -520,16 +295,3 @@ class Wav2VecBertEncoder(torch.nn.Module):
         if return_taps:
             return tokens, {"input_features": feats, "attention_mask": amask, "hidden": hidden}
         return tokens if want_tokens else hidden
-
-    def enable_profile(self, on: bool) -> None:
-        _cabi.check(self.lib.at_w2vbert_profile(self.handle, 1 if on else 0), "at_w2vbert_profile")
-
-    def read_profile(self) -> Dict[str, tuple]:
-        names = C.create_string_buffer(4096)
-        ms = (C.c_float * 64)()
-        ln = (C.c_int * 64)()
-        n = self.lib.at_w2vbert_profile_read(self.handle, names, 4096, ms, ln, 64)
-        if n < 0:
-            raise _cabi.HipLibraryError(f"at_w2vbert_profile_read failed: {_cabi.last_error()}")
-        keys = names.value.decode().split("\n")[:n]
-        return {k: (float(ms[i]), int(ln[i])) for i, k in enumerate(keys)}

@@ -12,11 +12,8 @@ from typing import Callable, Optional
 
 import torch
 
-from . import _cabi
+from . import _cabi, fallback
 from . import weights as W
-from .logger import get_logger
-
-logger = get_logger(__name__)
 
 HOP = W.ENCODEC_HOP          # 320 samples per frame
 FIRST_PUSH_FRAMES = 7        # the library's minimum for the first push of a stream (include/audiotoken_hip.h)
@@ -26,8 +23,8 @@ class AcousticStream:
     """``push(samples [B, n]) -> int16 [B, n_q, t]`` on the device (``t`` may be 0), ``flush() -> int16 [B, n_q, t_last]``, ``reset()``.
 
     All ``batch`` rows advance in lockstep. A push is a transaction: the library reads one state buffer and writes the other; when the
-    device status word of the push is non-zero the push is repeated from the untouched input state on the safe kernels, exactly as
-    ``AcousticEncoder.verified`` repeats a batch (bit 1: this push on the bf16x3 kernels, counted in ``fallback_batches``, the next push on
+    device status word of the push is non-zero the push is repeated from the untouched input state on the safe kernels, by the ladder
+    ``AcousticEncoder.verified`` repeats a batch with (audiotoken_amd/fallback.py; bit 1: this push on the bf16x3 kernels, counted in ``fallback_batches``, the next push on
     f16x2 again; bit 0: the LSTM route is switched for the rest of the handle's life). Reading the status word synchronises once per push.
 
     ``push_fn(samples [B, n], final) -> codes [B, n_q, t]`` replaces the device call (the host-side buffering is tested with a stub).
@@ -127,38 +124,7 @@ class AcousticStream:
 
     def _device_push(self, x: torch.Tensor, final: bool) -> torch.Tensor:
         enc = self._enc
-        codes = self._call(x, final)
-        status = enc.last_status()
-        if status & 4 and not status & 2:   # a NaN / infinity in the input: no kernel choice changes that (AcousticEncoder.verified)
-            enc.nonfinite_batches += 1
-            logger.error(f"acoustic stream: a NaN or an infinity reached the quantiser (status {status}); the token ids of this push are meaningless")
-            status &= ~4
-        if status != 0:
-            if status & 1:
-                if enc.get_option("lstm_pipe") == 1 and self.batch <= 80:
-                    logger.error(f"persistent LSTM hand-off timed out (status {status}): repeating this push with the layer-by-layer persistent LSTM (option lstm_pipe=0) from now on")
-                    enc.set_option("lstm_pipe", 0)
-                else:
-                    logger.error(f"persistent LSTM hand-off timed out (status {status}): repeating this push with per-step LSTM launches (option persistent_lstm=0) from now on")
-                    enc.set_option("persistent_lstm", 0)
-            saved = {}
-            if status & 2:
-                enc.fallback_batches += 1
-                logger.error(f"an activation exceeded the fp16 range of the f16x2 kernels (status {status}): repeating THIS push from the unchanged "
-                             f"state with the bf16x3 kernels (fallback batch #{enc.fallback_batches})")
-                for opt in enc.RANGE_OPTIONS:
-                    saved[opt] = enc.get_option(opt)
-                    enc.set_option(opt, 0)
-            try:
-                codes = self._call(x, final)     # same input state: the failed call wrote the other buffer only
-                if enc.last_status() & 1 and enc.get_option("persistent_lstm") == 1:
-                    logger.error("persistent LSTM hand-off timed out again: repeating with per-step LSTM launches (option persistent_lstm=0) from now on")
-                    enc.set_option("persistent_lstm", 0)
-                    codes = self._call(x, final)
-                if enc.last_status() & ~4 != 0:
-                    raise _cabi.HipLibraryError("acoustic stream push failed twice (status non-zero on the fallback kernels)")
-            finally:
-                for opt, v in saved.items():
-                    enc.set_option(opt, v)
+        # every repeat starts from the same input state: a failed call wrote the other buffer only
+        codes = fallback.encodec_ladder(enc, self._call(x, final), lambda: self._call(x, final), self.batch, enc.RANGE_OPTIONS, "acoustic stream push")
         self._state.reverse()   # success: the written buffer is the next push's input
         return codes
