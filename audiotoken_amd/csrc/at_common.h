@@ -146,8 +146,11 @@ struct Profiler {
     void begin(const char* group, int launches, hipStream_t s);
     void end(hipStream_t s);
     void reset();
+    void restart(bool enable) { reset(); enabled = enable; }   // at_*_profile
     // sums elapsed ms per group; synchronises on the recorded events
     int read(std::vector<float>& ms, std::vector<int>& launches);
+    // at_*_profile_read: the groups' names (newline-terminated each), total ms and launch counts into the caller's buffers; returns the number of groups
+    int read_groups(char* names, size_t names_cap, float* total_ms, int* launches, int max_groups);
     ~Profiler();
 };
 

@@ -18,7 +18,7 @@
 #include "../../include/audiotoken_hip.h"
 #include "at_common.h"
 #include "encodec_kernels.h"
-#include "gemm_bf16x3.h"
+#include "semantic_handle.h"   // HostTensor, stage_tensor, device_exists
 
 namespace at {
 
@@ -65,15 +65,26 @@ int Profiler::read(std::vector<float>& ms, std::vector<int>& launches) {
     }
     return 0;
 }
+int Profiler::read_groups(char* names_out, size_t names_cap, float* total_ms, int* launches, int max_groups) {
+    std::vector<float> ms;
+    std::vector<int> ln;
+    if (read(ms, ln) != 0) { set_error("profile read: event query failed"); return -2; }
+    std::string joined;
+    int n = 0;
+    for (size_t i = 0; i < names.size() && n < max_groups; ++i, ++n) {
+        joined += names[i];
+        joined += '\n';
+        total_ms[n] = ms[i];
+        launches[n] = ln[i];
+    }
+    AT_REQUIRE(joined.size() + 1 <= names_cap, "names buffer too small");
+    std::memcpy(names_out, joined.c_str(), joined.size() + 1);
+    return n;
+}
 Profiler::~Profiler() {
     reset();
     for (auto e : pool) (void)hipEventDestroy(e);
 }
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
 
 struct ConvW {
     const float* w = nullptr;
@@ -622,25 +633,13 @@ int at_version(void) { return 1; }
 const char* at_last_error(void) { return at::last_error_cstr(); }
 
 at_encodec_t* at_encodec_create(int device_id) {
-    int n = 0;
-    if (!host_only_test() && (hipGetDeviceCount(&n) != hipSuccess || device_id < 0 || device_id >= n)) {
-        set_error("at_encodec_create: no such HIP device " + std::to_string(device_id));
-        return nullptr;
-    }
+    if (!device_exists("at_encodec_create", device_id)) return nullptr;
     at_encodec* h = new at_encodec();
     h->device = device_id;
     return h;
 }
-
 int at_encodec_set_tensor(at_encodec_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-    AT_REQUIRE(h && name && host_data && shape && ndim >= 1 && ndim <= 4, "bad arguments");
-    AT_REQUIRE(!h->finalized, "model already finalized");
-    HostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-    t.data.assign(host_data, host_data + n);
-    h->staged[name] = std::move(t);
-    return 0;
+    return stage_tensor(h, name, host_data, shape, ndim);
 }
 
 int at_encodec_finalize(at_encodec_t* h, int with_decoder) {
@@ -1357,29 +1356,9 @@ int at_encodec_range_sites(char* names, size_t cap) {
     return (int)AC_NSITES;
 }
 
-int at_encodec_profile(at_encodec_t* h, int enable) {
-    AT_REQUIRE(h != nullptr, "null handle");
-    h->prof.reset();
-    h->prof.enabled = enable != 0;
-    return 0;
-}
-
+int at_encodec_profile(at_encodec_t* h, int enable) { return profile_enable(h, enable); }
 int at_encodec_profile_read(at_encodec_t* h, char* names, size_t names_cap, float* total_ms, int* launches, int max_groups) {
-    AT_REQUIRE(h && names && total_ms && launches, "null pointer");
-    std::vector<float> ms;
-    std::vector<int> ln;
-    if (h->prof.read(ms, ln) != 0) { set_error("profile read: event query failed"); return -2; }
-    std::string joined;
-    int n = 0;
-    for (size_t i = 0; i < h->prof.names.size() && n < max_groups; ++i, ++n) {
-        joined += h->prof.names[i];
-        joined += '\n';
-        total_ms[n] = ms[i];
-        launches[n] = ln[i];
-    }
-    AT_REQUIRE(joined.size() + 1 <= names_cap, "names buffer too small");
-    std::memcpy(names, joined.c_str(), joined.size() + 1);
-    return n;
+    return profile_read(h, names, names_cap, total_ms, launches, max_groups);
 }
 
 size_t at_encodec_decode_workspace_bytes(const at_encodec_t* h, int B, int T) {

@@ -7,17 +7,13 @@
 //   feature-extractor convs [512][Cin][k] -> [512][k*Cin] (tap-major, channels-last windows); conv 0 keeps [512][10]
 //   positional conv (weight-norm folded by the caller) [768][48][128], groups 16 -> 16 x [48][128*48]
 //   q,k,v Linear -> one [2304][768]
-#include <map>
 #include <string>
 #include <vector>
 #include <cstring>
 
 #include "../../include/audiotoken_hip.h"
-#include "at_common.h"
+#include "semantic_handle.h"
 #include "hubert_kernels.h"
-#include "gemm_bf16x3.h"
-#include "packed_model.h"
-#include <cstdlib>
 #include "w2vbert_kernels.h"
 
 using namespace at;
@@ -26,10 +22,6 @@ namespace {
 constexpr int kCd = 512, kHid = 768, kFfn = 3072, kHeads = 12, kPosK = 128, kGroups = 16, kGc = 48, kCenters = 1000, kCentersPad = 1024;
 constexpr int kKs[7] = {10, 3, 3, 3, 3, 2, 2}, kSt[7] = {5, 2, 2, 2, 2, 2, 2};
 
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
 struct LayerW {
     const float *wqkv, *bqkv, *wo, *bo, *ln1_g, *ln1_b, *w1, *b1, *w2, *b2, *ln2_g, *ln2_b;
     // the four linear layers as 16-bit operand pieces per scheme [XB_SCHEME_*][HW_*] (gemm_bf16x3.h); wscale: the fp16 scheme's weight scales
@@ -41,78 +33,44 @@ struct LayerW {
     float xs_qkv = XB_F16_ACT_SCALE, xs_ffn = XB_F16_ACT_SCALE;
 };
 enum { HW_QKV = 0, HW_O, HW_1, HW_2 };
-enum { ARITH_F32 = 0, ARITH_BF16X3 = 1, ARITH_F16X2 = 2 };
-}  // namespace
 
-struct at_hubert {
-    int device = 0;
-    bool finalized = false;
-    std::map<std::string, HostTensor> staged;
-    DeviceArena arena;          // every device allocation of finalize(), in order (packed_model.h: export / import of the finalized model)
-    PackedHeader imp{};         // import_packed: the exporter's record (layer count, flags) while finalize is replayed
-    std::vector<int> split_seq; // the schemes whose weight pieces exist, in the order they were split (= their order in the arena)
-    int* range_tab = nullptr;   // device, {flag, census} per (row, HSite): row 0 = conv feature encoder + positional conv, row 1 + l = transformer layer l; zeroed per encode
-    std::vector<int> layer_arith;   // per transformer layer: -1 = the handle's arithmetic, else ARITH_BF16X3 / ARITH_F16X2 for that layer only (option "layer_arith:<i>")
+// Sites of the handle's range table (semantic_handle.h, RangeTable): where activations become fp16 pieces
+enum HSite { HS_CONV0 = 0, HS_FE_CONV, HS_X_IN, HS_QKV_KV, HS_ATTENTION, HS_FFN_HIDDEN, HS_OTHER, H_NSITES };
+static const char* const kHSiteNames[H_NSITES] = {"conv0_out", "feature_convs", "layer_input", "qkv_kv", "attention", "ffn_hidden", "other"};
+// rows of the range table: row 0 = conv feature encoder + positional conv, row 1 + l = transformer layer l, up to 32 layers
+constexpr int kRangeRows = 33, kRangeLayer0 = 1;
+
+// what finalize builds on the device
+struct HubertW {
     const float* conv_w[7] = {};
     const float *gn_g = nullptr, *gn_b = nullptr, *fp_ln_g = nullptr, *fp_ln_b = nullptr, *fp_w = nullptr, *fp_b = nullptr;
     const float *pos_w = nullptr, *pos_b = nullptr, *enc_ln_g = nullptr, *enc_ln_b = nullptr;
     std::vector<LayerW> layers;
     const float *centers = nullptr, *c2 = nullptr;
     const piece_t* conv_ws[2][7] = {};   // conv weights of layers 1..6 as operand pieces, per scheme
+    float conv_wscale[7] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
     const piece_t* pos_ws = nullptr;     // positional-conv weights as fp16 pieces in the per-K-step layout of hubert_posconv.hip (f16x2 scheme only)
     float pos_wscale = 1.f;
     const piece_t* cen_s[2] = {};        // the k-means centres as operand pieces per scheme, rows padded 1000 -> 1024 (zero rows): the score GEMM on the split kernel
     float cen_scale = 1.f;
-    bool kmeans_split = true;            // option "kmeans_split": that GEMM on the split kernel instead of the fp32 MFMA (as at_w2vbert's "vq_split")
-    bool vq_refine = true;               // option "vq_refine" (round 5): near-tie centres re-evaluated exactly (vq_argmax_kernel)
+};
+}  // namespace
+
+struct at_hubert : SemanticHandle, HubertW {
+    bool kmeans_split = true;            // option "kmeans_split": the score GEMM on the split kernel instead of the fp32 MFMA (as at_w2vbert's "vq_split")
     bool ln_split = true;                // option "ln_split" (round 5): the post-LN LayerNorms write the fp32 residual stream AND the next GEMM's operand pieces in one pass (launch_layernorm_split, D = 768) instead of LayerNorm + a separate split pass; bit-identical
     bool posconv_split = true;           // option "posconv_split": the LDS-resident grouped conv kernel (hubert_posconv.hip) instead of 16 fp32 windowed GEMMs
-    float conv_wscale[7] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-    int arith = ARITH_F16X2;   // linear layers + conv chain: ARITH_* ($AUDIOTOKEN_SEMANTIC_ARITH = f32 | bf16x3 | f16x2; option "arith")
-    bool split_done[2] = {false, false};
-    int attn_w8 = -1;          // option "attn_w8" (as at_w2vbert): the round-4 attention kernel (attention_f16x2_w8.hip) or its round-3 twin
-    std::map<const float*, float> wmax;   // max |w| of every uploaded tensor
-    Profiler prof;
+    explicit at_hubert(int device_id) : SemanticHandle(PACKED_MODEL_HUBERT, device_id, RangeTable{kRangeRows, (int)H_NSITES, kRangeLayer0}) {
+        bool_opts = {{"posconv_split", &posconv_split}, {"ln_split", &ln_split}, {"kmeans_split", &kmeans_split}};
+    }
+    int finalize_model() override;
+    int split_model(int scheme) override;
+    void forget_model() override { static_cast<HubertW&>(*this) = HubertW{}; }
+    int num_layers() const override { return (int)layers.size(); }
+    bool has_codes() const override { return centers != nullptr; }
 };
 
 namespace {
-
-const HostTensor* find(const at_hubert* h, const std::string& name) {
-    auto it = h->staged.find(name);
-    return it == h->staged.end() ? nullptr : &it->second;
-}
-const float* upload(at_hubert* h, const std::vector<float>& v) {
-    const size_t n = (v.size() + 3) / 4 * 4;
-    float* d = static_cast<float*>(h->arena.alloc(n * sizeof(float)));
-    if (!d) return nullptr;
-    if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    float mx = 0.f;
-    for (float x : v) mx = std::fmax(mx, std::fabs(x));
-    h->arena.blocks.back().wmax = mx;
-    h->wmax[d] = mx;
-    return d;
-}
-// import_packed: the tensor's bytes are already in the blob — take the next slice and the recorded max |w|
-const float* reserve(at_hubert* h, size_t n_floats) {
-    float* d = static_cast<float*>(h->arena.alloc((n_floats + 3) / 4 * 4 * sizeof(float)));
-    if (d) h->wmax[d] = h->arena.blocks.back().wmax;
-    return d;
-}
-const float* take(at_hubert* h, const std::string& name, std::vector<int64_t> shape, bool& ok) {
-    if (h->arena.importing) {
-        size_t n = 1;
-        for (int64_t d : shape) n *= (size_t)d;
-        const float* d = reserve(h, n);
-        if (!d) ok = false;
-        return d;
-    }
-    const HostTensor* t = find(h, name);
-    if (!t) { set_error("missing tensor " + name); ok = false; return nullptr; }
-    if (t->shape != shape) { set_error("bad shape for " + name); ok = false; return nullptr; }
-    const float* d = upload(h, t->data);
-    if (!d) { set_error("device allocation/copy failed for " + name); ok = false; }
-    return d;
-}
 
 struct Plan {
     int L[8];   // L[0] = N, L[i+1] = frames after conv i
@@ -160,73 +118,11 @@ Plan make_plan(int B, int N) {
     return p;
 }
 
-// Sites of the handle's range table (gemm_bf16x3.h, launch_range_combine): where activations become fp16 pieces
-enum HSite { HS_CONV0 = 0, HS_FE_CONV, HS_X_IN, HS_QKV_KV, HS_ATTENTION, HS_FFN_HIDDEN, HS_OTHER, H_NSITES };
-static const char* const kHSiteNames[H_NSITES] = {"conv0_out", "feature_convs", "layer_input", "qkv_kv", "attention", "ffn_hidden", "other"};
-constexpr int kRangeRows = 33;                               // rows of the range table: the front end + up to 32 transformer layers
-constexpr int kRangeInts = kRangeRows * 2 * (int)H_NSITES;
 struct SplitCtx {
     int scheme; int* tab;
     int* site(int k) const { return tab ? tab + 2 * k : nullptr; }
     float act_scale() const { return scheme == XB_SCHEME_F16X2 ? XB_F16_ACT_SCALE : 1.0f; }
 };
-
-// Split the conv chain's and the transformer's weights into the 16-bit pieces of `scheme` (once per scheme)
-int split_weights(at_hubert* h, int scheme) {
-    if (h->split_done[scheme]) return 0;
-    const int np = xb_pieces(scheme);
-    auto one = [&](const float* src, int n, int k, const piece_t** dst, float* scale_out, int win_cblocks = 0, int win_stride = 1) -> int {
-        piece_t* d = static_cast<piece_t*>(h->arena.alloc((size_t)np * n * k * sizeof(piece_t)));
-        if (!d) return -1;
-        float sc = 1.0f;
-        if (scheme == XB_SCHEME_F16X2) {
-            auto it = h->wmax.find(src);
-            AT_REQUIRE(it != h->wmax.end(), "weight maximum not recorded");
-            sc = xb_weight_scale(it->second);
-            *scale_out = sc;
-        }
-        if (!h->arena.importing)   // import_packed: the pieces are in the blob
-            if (int rc = launch_split_blocked(src, k, n, n, k, d, nullptr, scheme, sc, nullptr, win_cblocks, win_stride)) return rc;
-        *dst = d;
-        return 0;
-    };
-    for (int i = 1; i < 7; ++i)
-        if (int rc = one(h->conv_w[i], kCd, kKs[i] * kCd, &h->conv_ws[scheme][i], &h->conv_wscale[i], kCd / 16, kSt[i])) return rc;   // window order
-    if (scheme == XB_SCHEME_F16X2) {   // the positional conv's weights in hubert_posconv.hip's layout ([group][K step][piece][k-block][48][16])
-        piece_t* d = static_cast<piece_t*>(h->arena.alloc(posconv_weight_pieces_bytes()));
-        if (!d) return -1;
-        auto it = h->wmax.find(h->pos_w);
-        AT_REQUIRE(it != h->wmax.end(), "weight maximum not recorded");
-        h->pos_wscale = xb_weight_scale(it->second);
-        if (!h->arena.importing)
-            if (int rc = launch_posconv_weight_split(h->pos_w, d, h->pos_wscale, nullptr)) return rc;
-        h->pos_ws = d;
-    }
-    for (LayerW& L : h->layers) {
-        const float* src[4] = {L.wqkv, L.wo, L.w1, L.w2};
-        const int ns[4] = {3 * kHid, kHid, kFfn, kHid}, ks[4] = {kHid, kHid, kHid, kFfn};
-        for (int j = 0; j < 4; ++j)
-            if (int rc = one(src[j], ns[j], ks[j], &L.ws[scheme][j], &L.wscale[j])) return rc;
-    }
-    if (h->centers) {   // k-means centres [1000][768] -> pieces of 1024 rows (the last 24 zero: their scores are never read)
-        piece_t* d = static_cast<piece_t*>(h->arena.alloc((size_t)np * kCentersPad * kHid * sizeof(piece_t)));
-        if (!d) return -1;
-        float sc = 1.0f;
-        if (scheme == XB_SCHEME_F16X2) {
-            auto it = h->wmax.find(h->centers);
-            AT_REQUIRE(it != h->wmax.end(), "weight maximum not recorded");
-            sc = xb_weight_scale(it->second);
-            h->cen_scale = sc;
-        }
-        if (!h->arena.importing)
-            if (int rc = launch_split_blocked(h->centers, kHid, kCenters, kCentersPad, kHid, d, nullptr, scheme, sc, nullptr)) return rc;
-        h->cen_s[scheme] = d;
-    }
-    AT_CHECK_HIP(hipDeviceSynchronize());
-    h->split_done[scheme] = true;
-    h->split_seq.push_back(scheme);
-    return 0;
-}
 
 // C = epi(X . W^T) through the split GEMM: X fp32 row-major [M][K] is split into xs first (unless it already is: X == nullptr)
 // x_scale: the f16x2 scale of the A operand (the pieces in xs, or what X is split with here); 16 except at the LayerNorm-fed sites
@@ -256,33 +152,33 @@ int linear(const float* X, int K, const float* W, const float* bias, float* C, i
 
 }  // namespace
 
-extern "C" {
-
-at_hubert_t* at_hubert_create(int device_id) {
-    int n = 0;
-    if (!host_only_test() && (hipGetDeviceCount(&n) != hipSuccess || device_id < 0 || device_id >= n)) {
-        set_error("at_hubert_create: no such HIP device " + std::to_string(device_id));
-        return nullptr;
+// Split the conv chain's and the transformer's weights into the 16-bit pieces of `scheme`
+int at_hubert::split_model(int scheme) {
+    at_hubert* const h = this;
+    for (int i = 1; i < 7; ++i)
+        if (int rc = split_one(h, scheme, h->conv_w[i], kCd, kKs[i] * kCd, &h->conv_ws[scheme][i], &h->conv_wscale[i], 0, kCd / 16, kSt[i])) return rc;   // window order
+    if (scheme == XB_SCHEME_F16X2) {   // the positional conv's weights in hubert_posconv.hip's layout ([group][K step][piece][k-block][48][16])
+        piece_t* d = static_cast<piece_t*>(h->arena.alloc(posconv_weight_pieces_bytes()));
+        if (!d) return -1;
+        if (int rc = weight_scale(h, h->pos_w, &h->pos_wscale)) return rc;
+        if (!h->arena.importing)
+            if (int rc = launch_posconv_weight_split(h->pos_w, d, h->pos_wscale, nullptr)) return rc;
+        h->pos_ws = d;
     }
-    at_hubert* h = new at_hubert();
-    h->device = device_id;
-    return h;
-}
-
-int at_hubert_set_tensor(at_hubert_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-    AT_REQUIRE(h && name && host_data && shape && ndim >= 1 && ndim <= 4, "bad arguments");
-    AT_REQUIRE(!h->finalized, "model already finalized");
-    HostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-    t.data.assign(host_data, host_data + n);
-    h->staged[name] = std::move(t);
+    for (LayerW& L : h->layers) {
+        const float* src[4] = {L.wqkv, L.wo, L.w1, L.w2};
+        const int ns[4] = {3 * kHid, kHid, kFfn, kHid}, ks[4] = {kHid, kHid, kHid, kFfn};
+        for (int j = 0; j < 4; ++j)
+            if (int rc = split_one(h, scheme, src[j], ns[j], ks[j], &L.ws[scheme][j], &L.wscale[j])) return rc;
+    }
+    if (h->centers)   // k-means centres [1000][768] -> pieces of 1024 rows (the last 24 zero: their scores are never read)
+        if (int rc = split_one(h, scheme, h->centers, kCenters, kHid, &h->cen_s[scheme], &h->cen_scale, kCentersPad)) return rc;
     return 0;
 }
 
-// finalize(): staged host tensors -> device. With the arena in import mode (at_hubert_import_packed) the same code REPLAYS the allocation order over the
-// packed blob: no host tensor is read, nothing is uploaded or split — only the pointers and scales are rebuilt.
-static int finalize_impl(at_hubert* h) {
+// The model part of finalize(): staged host tensors -> device (semantic_handle.h, finalize_model)
+int at_hubert::finalize_model() {
+    at_hubert* const h = this;
     const bool imp = h->arena.importing;
     bool ok = true;
     for (int i = 0; i < 7; ++i) {
@@ -394,99 +290,25 @@ static int finalize_impl(at_hubert* h) {
         h->c2 = upload(h, c2);
         AT_REQUIRE(h->centers && h->c2, "device allocation failed");
     }
-    h->staged.clear();
-    if (imp) {
-        h->arith = h->imp.arith;
-    } else {
-        h->arith = ARITH_F16X2;
-        if (const char* e = std::getenv("AUDIOTOKEN_SEMANTIC_ARITH")) {
-            const std::string v(e);
-            AT_REQUIRE(v == "f32" || v == "bf16x3" || v == "f16x2", "AUDIOTOKEN_SEMANTIC_ARITH must be f32, bf16x3 or f16x2");
-            h->arith = v == "f32" ? ARITH_F32 : v == "bf16x3" ? ARITH_BF16X3 : ARITH_F16X2;
-        }
-    }
-    if (imp) {
-        // the exporter's splits in ITS order (flags bits 1-2 = count, bits 3.. = one bit per split: 1 = bf16x3). Normally one: the default scheme at
-        // finalize; two when the per-batch range fallback had run there (the other scheme is split lazily, and the handle's current arithmetic may be either)
-        const int n = (h->imp.flags >> 1) & 3;
-        for (int i = 0; i < n; ++i)
-            if (int rc = split_weights(h, ((h->imp.flags >> (3 + i)) & 1) ? XB_SCHEME_BF16X3 : XB_SCHEME_F16X2)) return rc;
-    } else if (h->arith != ARITH_F32) {
-        if (int rc = split_weights(h, h->arith == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3)) return rc;
-    }
-    if (!host_only_test() && !h->range_tab) {   // run-time state, not part of the packed model
-        // the table and, behind it, its per-encode initial image: row 0 = {flag 0, census 0} per site; every further row {flag 0, LINK to row 0's census word of
-        // that site} (split_scheme.h, range_publish): one flag word per (row, site), one census word per site
-        AT_CHECK_HIP(hipMalloc((void**)&h->range_tab, 2 * kRangeInts * sizeof(int)));
-        std::vector<int> init(kRangeInts, 0);
-        for (int r = 1; r < kRangeRows; ++r)
-            for (int k = 0; k < (int)H_NSITES; ++k) init[(r * (int)H_NSITES + k) * 2 + 1] = -(r * (int)H_NSITES * 2);
-        AT_CHECK_HIP(hipMemcpy(h->range_tab + kRangeInts, init.data(), kRangeInts * sizeof(int), hipMemcpyHostToDevice));
-        AT_CHECK_HIP(hipMemcpy(h->range_tab, init.data(), kRangeInts * sizeof(int), hipMemcpyHostToDevice));
-    }
-    h->finalized = true;
     return 0;
 }
 
-int at_hubert_finalize(at_hubert_t* h) {
-    AT_REQUIRE(h && !h->finalized, "bad handle");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    return finalize_impl(h);
-}
+extern "C" {
 
-// ---- the finalized model as one device blob (packed_model.h) ------------------------------------------------------------------------------
-static int packed_flags(const at_hubert* h) {
-    int f = (h->centers ? 1 : 0) | ((int)h->split_seq.size() << 1);
-    for (size_t i = 0; i < h->split_seq.size(); ++i) f |= (h->split_seq[i] == XB_SCHEME_BF16X3 ? 1 : 0) << (3 + i);
-    return f;
+at_hubert_t* at_hubert_create(int device_id) { return device_exists("at_hubert_create", device_id) ? new at_hubert(device_id) : nullptr; }
+int at_hubert_set_tensor(at_hubert_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
+    return stage_tensor(h, name, host_data, shape, ndim);
 }
-int64_t at_hubert_packed_bytes(at_hubert_t* h) {
-    if (!h || !h->finalized) { set_error("at_hubert_packed_bytes: model not finalized"); return -1; }
-    return (int64_t)h->arena.packed_bytes();
-}
-int64_t at_hubert_packed_meta(at_hubert_t* h, void* host_dst, int64_t cap) {
-    if (!h || !h->finalized) { set_error("at_hubert_packed_meta: model not finalized"); return -1; }
-    return packed_write_meta(h->arena, PACKED_MODEL_HUBERT, (int)h->layers.size(), packed_flags(h), h->arith, host_dst, cap);
-}
+int at_hubert_finalize(at_hubert_t* h) { return sem_finalize(h); }
+int64_t at_hubert_packed_bytes(at_hubert_t* h) { return sem_packed_bytes(h, "at_hubert_packed_bytes"); }
+int64_t at_hubert_packed_meta(at_hubert_t* h, void* host_dst, int64_t cap) { return sem_packed_meta(h, "at_hubert_packed_meta", host_dst, cap); }
 int at_hubert_export_packed(at_hubert_t* h, void* device_dst, int64_t bytes, void* stream) {
-    AT_REQUIRE(h && h->finalized, "at_hubert_export_packed: model not finalized");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    return packed_export(h->arena, device_dst, bytes, (hipStream_t)stream);
+    return sem_export_packed(h, "at_hubert_export_packed", device_dst, bytes, stream);
 }
 int at_hubert_import_packed(at_hubert_t* h, const void* host_meta, int64_t meta_bytes, const void* device_src, int64_t bytes, void* stream) {
-    AT_REQUIRE(h && !h->finalized && h->staged.empty(), "at_hubert_import_packed needs a fresh handle (no set_tensor, no finalize)");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    if (int rc = packed_begin_import(h->arena, PACKED_MODEL_HUBERT, host_meta, meta_bytes, device_src, bytes, (hipStream_t)stream, &h->imp)) return rc;
-    int rc = finalize_impl(h);
-    if (!rc) rc = packed_end_import(h->arena);
-    if (rc) {
-        // a failed import leaves an EMPTY handle that can only be destroyed (or imported into again): not a half-built model that reports `finalized`
-        h->finalized = false;
-        h->arena.importing = false;
-        h->layers.clear();
-        h->split_seq.clear();
-        h->split_done[0] = h->split_done[1] = false;
-        h->wmax.clear();
-        h->centers = h->c2 = nullptr;
-        h->pos_ws = nullptr;
-        for (int s = 0; s < 2; ++s)
-            for (int j = 0; j < 7; ++j) h->conv_ws[s][j] = nullptr;
-        h->arena.free_all();
-        if (h->range_tab) { (void)hipFree(h->range_tab); h->range_tab = nullptr; }
-    }
-    return rc;
+    return sem_import_packed(h, "at_hubert_import_packed", host_meta, meta_bytes, device_src, bytes, stream);
 }
-
-void at_hubert_destroy(at_hubert_t* h) {
-    if (!h) return;
-    DeviceGuard guard(h->device);   // restores the caller's current device
-    h->arena.free_all();
-    if (h->range_tab) (void)hipFree(h->range_tab);
-    delete h;
-}
+void at_hubert_destroy(at_hubert_t* h) { sem_destroy(h); }
 
 int at_hubert_num_layers(const at_hubert_t* h) { return h ? (int)h->layers.size() : 0; }
 
@@ -502,54 +324,8 @@ size_t at_hubert_workspace_bytes(const at_hubert_t* h, int B, int N) {
     return make_plan(B, N).total_floats * sizeof(float);
 }
 
-int at_hubert_set_option(at_hubert_t* h, const char* name, int value) {
-    AT_REQUIRE(h && h->finalized && name, "bad handle");
-    const std::string n(name);
-    if (n == "arith") {
-        AT_REQUIRE(value == ARITH_F32 || value == ARITH_BF16X3 || value == ARITH_F16X2, "arith: 0 = f32 MFMA, 1 = bf16x3, 2 = f16x2");
-        DeviceGuard guard(h->device);
-        AT_REQUIRE(guard.ok, "cannot select the handle's device");
-        if (value != ARITH_F32)
-            if (int rc = split_weights(h, value == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3)) return rc;
-        h->arith = value;
-        return 0;
-    }
-    if (n.rfind("layer_arith:", 0) == 0) {   // "layer_arith:<l>": -1 = follow "arith", 1 = bf16x3, 2 = f16x2 for transformer layer l only
-        const int li = std::atoi(n.c_str() + 12);
-        AT_REQUIRE(li >= 0 && li < (int)h->layers.size(), "layer_arith: no such layer");
-        AT_REQUIRE(value == -1 || value == ARITH_BF16X3 || value == ARITH_F16X2, "layer_arith:<l>: -1 = the handle's arithmetic, 1 = bf16x3, 2 = f16x2");
-        if (value > 0) {
-            DeviceGuard guard(h->device);
-            AT_REQUIRE(guard.ok, "cannot select the handle's device");
-            if (int rc = split_weights(h, value == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3)) return rc;
-        }
-        if (h->layer_arith.size() < h->layers.size()) h->layer_arith.resize(h->layers.size(), -1);
-        h->layer_arith[li] = value;
-        return 0;
-    }
-    if (n == "attn_w8") { h->attn_w8 = value < 0 ? -1 : (value != 0); return 0; }
-    if (n == "posconv_split") { h->posconv_split = value != 0; return 0; }
-    if (n == "ln_split") { h->ln_split = value != 0; return 0; }
-    if (n == "vq_refine") { h->vq_refine = value != 0; return 0; }
-    if (n == "kmeans_split") { h->kmeans_split = value != 0; return 0; }
-    set_error("at_hubert_set_option: unknown option " + n);
-    return -1;
-}
-
-int at_hubert_get_option(const at_hubert_t* h, const char* name) {
-    if (!h || !name) return -1;
-    if (std::string(name) == "arith") return h->arith;
-    if (std::string(name).rfind("layer_arith:", 0) == 0) {
-        const int li = std::atoi(name + 12);
-        return (li >= 0 && li < (int)h->layer_arith.size()) ? h->layer_arith[li] : -1;
-    }
-    if (std::string(name) == "attn_w8") return h->attn_w8;
-    if (std::string(name) == "posconv_split") return h->posconv_split ? 1 : 0;
-    if (std::string(name) == "ln_split") return h->ln_split ? 1 : 0;
-    if (std::string(name) == "vq_refine") return h->vq_refine ? 1 : 0;
-    if (std::string(name) == "kmeans_split") return h->kmeans_split ? 1 : 0;
-    return -1;
-}
+int at_hubert_set_option(at_hubert_t* h, const char* name, int value) { return sem_set_option(h, "at_hubert_set_option", name, value); }
+int at_hubert_get_option(const at_hubert_t* h, const char* name) { return sem_get_option(h, name); }
 
 int at_hubert_encode(at_hubert_t* h, const float* wav, const float* mask, int B, int N, int n_layers, int16_t* tokens, int* T_out,
                      float* hidden_out, void* workspace, size_t workspace_bytes, at_stream_t stream_) {
@@ -575,12 +351,11 @@ int at_hubert_encode_checked(at_hubert_t* h, const float* wav, const float* mask
     Profiler& prof = h->prof;
     if (status_dev) AT_CHECK_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), (hipStream_t)stream_));
     const bool split = h->arith != ARITH_F32;
-    AT_REQUIRE(n_layers + 1 <= kRangeRows, "more transformer layers than range-table rows");
-    AT_CHECK_HIP(hipMemcpyAsync(h->range_tab, h->range_tab + kRangeInts, kRangeInts * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream_));   // flags 0, census 0 / links
-    const SplitCtx sc{h->arith == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, h->range_tab};   // the front end (row 0) and the k-means GEMM
+    AT_REQUIRE(kRangeLayer0 + n_layers <= kRangeRows, "more transformer layers than range-table rows");
+    if (int rc = h->range.reset((hipStream_t)stream_)) return rc;
+    const SplitCtx sc{h->arith == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, h->range.dev};   // the front end (row 0) and the k-means GEMM
     // transformer layer l: its own row of the range table and, when the range fallback has pinned it (option "layer_arith:<l>"), its own arithmetic
-    auto arith_of = [&](int li) { return (split && li < (int)h->layer_arith.size() && h->layer_arith[li] > 0) ? h->layer_arith[li] : h->arith; };
-    auto ctx_of = [&](int li) { return SplitCtx{arith_of(li) == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, h->range_tab + (1 + li) * 2 * (int)H_NSITES}; };
+    auto ctx_of = [&](int li) { return SplitCtx{h->arith_of(li) == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, h->range.layer_row(li)}; };
 
     // ---- conv feature encoder (7 valid strided convs, GroupNorm after the first, GELU) ----------------------
     float* bufs[2] = {ws + p.off_a, ws + p.off_b};
@@ -669,7 +444,7 @@ int at_hubert_encode_checked(at_hubert_t* h, const float* wav, const float* mask
     for (int li = 0; li < n_layers; ++li) {
         const LayerW& L = h->layers[li];
         const SplitCtx scl = ctx_of(li);              // this layer's scheme and range row
-        const int attn_arith_l = split ? arith_of(li) : attn_arith;
+        const int attn_arith_l = split ? h->arith_of(li) : attn_arith;
         prof.begin("attn_proj", 3, stream);
         // f16x2: the projection's epilogue writes k / v as fp16 pieces, the attention kernel stages them unsplit and writes its context as the
         // output projection's operand pieces (as in w2vbert.hip)
@@ -713,7 +488,7 @@ int at_hubert_encode_checked(at_hubert_t* h, const float* wav, const float* mask
         prof.end(stream);
     }
     if (status_dev)   // every site's range verdict of this call -> the caller's status word
-        if (int rc = launch_range_combine(h->range_tab, (1 + n_layers) * (int)H_NSITES, reinterpret_cast<int*>(status_dev), stream)) return rc;
+        if (int rc = launch_range_combine(h->range.dev, (kRangeLayer0 + n_layers) * (int)H_NSITES, reinterpret_cast<int*>(status_dev), stream)) return rc;
     if (hidden_out) AT_CHECK_HIP(hipMemcpyAsync(hidden_out, x, (size_t)M * kHid * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (tokens) {
         prof.begin("kmeans", 3, stream);
@@ -738,39 +513,9 @@ int at_hubert_encode_checked(at_hubert_t* h, const float* wav, const float* mask
     return 0;
 }
 
-// The measured fp16 headroom of the LAST encode of this handle (see at_w2vbert_range_report)
-int at_hubert_range_report(at_hubert_t* h, float* max_scaled, int cap) {
-    AT_REQUIRE(h && h->finalized && h->range_tab && max_scaled && cap >= (int)H_NSITES, "at_hubert_range_report: bad arguments");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    std::vector<int> host(kRangeInts);
-    AT_CHECK_HIP(hipDeviceSynchronize());
-    AT_CHECK_HIP(hipMemcpy(host.data(), h->range_tab, kRangeInts * sizeof(int), hipMemcpyDeviceToHost));
-    for (int k = 0; k < (int)H_NSITES; ++k) {
-        float f;   // row 0 holds the one census word of the site; the other rows' second words are links to it (split_scheme.h)
-        std::memcpy(&f, &host[k * 2 + 1], sizeof(f));
-        max_scaled[k] = f;
-    }
-    return (int)H_NSITES;
-}
-// Status flags of the LAST encode per part of the model: flags[0] = conv feature encoder + positional conv, flags[1 + l] = transformer layer l (the OR of its
-// split sites; bit 1 = an activation left the fp16 range; the FIRST flagged entry is the cause, later ones inherit its infinities). Returns the number of
-// entries written (1 + layers, <= cap). Synchronises the device. (As at_w2vbert_layer_status.)
-int at_hubert_layer_status(at_hubert_t* h, int32_t* flags, int cap) {
-    AT_REQUIRE(h && h->finalized && h->range_tab && flags && cap >= 1, "at_hubert_layer_status: bad arguments");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    std::vector<int> host(kRangeInts);
-    AT_CHECK_HIP(hipDeviceSynchronize());
-    AT_CHECK_HIP(hipMemcpy(host.data(), h->range_tab, kRangeInts * sizeof(int), hipMemcpyDeviceToHost));
-    const int n = std::min<int>({cap, 1 + (int)h->layers.size(), kRangeRows});
-    for (int r = 0; r < n; ++r) {
-        int v = 0;
-        for (int k = 0; k < (int)H_NSITES; ++k) v |= host[(r * (int)H_NSITES + k) * 2];
-        flags[r] = v;
-    }
-    return n;
-}
+int at_hubert_range_report(at_hubert_t* h, float* max_scaled, int cap) { return sem_range_report(h, "at_hubert_range_report", max_scaled, cap); }
+// flags[0] = conv feature encoder + positional conv, flags[1 + l] = transformer layer l: 1 + layers entries
+int at_hubert_layer_status(at_hubert_t* h, int32_t* flags, int cap) { return sem_layer_status(h, "at_hubert_layer_status", flags, cap); }
 // The activation scales of the two LayerNorm-fed split sites of every transformer layer: scales[2 l] = the q/k/v projection's input, scales[2 l + 1] = the
 // first FFN GEMM's input (16 unless a LayerNorm's gains force the provable scale below that). Returns the number of floats written. Host-only.
 int at_hubert_site_scales(const at_hubert_t* h, float* scales, int cap) {
@@ -780,37 +525,11 @@ int at_hubert_site_scales(const at_hubert_t* h, float* scales, int cap) {
     for (size_t l = 0; l < h->layers.size(); ++l) { scales[2 * l] = h->layers[l].xs_qkv; scales[2 * l + 1] = h->layers[l].xs_ffn; }
     return n;
 }
-int at_hubert_range_sites(char* names, size_t cap) {
-    std::string s;
-    for (int k = 0; k < (int)H_NSITES; ++k) { s += kHSiteNames[k]; s += "\n"; }
-    if (!names || cap < s.size() + 1) return -(int)(s.size() + 1);
-    std::memcpy(names, s.c_str(), s.size() + 1);
-    return (int)H_NSITES;
-}
+int at_hubert_range_sites(char* names, size_t cap) { return range_sites(kHSiteNames, (int)H_NSITES, names, cap); }
 
-int at_hubert_profile(at_hubert_t* h, int enable) {
-    AT_REQUIRE(h != nullptr, "null handle");
-    h->prof.reset();
-    h->prof.enabled = enable != 0;
-    return 0;
-}
-
+int at_hubert_profile(at_hubert_t* h, int enable) { return profile_enable(h, enable); }
 int at_hubert_profile_read(at_hubert_t* h, char* names, size_t names_cap, float* total_ms, int* launches, int max_groups) {
-    AT_REQUIRE(h && names && total_ms && launches, "null pointer");
-    std::vector<float> ms;
-    std::vector<int> ln;
-    if (h->prof.read(ms, ln) != 0) { set_error("profile read: event query failed"); return -2; }
-    std::string joined;
-    int n = 0;
-    for (size_t i = 0; i < h->prof.names.size() && n < max_groups; ++i, ++n) {
-        joined += h->prof.names[i];
-        joined += '\n';
-        total_ms[n] = ms[i];
-        launches[n] = ln[i];
-    }
-    AT_REQUIRE(joined.size() + 1 <= names_cap, "names buffer too small");
-    std::memcpy(names, joined.c_str(), joined.size() + 1);
-    return n;
+    return profile_read(h, names, names_cap, total_ms, launches, max_groups);
 }
 
 }  // extern "C"

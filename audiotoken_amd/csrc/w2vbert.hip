@@ -15,18 +15,14 @@
 //   pointwise_conv1 [2048][1024][1] -> rows interleaved (a_c, b_c) so GLU is the GEMM epilogue
 //   depthwise_conv [1024][1][31] -> [31][1024]
 //   distance_embedding [73][64] -> [80][64] zero padded (MFMA row tiles)
-#include <map>
 #include <string>
 #include <vector>
 #include <cstring>
 #include <cmath>
 
 #include "../../include/audiotoken_hip.h"
-#include "at_common.h"
+#include "semantic_handle.h"
 #include "w2vbert_kernels.h"
-#include <cstdlib>
-#include "gemm_bf16x3.h"
-#include "packed_model.h"
 
 namespace at {
 const char* last_error_cstr();
@@ -36,11 +32,6 @@ using namespace at;
 namespace {
 constexpr int kHid = 1024, kFfn = 4096, kFeat = 160, kMel = 80, kFrame = 400, kHop = 160;
 constexpr int kSpecLd = 520, kImOff = 260, kCodes = 2048, kBuckets = 73;
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
 
 struct LayerW {
     const float *ln_ffn1_g, *ln_ffn1_b, *w1a, *b1a, *w1b, *b1b;
@@ -60,19 +51,16 @@ struct LayerW {
                             XB_F16_ACT_SCALE, XB_F16_ACT_SCALE, XB_F16_ACT_SCALE, XB_F16_ACT_SCALE, XB_F16_ACT_SCALE};
 };
 enum { W_1A = 0, W_1B, W_2A, W_2B, W_QKV, W_O, W_PW1, W_PW2 };
-// arithmetic of the linear layers: the fp32 MFMA, or operand splits on the 16-bit matrix cores (gemm_bf16x3.h)
-enum { ARITH_F32 = 0, ARITH_BF16X3 = 1, ARITH_F16X2 = 2 };
-}  // namespace
 
-struct at_w2vbert {
-    int device = 0;
-    bool finalized = false;
-    std::map<std::string, HostTensor> staged;
-    DeviceArena arena;          // every device allocation of finalize(), in order (packed_model.h: export / import of the finalized model)
-    PackedHeader imp{};         // import_packed: the exporter's record (layer count, flags) while finalize is replayed
-    std::vector<int> split_seq; // the schemes whose weight pieces exist, in the order they were split (= their order in the arena)
-    int* range_tab = nullptr;   // device, {flag, census} per (layer, WSite), zeroed at the start of every encode (at_w2vbert_range_report / _layer_status read it)
-    std::vector<int> layer_arith;   // per conformer layer: -1 = the handle's arithmetic, else ARITH_BF16X3 / ARITH_F16X2 for that layer only (option "layer_arith:<i>")
+// Sites of the handle's range table (semantic_handle.h, RangeTable): where activations become fp16 pieces. The same site in every layer.
+enum WSite { WS_LN_FFN1 = 0, WS_FFN1_HIDDEN, WS_LN_ATTN, WS_QKV_KV, WS_ATTENTION, WS_LN_CONV, WS_DWCONV, WS_LN_FFN2, WS_FFN2_HIDDEN, WS_OTHER, W_NSITES };
+static const char* const kWSiteNames[W_NSITES] = {"ln_ffn1", "ffn1_hidden", "ln_attn", "qkv_kv", "attention", "ln_conv", "dwconv_out", "ln_ffn2", "ffn2_hidden", "other"};
+static_assert((int)W_NSITES == 10, "LayerW::site_scale has one entry per WSite");
+// rows of the range table: one per conformer layer, layer l is row l, up to 64 layers
+constexpr int kRangeLayers = 64, kRangeLayer0 = 0;
+
+// what finalize builds on the device
+struct W2vBertW {
     const float *window = nullptr, *melw = nullptr;
     double* dft64 = nullptr;  // [520][400] DFT matrix in double (see dft_f64_kernel)
     const float *fp_ln_g = nullptr, *fp_ln_b = nullptr, *fp_w = nullptr, *fp_b = nullptr;
@@ -80,57 +68,23 @@ struct at_w2vbert {
     const float *codebook = nullptr, *e2 = nullptr;
     const piece_t* cb_s[2] = {};   // the code book as operand pieces, per scheme (the VQ score GEMM on the split kernel; option "vq_split")
     float cb_scale = 1.f;
+};
+}  // namespace
+
+struct at_w2vbert : SemanticHandle, W2vBertW {
     bool vq_split = true;
-    bool vq_refine = true;      // option "vq_refine" (round 5): near-tie codes re-evaluated exactly (vq_argmax_kernel); 0 = the expanded fp32 form alone, as rounds 1-4
-    int arith = ARITH_F16X2;   // linear layers: ARITH_* ($AUDIOTOKEN_SEMANTIC_ARITH = f32 | bf16x3 | f16x2; option "arith")
-    bool split_done[2] = {false, false};
-    std::map<const float*, float> wmax;   // max |w| of every uploaded tensor (the fp16 scheme's weight scales)
     bool dwconv_stream = true;  // option "dwconv_stream": depthwise conv + LayerNorm + swish on the streaming kernel (dwconv_stream.hip)
-    int attn_w8 = -1;           // option "attn_w8": 1 / 0 = the 8-wave 64-key LDS-DMA attention (attention_f16x2_w8.hip) / its round-3 twin; -1 = $AUDIOTOKEN_ATTN_W8, default 1
-    Profiler prof;
+    explicit at_w2vbert(int device_id) : SemanticHandle(PACKED_MODEL_W2VBERT, device_id, RangeTable{kRangeLayers, (int)W_NSITES, kRangeLayer0}) {
+        bool_opts = {{"dwconv_stream", &dwconv_stream}, {"vq_split", &vq_split}};
+    }
+    int finalize_model() override;
+    int split_model(int scheme) override;
+    void forget_model() override { static_cast<W2vBertW&>(*this) = W2vBertW{}; }
+    int num_layers() const override { return (int)layers.size(); }
+    bool has_codes() const override { return codebook != nullptr; }
 };
 
 namespace {
-
-const HostTensor* find(const at_w2vbert* h, const std::string& name) {
-    auto it = h->staged.find(name);
-    return it == h->staged.end() ? nullptr : &it->second;
-}
-
-// upload one packed tensor into its own device allocation (the model is ~1.8 GB: no second full host copy)
-const float* upload(at_w2vbert* h, const std::vector<float>& v) {
-    const size_t n = (v.size() + 3) / 4 * 4;
-    float* d = static_cast<float*>(h->arena.alloc(n * sizeof(float)));
-    if (!d) return nullptr;
-    if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    float mx = 0.f;
-    for (float x : v) mx = std::fmax(mx, std::fabs(x));
-    h->arena.blocks.back().wmax = mx;
-    h->wmax[d] = mx;
-    return d;
-}
-// import_packed: the tensor's bytes are already in the blob — take the next slice and the recorded max |w|
-const float* reserve(at_w2vbert* h, size_t n_floats) {
-    float* d = static_cast<float*>(h->arena.alloc((n_floats + 3) / 4 * 4 * sizeof(float)));
-    if (d) h->wmax[d] = h->arena.blocks.back().wmax;
-    return d;
-}
-
-const float* take(at_w2vbert* h, const std::string& name, std::vector<int64_t> shape, bool& ok) {
-    if (h->arena.importing) {
-        size_t n = 1;
-        for (int64_t d : shape) n *= (size_t)d;
-        const float* d = reserve(h, n);
-        if (!d) ok = false;
-        return d;
-    }
-    const HostTensor* t = find(h, name);
-    if (!t) { set_error("missing tensor " + name); ok = false; return nullptr; }
-    if (t->shape != shape) { set_error("bad shape for " + name); ok = false; return nullptr; }
-    const float* d = upload(h, t->data);
-    if (!d) { set_error("device allocation/copy failed for " + name); ok = false; }
-    return d;
-}
 
 int frames_of(int N) { return N >= kFrame ? 1 + (N - kFrame) / kHop : 0; }
 int tokens_of(int N, int mult) {
@@ -181,66 +135,6 @@ int linear(const float* X, int K, const float* W, const float* bias, float* C, i
     return launch_gemm(a, stream);
 }
 
-// Split the eight linear layers of every conformer layer into the 16-bit pieces of `scheme` (once per scheme)
-int split_weights(at_w2vbert* h, int scheme) {
-    if (h->split_done[scheme]) return 0;
-    const int np = xb_pieces(scheme);
-    for (LayerW& L : h->layers) {
-        const float* src[8] = {L.w1a, L.w1b, L.w2a, L.w2b, L.wqkv, L.wo, L.pw1, L.pw2};
-        const int ns[8] = {kFfn, kHid, kFfn, kHid, 3 * kHid, kHid, 2 * kHid, kHid}, ks[8] = {kHid, kFfn, kHid, kFfn, kHid, kHid, kHid, kHid};
-        for (int j = 0; j < 8; ++j) {
-            const int n = ns[j], k = ks[j];
-            piece_t* d = static_cast<piece_t*>(h->arena.alloc((size_t)np * n * k * sizeof(piece_t)));
-            if (!d) return -1;
-            float sc = 1.0f;
-            if (scheme == XB_SCHEME_F16X2) {
-                auto it = h->wmax.find(src[j]);
-                AT_REQUIRE(it != h->wmax.end(), "weight maximum not recorded");
-                sc = xb_weight_scale(it->second);
-                L.wscale[j] = sc;
-            }
-            if (!h->arena.importing)   // import_packed: the pieces are in the blob
-                if (int rc = launch_split_blocked(src[j], k, n, n, k, d, nullptr, scheme, sc, nullptr)) return rc;
-            L.ws[scheme][j] = d;
-        }
-        if (scheme == XB_SCHEME_F16X2) {   // distance embeddings -> pieces for the attention kernel's rel-pos table
-            piece_t* d = static_cast<piece_t*>(h->arena.alloc((size_t)2 * 96 * 64 * sizeof(piece_t)));
-            if (!d) return -1;
-            auto it = h->wmax.find(L.dist);
-            AT_REQUIRE(it != h->wmax.end(), "distance embedding maximum not recorded");
-            L.dist_scale = xb_weight_scale(it->second);
-            if (!h->arena.importing)
-                if (int rc = launch_dist_split(L.dist, d, L.dist_scale, nullptr)) return rc;
-            L.dist_s = d;
-        }
-    }
-    if (h->codebook) {   // the VQ score GEMM dots = LN(x) . E^T [M x 1024] x [1024 x 2048]
-        piece_t* d = static_cast<piece_t*>(h->arena.alloc((size_t)np * kCodes * kHid * sizeof(piece_t)));
-        if (!d) return -1;
-        float sc = 1.0f;
-        if (scheme == XB_SCHEME_F16X2) {
-            auto it = h->wmax.find(h->codebook);
-            AT_REQUIRE(it != h->wmax.end(), "code book maximum not recorded");
-            sc = xb_weight_scale(it->second);
-            h->cb_scale = sc;
-        }
-        if (!h->arena.importing)
-            if (int rc = launch_split_blocked(h->codebook, kHid, kCodes, kCodes, kHid, d, nullptr, scheme, sc, nullptr)) return rc;
-        h->cb_s[scheme] = d;
-    }
-    AT_CHECK_HIP(hipDeviceSynchronize());
-    h->split_done[scheme] = true;
-    h->split_seq.push_back(scheme);
-    return 0;
-}
-
-// One split-operand GEMM of the conformer: C / S = epi(A . W^T) with A given as pieces (gemm_bf16x3.hip)
-// Sites of the handle's range table (gemm_bf16x3.h, launch_range_combine): where activations become fp16 pieces. The same site in every layer.
-enum WSite { WS_LN_FFN1 = 0, WS_FFN1_HIDDEN, WS_LN_ATTN, WS_QKV_KV, WS_ATTENTION, WS_LN_CONV, WS_DWCONV, WS_LN_FFN2, WS_FFN2_HIDDEN, WS_OTHER, W_NSITES };
-static const char* const kWSiteNames[W_NSITES] = {"ln_ffn1", "ffn1_hidden", "ln_attn", "qkv_kv", "attention", "ln_conv", "dwconv_out", "ln_ffn2", "ffn2_hidden", "other"};
-static_assert((int)W_NSITES == 10, "LayerW::site_scale has one entry per WSite");
-constexpr int kRangeLayers = 64;                              // rows of the range table: one per conformer layer
-constexpr int kRangeInts = kRangeLayers * 2 * (int)W_NSITES;
 struct SplitCtx {
     int scheme; int* tab; const LayerW* L;
     int* site(int k) const { return tab ? tab + 2 * k : nullptr; }
@@ -254,6 +148,7 @@ int a_site_of(int w) {
         case W_QKV: return WS_LN_ATTN; case W_O: return WS_ATTENTION;     case W_PW1: return WS_LN_CONV; default: return WS_DWCONV;
     }
 }
+// One split-operand GEMM of the conformer: C / S = epi(A . W^T) with A given as pieces (gemm_bf16x3.hip)
 int gemm_split(const SplitCtx& c, const piece_t* A, const LayerW& L, int w, const float* bias, int N, int K, long long M, long long Mpad, int epi,
                float alpha, float* C, const float* R, int ldc, piece_t* S, hipStream_t stream) {
     Bf16x3Args a;
@@ -267,33 +162,31 @@ int gemm_split(const SplitCtx& c, const piece_t* A, const LayerW& L, int w, cons
 
 }  // namespace
 
-extern "C" {
-
-at_w2vbert_t* at_w2vbert_create(int device_id) {
-    int n = 0;
-    if (!host_only_test() && (hipGetDeviceCount(&n) != hipSuccess || device_id < 0 || device_id >= n)) {
-        set_error("at_w2vbert_create: no such HIP device " + std::to_string(device_id));
-        return nullptr;
+// Split the eight linear layers of every conformer layer into the 16-bit pieces of `scheme`
+int at_w2vbert::split_model(int scheme) {
+    at_w2vbert* const h = this;
+    for (LayerW& L : h->layers) {
+        const float* src[8] = {L.w1a, L.w1b, L.w2a, L.w2b, L.wqkv, L.wo, L.pw1, L.pw2};
+        const int ns[8] = {kFfn, kHid, kFfn, kHid, 3 * kHid, kHid, 2 * kHid, kHid}, ks[8] = {kHid, kFfn, kHid, kFfn, kHid, kHid, kHid, kHid};
+        for (int j = 0; j < 8; ++j)
+            if (int rc = split_one(h, scheme, src[j], ns[j], ks[j], &L.ws[scheme][j], &L.wscale[j])) return rc;
+        if (scheme == XB_SCHEME_F16X2) {   // distance embeddings -> pieces for the attention kernel's rel-pos table
+            piece_t* d = static_cast<piece_t*>(h->arena.alloc((size_t)2 * 96 * 64 * sizeof(piece_t)));
+            if (!d) return -1;
+            if (int rc = weight_scale(h, L.dist, &L.dist_scale)) return rc;
+            if (!h->arena.importing)
+                if (int rc = launch_dist_split(L.dist, d, L.dist_scale, nullptr)) return rc;
+            L.dist_s = d;
+        }
     }
-    at_w2vbert* h = new at_w2vbert();
-    h->device = device_id;
-    return h;
-}
-
-int at_w2vbert_set_tensor(at_w2vbert_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-    AT_REQUIRE(h && name && host_data && shape && ndim >= 1 && ndim <= 4, "bad arguments");
-    AT_REQUIRE(!h->finalized, "model already finalized");
-    HostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-    t.data.assign(host_data, host_data + n);
-    h->staged[name] = std::move(t);
+    if (h->codebook)   // the VQ score GEMM dots = LN(x) . E^T [M x 1024] x [1024 x 2048]
+        if (int rc = split_one(h, scheme, h->codebook, kCodes, kHid, &h->cb_s[scheme], &h->cb_scale)) return rc;
     return 0;
 }
 
-// finalize(): staged host tensors -> device. With the arena in import mode (at_w2vbert_import_packed) the same code REPLAYS the allocation order over
-// the packed blob: no host tensor is read, nothing is uploaded or split — only the pointers and scales are rebuilt.
-static int finalize_impl(at_w2vbert* h) {
+// The model part of finalize(): staged host tensors -> device (semantic_handle.h, finalize_model)
+int at_w2vbert::finalize_model() {
+    at_w2vbert* const h = this;
     const bool imp = h->arena.importing;
     bool ok = true;
     // ---- front-end tables --------------------------------------------------------------------
@@ -445,97 +338,25 @@ static int finalize_impl(at_w2vbert* h) {
         h->e2 = upload(h, e2);
         AT_REQUIRE(h->codebook && h->e2, "device allocation failed (codebook)");
     }
-    h->staged.clear();
-    if (imp) {
-        h->arith = h->imp.arith;
-    } else {
-        h->arith = ARITH_F16X2;
-        if (const char* e = std::getenv("AUDIOTOKEN_SEMANTIC_ARITH")) {
-            const std::string v(e);
-            AT_REQUIRE(v == "f32" || v == "bf16x3" || v == "f16x2", "AUDIOTOKEN_SEMANTIC_ARITH must be f32, bf16x3 or f16x2");
-            h->arith = v == "f32" ? ARITH_F32 : v == "bf16x3" ? ARITH_BF16X3 : ARITH_F16X2;
-        }
-    }
-    if (imp) {
-        // the exporter's splits in ITS order (flags bits 1-2 = count, bits 3.. = one bit per split: 1 = bf16x3). Normally one: the default scheme at
-        // finalize; two when the per-batch range fallback had run there (the other scheme is split lazily, and the handle's current arithmetic may be either)
-        const int n = (h->imp.flags >> 1) & 3;
-        for (int i = 0; i < n; ++i)
-            if (int rc = split_weights(h, ((h->imp.flags >> (3 + i)) & 1) ? XB_SCHEME_BF16X3 : XB_SCHEME_F16X2)) return rc;
-    } else if (h->arith != ARITH_F32) {
-        if (int rc = split_weights(h, h->arith == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3)) return rc;
-    }
-    if (!host_only_test() && !h->range_tab) {   // run-time state, not part of the packed model
-        // the table and, behind it, its per-encode initial image: row 0 = {flag 0, census 0} per site; every further row {flag 0, LINK to row 0's census word of
-        // that site} (split_scheme.h, range_publish): one flag word per (row, site), one census word per site
-        AT_CHECK_HIP(hipMalloc((void**)&h->range_tab, 2 * kRangeInts * sizeof(int)));
-        std::vector<int> init(kRangeInts, 0);
-        for (int r = 1; r < kRangeLayers; ++r)
-            for (int k = 0; k < (int)W_NSITES; ++k) init[(r * (int)W_NSITES + k) * 2 + 1] = -(r * (int)W_NSITES * 2);
-        AT_CHECK_HIP(hipMemcpy(h->range_tab + kRangeInts, init.data(), kRangeInts * sizeof(int), hipMemcpyHostToDevice));
-        AT_CHECK_HIP(hipMemcpy(h->range_tab, init.data(), kRangeInts * sizeof(int), hipMemcpyHostToDevice));
-    }
-    h->finalized = true;
     return 0;
 }
 
-int at_w2vbert_finalize(at_w2vbert_t* h) {
-    AT_REQUIRE(h && !h->finalized, "bad handle");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    return finalize_impl(h);
-}
+extern "C" {
 
-// ---- the finalized model as one device blob (packed_model.h) ------------------------------------------------------------------------------
-static int packed_flags(const at_w2vbert* h) {
-    int f = (h->codebook ? 1 : 0) | ((int)h->split_seq.size() << 1);
-    for (size_t i = 0; i < h->split_seq.size(); ++i) f |= (h->split_seq[i] == XB_SCHEME_BF16X3 ? 1 : 0) << (3 + i);
-    return f;
+at_w2vbert_t* at_w2vbert_create(int device_id) { return device_exists("at_w2vbert_create", device_id) ? new at_w2vbert(device_id) : nullptr; }
+int at_w2vbert_set_tensor(at_w2vbert_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
+    return stage_tensor(h, name, host_data, shape, ndim);
 }
-int64_t at_w2vbert_packed_bytes(at_w2vbert_t* h) {
-    if (!h || !h->finalized) { set_error("at_w2vbert_packed_bytes: model not finalized"); return -1; }
-    return (int64_t)h->arena.packed_bytes();
-}
-int64_t at_w2vbert_packed_meta(at_w2vbert_t* h, void* host_dst, int64_t cap) {
-    if (!h || !h->finalized) { set_error("at_w2vbert_packed_meta: model not finalized"); return -1; }
-    return packed_write_meta(h->arena, PACKED_MODEL_W2VBERT, (int)h->layers.size(), packed_flags(h), h->arith, host_dst, cap);
-}
+int at_w2vbert_finalize(at_w2vbert_t* h) { return sem_finalize(h); }
+int64_t at_w2vbert_packed_bytes(at_w2vbert_t* h) { return sem_packed_bytes(h, "at_w2vbert_packed_bytes"); }
+int64_t at_w2vbert_packed_meta(at_w2vbert_t* h, void* host_dst, int64_t cap) { return sem_packed_meta(h, "at_w2vbert_packed_meta", host_dst, cap); }
 int at_w2vbert_export_packed(at_w2vbert_t* h, void* device_dst, int64_t bytes, void* stream) {
-    AT_REQUIRE(h && h->finalized, "at_w2vbert_export_packed: model not finalized");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    return packed_export(h->arena, device_dst, bytes, (hipStream_t)stream);
+    return sem_export_packed(h, "at_w2vbert_export_packed", device_dst, bytes, stream);
 }
 int at_w2vbert_import_packed(at_w2vbert_t* h, const void* host_meta, int64_t meta_bytes, const void* device_src, int64_t bytes, void* stream) {
-    AT_REQUIRE(h && !h->finalized && h->staged.empty(), "at_w2vbert_import_packed needs a fresh handle (no set_tensor, no finalize)");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    if (int rc = packed_begin_import(h->arena, PACKED_MODEL_W2VBERT, host_meta, meta_bytes, device_src, bytes, (hipStream_t)stream, &h->imp)) return rc;
-    int rc = finalize_impl(h);
-    if (!rc) rc = packed_end_import(h->arena);
-    if (rc) {
-        // a failed import leaves an EMPTY handle that can only be destroyed (or imported into again): not a half-built model that reports `finalized`
-        h->finalized = false;
-        h->arena.importing = false;
-        h->layers.clear();
-        h->split_seq.clear();
-        h->split_done[0] = h->split_done[1] = false;
-        h->wmax.clear();
-        h->codebook = h->e2 = nullptr;
-        h->cb_s[0] = h->cb_s[1] = nullptr;
-        h->arena.free_all();
-        if (h->range_tab) { (void)hipFree(h->range_tab); h->range_tab = nullptr; }
-    }
-    return rc;
+    return sem_import_packed(h, "at_w2vbert_import_packed", host_meta, meta_bytes, device_src, bytes, stream);
 }
-
-void at_w2vbert_destroy(at_w2vbert_t* h) {
-    if (!h) return;
-    DeviceGuard guard(h->device);   // restores the caller's current device (destroy runs from garbage collection in Python)
-    h->arena.free_all();
-    if (h->range_tab) (void)hipFree(h->range_tab);
-    delete h;
-}
+void at_w2vbert_destroy(at_w2vbert_t* h) { sem_destroy(h); }
 
 int at_w2vbert_num_layers(const at_w2vbert_t* h) { return h ? (int)h->layers.size() : 0; }
 int at_w2vbert_num_tokens(int N, int pad_to_multiple_of) { return tokens_of(N, pad_to_multiple_of); }
@@ -546,77 +367,13 @@ size_t at_w2vbert_workspace_bytes(const at_w2vbert_t* h, int B, int N, int pad_t
     return make_plan(B, N, pad_to_multiple_of).total_floats * sizeof(float);
 }
 
-int at_w2vbert_profile(at_w2vbert_t* h, int enable) {
-    AT_REQUIRE(h != nullptr, "null handle");
-    h->prof.reset();
-    h->prof.enabled = enable != 0;
-    return 0;
-}
-
+int at_w2vbert_profile(at_w2vbert_t* h, int enable) { return profile_enable(h, enable); }
 int at_w2vbert_profile_read(at_w2vbert_t* h, char* names, size_t names_cap, float* total_ms, int* launches, int max_groups) {
-    AT_REQUIRE(h && names && total_ms && launches, "null pointer");
-    std::vector<float> ms;
-    std::vector<int> ln;
-    if (h->prof.read(ms, ln) != 0) { set_error("profile read: event query failed"); return -2; }
-    std::string joined;
-    int n = 0;
-    for (size_t i = 0; i < h->prof.names.size() && n < max_groups; ++i, ++n) {
-        joined += h->prof.names[i];
-        joined += '\n';
-        total_ms[n] = ms[i];
-        launches[n] = ln[i];
-    }
-    AT_REQUIRE(joined.size() + 1 <= names_cap, "names buffer too small");
-    std::memcpy(names, joined.c_str(), joined.size() + 1);
-    return n;
+    return profile_read(h, names, names_cap, total_ms, launches, max_groups);
 }
 
-int at_w2vbert_set_option(at_w2vbert_t* h, const char* name, int value) {
-    AT_REQUIRE(h && h->finalized && name, "bad handle");
-    const std::string n(name);
-    if (n == "arith") {
-        AT_REQUIRE(value == ARITH_F32 || value == ARITH_BF16X3 || value == ARITH_F16X2, "arith: 0 = f32 MFMA, 1 = bf16x3, 2 = f16x2");
-        DeviceGuard guard(h->device);
-        AT_REQUIRE(guard.ok, "cannot select the handle's device");
-        if (value != ARITH_F32)
-            if (int rc = split_weights(h, value == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3)) return rc;
-        h->arith = value;
-        return 0;
-    }
-    if (n.rfind("layer_arith:", 0) == 0) {   // "layer_arith:<i>": -1 = follow "arith", 1 = bf16x3, 2 = f16x2 for conformer layer i only
-        const int li = std::atoi(n.c_str() + 12);
-        AT_REQUIRE(li >= 0 && li < (int)h->layers.size(), "layer_arith: no such layer");
-        AT_REQUIRE(value == -1 || value == ARITH_BF16X3 || value == ARITH_F16X2, "layer_arith:<i>: -1 = the handle's arithmetic, 1 = bf16x3, 2 = f16x2");
-        if (value > 0) {
-            DeviceGuard guard(h->device);
-            AT_REQUIRE(guard.ok, "cannot select the handle's device");
-            if (int rc = split_weights(h, value == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3)) return rc;
-        }
-        if (h->layer_arith.size() < h->layers.size()) h->layer_arith.resize(h->layers.size(), -1);
-        h->layer_arith[li] = value;
-        return 0;
-    }
-    if (n == "dwconv_stream") { h->dwconv_stream = value != 0; return 0; }
-    if (n == "vq_split") { h->vq_split = value != 0; return 0; }
-    if (n == "vq_refine") { h->vq_refine = value != 0; return 0; }
-    if (n == "attn_w8") { h->attn_w8 = value < 0 ? -1 : (value != 0); return 0; }
-    set_error("at_w2vbert_set_option: unknown option " + n);
-    return -1;
-}
-
-int at_w2vbert_get_option(const at_w2vbert_t* h, const char* name) {
-    if (!h || !name) return -1;
-    if (std::string(name) == "arith") return h->arith;
-    if (std::string(name).rfind("layer_arith:", 0) == 0) {
-        const int li = std::atoi(name + 12);
-        return (li >= 0 && li < (int)h->layer_arith.size()) ? h->layer_arith[li] : -1;
-    }
-    if (std::string(name) == "dwconv_stream") return h->dwconv_stream ? 1 : 0;
-    if (std::string(name) == "vq_split") return h->vq_split ? 1 : 0;
-    if (std::string(name) == "vq_refine") return h->vq_refine ? 1 : 0;
-    if (std::string(name) == "attn_w8") return h->attn_w8;
-    return -1;
-}
+int at_w2vbert_set_option(at_w2vbert_t* h, const char* name, int value) { return sem_set_option(h, "at_w2vbert_set_option", name, value); }
+int at_w2vbert_get_option(const at_w2vbert_t* h, const char* name) { return sem_get_option(h, name); }
 
 int at_w2vbert_encode(at_w2vbert_t* h, const float* wav, const float* mask, int B, int N, int pad_to_multiple_of, int n_layers,
                       int16_t* tokens, int* T_out, float* features_out, float* attn_mask_out, float* hidden_out, void* workspace,
@@ -647,11 +404,10 @@ int at_w2vbert_encode_checked(at_w2vbert_t* h, const float* wav, const float* ma
     if (status_dev) AT_CHECK_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
     const bool split = h->arith != ARITH_F32;
     AT_REQUIRE(n_layers <= kRangeLayers, "more conformer layers than range-table rows");
-    AT_CHECK_HIP(hipMemcpyAsync(h->range_tab, h->range_tab + kRangeInts, kRangeInts * sizeof(int), hipMemcpyDeviceToDevice, stream));   // flags 0, census 0 / links
+    if (int rc = h->range.reset(stream)) return rc;
     // arithmetic per layer: the handle's, unless that layer is pinned to another split scheme (option "layer_arith:<i>": what the product's range
     // fallback sets for a layer whose activations do not fit fp16 — the other layers stay on f16x2). Each layer has its own row of the range table.
-    auto arith_of = [&](int li) { return (split && li < (int)h->layer_arith.size() && h->layer_arith[li] > 0) ? h->layer_arith[li] : h->arith; };
-    auto ctx_of = [&](int li) { return SplitCtx{arith_of(li) == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, h->range_tab + li * 2 * (int)W_NSITES, &h->layers[li]}; };
+    auto ctx_of = [&](int li) { return SplitCtx{h->arith_of(li) == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, h->range.layer_row(li), &h->layers[li]}; };
     const SplitCtx sc_model{h->arith == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3, nullptr, nullptr};   // the VQ score GEMM (no range site, non-affine LayerNorm: scale 16)
 
     // ---- log-mel front-end (reference processors.py) -------------------------------------------
@@ -690,7 +446,7 @@ int at_w2vbert_encode_checked(at_w2vbert_t* h, const float* wav, const float* ma
     for (int li = 0; li < n_layers; ++li) {
         const LayerW& L = h->layers[li];
         const SplitCtx sc = ctx_of(li);
-        const int attn_arith = arith_of(li);   // attention follows the layer's arithmetic (0: the fp32-MFMA kernel)
+        const int attn_arith = h->arith_of(li);   // attention follows the layer's arithmetic (0: the fp32-MFMA kernel)
         if (split) {
             // Split arithmetic: every GEMM operand is produced directly as K-blocked pieces — LayerNorm (launch_layernorm_split), the first
             // FFN GEMM's swish epilogue, the attention kernel's context and the depthwise-conv kernel's output — so no fp32 activation is
@@ -793,7 +549,7 @@ int at_w2vbert_encode_checked(at_w2vbert_t* h, const float* wav, const float* ma
         prof.end(stream);
     }
     if (status_dev)   // every site's range verdict of this call -> the caller's status word
-        if (int rc = launch_range_combine(h->range_tab, n_layers * (int)W_NSITES, reinterpret_cast<int*>(status_dev), stream)) return rc;
+        if (int rc = launch_range_combine(h->range.dev, n_layers * (int)W_NSITES, reinterpret_cast<int*>(status_dev), stream)) return rc;
     if (hidden_out) AT_CHECK_HIP(hipMemcpyAsync(hidden_out, x, (size_t)M * kHid * sizeof(float), hipMemcpyDeviceToDevice, stream));
 
     if (tokens) {
@@ -819,39 +575,9 @@ int at_w2vbert_encode_checked(at_w2vbert_t* h, const float* wav, const float* ma
     return 0;
 }
 
-// The measured fp16 headroom of the LAST encode of this handle: per site (at_w2vbert_range_sites) the largest |x * scale| a split writer saw over all
-// layers (0: the site did not run on the fp16 scheme); the scheme overflows at 65504. Synchronises the device.
-int at_w2vbert_range_report(at_w2vbert_t* h, float* max_scaled, int cap) {
-    AT_REQUIRE(h && h->finalized && h->range_tab && max_scaled && cap >= (int)W_NSITES, "at_w2vbert_range_report: bad arguments");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    std::vector<int> host(kRangeInts);
-    AT_CHECK_HIP(hipDeviceSynchronize());
-    AT_CHECK_HIP(hipMemcpy(host.data(), h->range_tab, kRangeInts * sizeof(int), hipMemcpyDeviceToHost));
-    for (int k = 0; k < (int)W_NSITES; ++k) {
-        float f;   // row 0 holds the one census word of the site; the other rows' second words are links to it (split_scheme.h)
-        std::memcpy(&f, &host[k * 2 + 1], sizeof(f));
-        max_scaled[k] = f;
-    }
-    return (int)W_NSITES;
-}
-// Per conformer layer, the OR of its sites' status flags in the LAST encode (bit 1 = an activation of that layer left the fp16 range; an overflow turns
-// into infinities that later layers flag too: the FIRST flagged layer is the cause). Returns the number of layers written. Synchronises the device.
-int at_w2vbert_layer_status(at_w2vbert_t* h, int32_t* flags, int cap) {
-    AT_REQUIRE(h && h->finalized && h->range_tab && flags && cap >= 1, "at_w2vbert_layer_status: bad arguments");
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    std::vector<int> host(kRangeInts);
-    AT_CHECK_HIP(hipDeviceSynchronize());
-    AT_CHECK_HIP(hipMemcpy(host.data(), h->range_tab, kRangeInts * sizeof(int), hipMemcpyDeviceToHost));
-    const int n = std::min<int>({cap, (int)h->layers.size(), kRangeLayers});
-    for (int l = 0; l < n; ++l) {
-        int v = 0;
-        for (int k = 0; k < (int)W_NSITES; ++k) v |= host[(l * (int)W_NSITES + k) * 2];
-        flags[l] = v;
-    }
-    return n;
-}
+int at_w2vbert_range_report(at_w2vbert_t* h, float* max_scaled, int cap) { return sem_range_report(h, "at_w2vbert_range_report", max_scaled, cap); }
+// flags[l] = conformer layer l: `layers` entries
+int at_w2vbert_layer_status(at_w2vbert_t* h, int32_t* flags, int cap) { return sem_layer_status(h, "at_w2vbert_layer_status", flags, cap); }
 // The activation scale of every (layer, site): scales[l * n_sites + k], n_sites = at_w2vbert_range_sites. 16 everywhere unless a LayerNorm's gains force
 // the provable scale of a LayerNorm-fed site below that (xb_ln_site_scale). Returns the number of floats written. Host-only.
 int at_w2vbert_site_scales(const at_w2vbert_t* h, float* scales, int cap) {
@@ -862,13 +588,7 @@ int at_w2vbert_site_scales(const at_w2vbert_t* h, float* scales, int cap) {
         for (int k = 0; k < (int)W_NSITES; ++k) scales[l * W_NSITES + k] = h->layers[l].site_scale[k];
     return n;
 }
-int at_w2vbert_range_sites(char* names, size_t cap) {
-    std::string s;
-    for (int k = 0; k < (int)W_NSITES; ++k) { s += kWSiteNames[k]; s += "\n"; }
-    if (!names || cap < s.size() + 1) return -(int)(s.size() + 1);
-    std::memcpy(names, s.c_str(), s.size() + 1);
-    return (int)W_NSITES;
-}
+int at_w2vbert_range_sites(char* names, size_t cap) { return range_sites(kWSiteNames, (int)W_NSITES, names, cap); }
 
 /* ---- operator-level entry points for the parity tests ---------------------------------------------------- */
 int at_op_layernorm(const float* x, const float* gamma, const float* beta, const float* row_mask, float* y, int64_t rows, int D,

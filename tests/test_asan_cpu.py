@@ -53,6 +53,24 @@ lib.at_w2vbert_destroy(h)
 h = stage(lib.at_hubert_create, lib.at_hubert_set_tensor, fold_hubert_weights(W.synth_hubert_weights(1, 0, True), 1))
 assert lib.at_hubert_finalize(h) != 0
 lib.at_hubert_destroy(h)
+# options of the two semantic handles, which share one implementation: set_option needs a finalized handle (none can exist without a device), get_option reads
+# the defaults of any handle and answers -1 for a name it does not know
+for m, own in (("w2vbert", (b"dwconv_stream", b"vq_split")), ("hubert", (b"posconv_split", b"ln_split", b"kmeans_split"))):
+    create, destroy = getattr(lib, f"at_{m}_create"), getattr(lib, f"at_{m}_destroy")
+    set_option, get_option = getattr(lib, f"at_{m}_set_option"), getattr(lib, f"at_{m}_get_option")
+    h = create(0)
+    assert h
+    for name in (b"arith", b"vq_refine", b"no_such_option", b"layer_arith:0") + own:
+        assert set_option(h, name, 1) == -1 and b"bad handle" in lib.at_last_error()
+        assert set_option(None, name, 1) == -1
+    assert set_option(h, None, 1) == -1
+    assert get_option(h, b"arith") == 2 and get_option(h, b"attn_w8") == -1 and get_option(h, b"vq_refine") == 1
+    assert all(get_option(h, name) == 1 for name in own)
+    assert get_option(h, b"layer_arith:0") == -1 and get_option(h, b"layer_arith:-3") == -1 and get_option(h, b"layer_arith:") == -1
+    other = b"posconv_split" if m == "w2vbert" else b"dwconv_stream"
+    assert get_option(h, b"no_such_option") == -1 and get_option(h, other) == -1 and get_option(h, b"") == -1
+    assert get_option(h, None) == -1 and get_option(None, b"arith") == -1
+    destroy(h)
 print("ASAN_DRIVER_OK")
 '''
 
