@@ -564,8 +564,36 @@ class AudioToken:
                 raise ValueError(f"Tokenizer {self.tokenizer_name} not supported")
             self.decoder.eval()
 
-    def decode(self, tokens: Union[torch.Tensor, np.ndarray, os.PathLike, Path], **kwargs) -> torch.Tensor:
-        """core.py:317-353: tokens ``(B, K, T)`` -> audio ``(1, B*320*T)`` on the CPU."""
+    def decode_stream(self, batch: int = 1, **kwargs):
+        """A streaming acoustic decoder (``AcousticDecodeStream``: ``push`` / ``flush`` / ``reset``) for tokens that arrive frame by frame; the
+        concatenated audio is that of one-shot ``decode``. The semantic tokenizers have no decoder here and no streaming form."""
+        if self.tokenizer_name != Tokenizers.acoustic:
+            raise ValueError(f"streaming decode is available for Tokenizers.acoustic only; {self.tokenizer_name} has no streaming form")
+        self.load_decoder(**kwargs)
+        return self.decoder.new_stream(batch)
+
+    def decode(self, tokens: Union[torch.Tensor, np.ndarray, os.PathLike, Path], chunk_size: Optional[int] = None, stream: bool = False,
+               **kwargs) -> torch.Tensor:
+        """core.py:317-353: tokens ``(B, K, T)`` -> audio ``(1, B*320*T)`` on the CPU.
+        ``stream=True`` with a ``chunk_size`` in seconds (acoustic only, ``B = 1``) pushes ``chunk_size * 75`` frames at a time through ONE stream:
+        the whole clip's ``(1, 320*T)`` in the memory of one chunk."""
+        if stream:
+            if chunk_size is None:
+                raise ValueError("stream=True needs a chunk_size (seconds of audio per push)")
+            st = self.decode_stream(1, **kwargs)
+            if isinstance(tokens, np.ndarray):
+                tokens = torch.from_numpy(tokens)
+            elif isinstance(tokens, (os.PathLike, Path)):
+                tokens = torch.load(tokens, map_location="cpu")
+            if not isinstance(tokens, torch.Tensor):
+                raise ValueError(f"Unsupported input type {type(tokens)}. Should be one of: {np.ndarray, os.PathLike, Path}")
+            if tokens.dim() == 2:   # (K, sum T), what encode(path, chunk_size) returns
+                tokens = tokens.unsqueeze(0)
+            assert tokens.dim() == 3 and tokens.shape[0] == 1, "streamed decode takes one clip: tokens (1, K, T) or (K, T)"
+            step = max(1, int(round(chunk_size * self.model_config.model_token_rate)))
+            parts = [st.push(tokens[:, :, t0:t0 + step]).cpu() for t0 in range(0, tokens.shape[-1], step)]
+            parts.append(st.flush().cpu())
+            return torch.cat(parts, dim=-1)
         self.load_decoder(**kwargs)
         if isinstance(tokens, np.ndarray):
             return self._decode_single(torch.from_numpy(tokens))

@@ -186,11 +186,12 @@ struct at_encodec {
     std::vector<void*> extra_allocs;
     int* range_tab = nullptr;   // device, {flag, census} per AcSite, zeroed at the start of every encode / decode (at_encodec_range_report reads it)
     int sub_batch = at::sub_batch();   // clips per pass through the conv stack: bounds the workspace (option "subbatch")
+    bool dec_skip_twin = false;     // option "dec_skip_twin": one-shot decode and a stream's first push store through the skip / stride tail variants with skip = 0 and a dense stride (the A/B twin of the tests)
     bool persistent_lstm = false;   // whole-sequence persistent LSTM (needs one resident workgroup per CU for 256 CUs)
     unsigned lstm_spin_limit = 1u << 18;   // option "lstm_spin_limit": flag polls before a persistent-LSTM workgroup gives up
     // streaming encode: what the host knows about every state buffer it has reset or written (the state itself is device memory; this is
     // what lets a push be refused without a device synchronisation)
-    struct StreamInfo { int B = 0; bool started = false, finished = false; };
+    struct StreamInfo { int B = 0; bool started = false, finished = false, decode = false; };   // decode: a state of at_encodec_decode_stream_*
     std::map<const void*, StreamInfo> streams;
 };
 
@@ -623,6 +624,44 @@ DecPlan make_dec_plan(int B, int T, int sub) {
     p.off_dat3 = take((size_t)p.G * p.dMpc * 384 + 64);
     p.total_floats = cur;
     return p;
+}
+
+// Streaming decode (at_encodec_decode_stream_checked). State of B streams, floats: the last kDecHist rows of the quantised embedding z [B][6][128]
+// (the history of the k = 7 first conv), h and c of the two LSTM layers [4][B][512] (h0, c0, h1, c1), the last kDecCtx rows of ELU(lstm + skip)
+// [B][2][512]. An output sample n reaches back to row floor(n / 320) - 2 of that tensor (final conv 6 samples, per stage the block's k3 conv 2 rows
+// and the transposed conv 1 input row), so the upsampling stack runs on [2 carried rows | new rows] and its first 640 samples are never stored.
+constexpr int kDecHist = 6, kDecCtx = 2, kDecFirstFrames = 7;
+struct DecStreamState {
+    float *zhist, *h[2], *c[2], *yctx;
+    DecStreamState(void* base, int B) {
+        zhist = yctx = h[0] = h[1] = c[0] = c[1] = nullptr;
+        if (!base) return;
+        float* f = (float*)base;
+        zhist = f; f += (size_t)B * kDecHist * kDim;
+        for (int l = 0; l < 2; ++l) { h[l] = f; f += (size_t)B * kH; c[l] = f; f += (size_t)B * kH; }
+        yctx = f;
+    }
+    static size_t floats(int B) { return (size_t)B * (kDecHist * kDim + 4 * kH + kDecCtx * kH); }
+};
+struct DecStreamCall { const void* state_in; void* state_out; bool started; };
+// The one-shot plan of the window (Tw = new + context rows; the LSTM buffers hold the new rows only) and, behind it, the two windows the state
+// kernel writes: z [B][Tz][128] and ELU(lstm + skip) [B][Tw][512].
+struct DecStreamPlan {
+    DecPlan p;
+    int Tz = 0, Tw = 0;
+    size_t off_zw = 0, off_yw = 0, total_floats = 0;
+};
+DecStreamPlan make_dec_stream_plan(int B, int t_new, bool started, int sub) {
+    DecStreamPlan sp;
+    sp.Tz = t_new + (started ? kDecHist : 0);
+    sp.Tw = t_new + (started ? kDecCtx : 0);
+    sp.p = make_dec_plan(B, sp.Tw, sub);
+    size_t cur = sp.p.total_floats;
+    auto take = [&](size_t n) { size_t o = cur; cur += (n + 63) / 64 * 64; return o; };
+    sp.off_zw = take((size_t)B * sp.Tz * kDim);
+    sp.off_yw = take((size_t)B * sp.Tw * kH);
+    sp.total_floats = cur;
+    return sp;
 }
 
 }  // namespace
@@ -1261,6 +1300,7 @@ int at_encodec_encode_stream_checked(at_encodec_t* h, const void* state_in, void
     const auto it = h->streams.find(state_in);
     AT_REQUIRE(it != h->streams.end(), "at_encodec_encode_stream_checked: state_in was neither reset (at_encodec_stream_reset) nor written by a push of this handle");
     const at_encodec::StreamInfo in = it->second;
+    AT_REQUIRE(!in.decode, "at_encodec_encode_stream_checked: state_in is a decode stream's state (at_encodec_decode_stream_reset)");
     AT_REQUIRE(in.B == B, "at_encodec_encode_stream_checked: the state was reset for another B");
     AT_REQUIRE(!in.finished, "at_encodec_encode_stream_checked: push after the final push (reset the stream first)");
     AT_REQUIRE(final || (n_new > 0 && n_new % kHop == 0), "at_encodec_encode_stream_checked: n_new must be a positive multiple of 320 unless final");
@@ -1285,6 +1325,7 @@ int at_encodec_encode_stream_checked(at_encodec_t* h, const void* state_in, void
 namespace {
 struct BoolOption { const char* name; bool at_encodec::*member; };
 const BoolOption kBoolOptions[] = {
+    {"dec_skip_twin", &at_encodec::dec_skip_twin},
     {"persistent_lstm", &at_encodec::persistent_lstm},
     {"fused_stage0", &at_encodec::fused_stage0},
     {"fused_res64", &at_encodec::fused_res64},
@@ -1371,41 +1412,85 @@ int at_encodec_decode(at_encodec_t* h, const int64_t* codes, int B, int K, int T
     return at_encodec_decode_checked(h, codes, B, K, T, wav, workspace, workspace_bytes, stream_, nullptr);
 }
 
-int at_encodec_decode_checked(at_encodec_t* h, const int64_t* codes, int B, int K, int T, float* wav, void* workspace,
-                              size_t workspace_bytes, at_stream_t stream_, uint32_t* status_dev) {
+// One-shot decode (sc == nullptr) or one push of a stream: T new frames. A push differs in three places: the state kernel gathers z behind the carried
+// history (and the first conv then needs no padding), the LSTM starts from the carried (h, c), and the upsampling stack runs on Tw = T + 2 rows with
+// the tail kernels' skip / stride variant dropping the first 640 samples. Everything else is the one-shot code on the window.
+static int encodec_decode_impl(at_encodec_t* h, const int64_t* codes, int B, int K, int T, float* wav, void* workspace,
+                               size_t workspace_bytes, at_stream_t stream_, uint32_t* status_dev, const DecStreamCall* sc) {
     AT_REQUIRE(h && h->finalized && h->has_decoder, "model not finalized with a decoder");
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
     AT_REQUIRE(codes && wav && workspace, "null pointer");
-    AT_REQUIRE(B >= 1 && T >= 7 && K >= 1 && K <= h->n_codebooks, "bad B/T/K");
+    const bool mid = sc && sc->started;
+    AT_REQUIRE(B >= 1 && T >= (mid ? 1 : kDecFirstFrames) && K >= 1 && K <= h->n_codebooks, "bad B/T/K");
     hipStream_t stream = (hipStream_t)stream_;
-    const DecPlan p = make_dec_plan(B, T, h->sub_batch);
-    AT_REQUIRE(workspace_bytes >= p.total_floats * sizeof(float), "workspace too small");
+    const DecStreamPlan sp = sc ? make_dec_stream_plan(B, T, mid, h->sub_batch) : DecStreamPlan();
+    const DecPlan p = sc ? sp.p : make_dec_plan(B, T, h->sub_batch);
+    AT_REQUIRE(workspace_bytes >= (sc ? sp.total_floats : p.total_floats) * sizeof(float), "workspace too small");
     float* ws = (float*)workspace;
-    float* z = ws + p.off_z;
+    const int Tw = sc ? sp.Tw : T;   // rows through the upsampling stack
+    const DecStreamState sin(sc ? const_cast<void*>(sc->state_in) : nullptr, B), sout(sc ? sc->state_out : nullptr, B);
     Profiler& prof = h->prof;   // same HIP-event taps as the encoder (at_encodec_profile / at_encodec_profile_read)
     prof.begin("dec_rvq_conv0", 2, stream);
-    if (int rc = launch_rvq_decode(codes, B, K, T, h->codebooks, z, stream)) return rc;
     float* x0 = ws + p.off_x0;
-    if (int rc = conv_gemm(h->dconv0, z, (long long)T * kDim, T, x0, (long long)T * kH, T, B, PRO_NONE, nullptr, 0, stream)) return rc;
+    if (sc) {
+        float* zw = ws + sp.off_zw;
+        StreamDecStateArgs ga;
+        ga.hist_in = mid ? sin.zhist : nullptr; ga.hist = mid ? kDecHist : 0;
+        ga.codes = codes; ga.K = K; ga.codebooks = h->codebooks; ga.Tn = T; ga.C = kDim; ga.B = B;
+        ga.win = zw; ga.hist_out = sout.zhist; ga.keep = kDecHist;
+        if (int rc = launch_stream_dec_state(ga, stream)) return rc;
+        if (mid) {   // the carried rows are the left context: output row m reads window rows m .. m + 6, no padding
+            GemmArgs a;
+            a.X = zw; a.x_bstride = (long long)sp.Tz * kDim; a.Tin = sp.Tz; a.Cin = kDim; a.ldx = kDim;
+            a.ktaps = h->dconv0.k; a.stride = 1; a.pad_left = 0; a.pad_mode = 1;
+            a.W = h->dconv0.w; a.bias = h->dconv0.b;
+            a.C = x0; a.c_bstride = (long long)T * kH; a.ldc = kH;
+            a.M = T; a.N = kH; a.K = h->dconv0.k * kDim; a.batch = B; a.pro = PRO_NONE; a.epi = EPI_NONE; a.alpha = 1.0f;
+            if (int rc = launch_gemm(a, stream)) return rc;
+        } else if (int rc = conv_gemm(h->dconv0, zw, (long long)T * kDim, T, x0, (long long)T * kH, T, B, PRO_NONE, nullptr, 0, stream)) {
+            return rc;
+        }
+    } else {
+        float* z = ws + p.off_z;
+        if (int rc = launch_rvq_decode(codes, B, K, T, h->codebooks, z, stream)) return rc;
+        if (int rc = conv_gemm(h->dconv0, z, (long long)T * kDim, T, x0, (long long)T * kH, T, B, PRO_NONE, nullptr, 0, stream)) return rc;
+    }
     prof.end(stream);
     float* y = ws + p.off_y;
     unsigned* sync = reinterpret_cast<unsigned*>(ws + p.off_sync);
     AT_CHECK_HIP(hipMemsetAsync(sync, 0, 1024 * sizeof(unsigned), stream));
     AT_CHECK_HIP(hipMemsetAsync(h->range_tab, 0, 64 * sizeof(int), stream));
+    LstmCarry carry;
+    if (sc)
+        for (int l = 0; l < 2; ++l) { carry.h_init[l] = sin.h[l]; carry.c_init[l] = sin.c[l]; carry.c_final[l] = sout.c[l]; }
     // every activation that is only consumed through ELU is stored already ELU'd (once per element, in the producer's
     // epilogue) so the transposed convs run the plain-linear GEMM path: y (LSTM + skip) and the block outputs of stages 0-2
     if (int rc = lstm_skip(h->dwih, h->dwhh, h->dbih, h->dbhh, x0, ws + p.off_xg, ws + p.off_h0, ws + p.off_h1, ws + p.off_c, y, B, T, stream, prof,
                            sync, h->persistent_lstm, 1, h->bf16x3 ? h->dwih_s : nullptr, reinterpret_cast<__bf16*>(ws + p.off_xs), h->bf16x3 && h->lstm_x3, h->lstm_spin_limit,
                            (h->bf16x3 && h->ih_f16x2) ? h->dwih_f : nullptr, h->dwih_fs, h->range_tab + 2 * AS_DEC_LSTM_IH, h->lstm_f16x2 ? h->dwhh_fs : nullptr,
-                           (h->lstm_pipe && B <= kPipeMaxClips) ? ws + p.off_xg2 : nullptr))
+                           (h->lstm_pipe && B <= kPipeMaxClips) ? ws + p.off_xg2 : nullptr, sc ? &carry : nullptr))
         return rc;
-    const int Lout = p.L[4];
+    if (sc) {   // [carried rows | new rows] of ELU(lstm + skip), the next push's two rows and the last h of both layers (c: written by the LSTM)
+        StreamDecStateArgs ya;
+        ya.hist_in = mid ? sin.yctx : nullptr; ya.hist = mid ? kDecCtx : 0;
+        ya.src = y; ya.Tn = T; ya.C = kH; ya.B = B;
+        ya.win = mid ? ws + sp.off_yw : nullptr; ya.hist_out = sout.yctx; ya.keep = kDecCtx;
+        ya.h_src[0] = ws + p.off_h0; ya.h_src[1] = ws + p.off_h1; ya.h_out[0] = sout.h[0]; ya.h_out[1] = sout.h[1];
+        prof.begin("stream_state", 1, stream);
+        if (int rc = launch_stream_dec_state(ya, stream)) return rc;
+        prof.end(stream);
+        if (mid) y = ws + sp.off_yw;
+    }
+    const int Lout = p.L[4];   // samples per clip the stack computes; a mid-stream push stores all but the first kDecCtx * 320 of them
+    const int skip = mid ? kDecCtx * kHop : 0;
+    const long long ostride = (long long)Lout - skip;
+    const bool skip_variant = mid || h->dec_skip_twin;
     static const char* kUp[4] = {"dec_up0", "dec_up1", "dec_up2", "dec_up3"};
     static const char* kDRes[4] = {"dec_res0", "dec_res1", "dec_res2", "dec_res3"};
     for (int b0 = 0; b0 < B; b0 += p.G) {
         const int g = (B - b0) < p.G ? (B - b0) : p.G;
-        const float* in = y + (long long)b0 * T * kH;
+        const float* in = y + (long long)b0 * Tw * kH;
         int Cin = kH;
         bool tail_done = false;
         bool ap_ready = false;   // the next stage's transposed-conv operand already lies in `ap` as pieces
@@ -1413,7 +1498,7 @@ int at_encodec_decode_checked(at_encodec_t* h, const int64_t* codes, int B, int 
             const int Li = p.L[s], Lo = p.L[s + 1], Co = Cin / 2;
             if (s == 3 && h->fused_dectail && Li >= 8) {
                 DecTailArgs da;
-                da.x = in; da.out = wav + (long long)b0 * Lout;
+                da.x = in; da.out = wav + (long long)b0 * ostride;
                 da.wu = h->dup[3].w; da.bu = h->dup[3].b; da.w3 = h->dres[3][0].w; da.b3 = h->dres[3][0].b;
                 da.wt = h->dres[3][1].w; da.bt = h->dres[3][1].b; da.wl = h->dlast.w; da.bl = h->dlast.b;
                 da.B = g; da.L = Li;
@@ -1421,8 +1506,8 @@ int at_encodec_decode_checked(at_encodec_t* h, const int64_t* codes, int B, int 
                 if (h->tail_f16x2 && h->bf16x3 && h->dtail_up_fs > 0.f && h->dres_fs[3][0] > 0.f) {
                     da.act_scale = XB_F16_ACT_SCALE; da.wu_scale = h->dtail_up_fs; da.w3_scale = h->dres_fs[3][0]; da.wt_scale = h->dres_fs[3][1];
                     da.status = h->range_tab + 2 * AS_DEC_RES;
-                    if (int rc = launch_seanet_dectail_x2(da, stream)) return rc;
-                } else if (int rc = launch_seanet_dectail(da, stream)) {
+                    if (int rc = skip_variant ? launch_seanet_dectail_x2_skip(da, skip, ostride, stream) : launch_seanet_dectail_x2(da, stream)) return rc;
+                } else if (int rc = skip_variant ? launch_seanet_dectail_skip(da, skip, ostride, stream) : launch_seanet_dectail(da, stream)) {
                     return rc;
                 }
                 prof.end(stream);
@@ -1501,11 +1586,62 @@ int at_encodec_decode_checked(at_encodec_t* h, const int64_t* codes, int B, int 
         }
         if (!tail_done) {
             prof.begin("dec_tail", 1, stream);
-            if (int rc = launch_conv_last(in, h->dlast.w, h->dlast.b, wav + (long long)b0 * Lout, g, Lout, stream)) return rc;
+            if (int rc = skip_variant ? launch_conv_last_skip(in, h->dlast.w, h->dlast.b, wav + (long long)b0 * ostride, g, Lout, skip, ostride, stream)
+                                      : launch_conv_last(in, h->dlast.w, h->dlast.b, wav + (long long)b0 * Lout, g, Lout, stream)) return rc;
             prof.end(stream);
         }
     }
     if (status_dev) return launch_status_combine(sync, h->range_tab, status_dev, stream);   // LSTM hand-off + every range verdict of the call
+    return 0;
+}
+
+int at_encodec_decode_checked(at_encodec_t* h, const int64_t* codes, int B, int K, int T, float* wav, void* workspace,
+                              size_t workspace_bytes, at_stream_t stream_, uint32_t* status_dev) {
+    return encodec_decode_impl(h, codes, B, K, T, wav, workspace, workspace_bytes, stream_, status_dev, nullptr);
+}
+
+size_t at_encodec_decode_stream_state_bytes(const at_encodec_t* h, int B) {
+    (void)h;
+    return B >= 1 ? DecStreamState::floats(B) * sizeof(float) : 0;
+}
+
+int at_encodec_decode_stream_reset(at_encodec_t* h, void* state_dev, int B, at_stream_t stream) {
+    AT_REQUIRE(h && h->finalized && h->has_decoder, "model not finalized with a decoder");
+    AT_REQUIRE(state_dev && B >= 1, "at_encodec_decode_stream_reset: null state or B < 1");
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    AT_CHECK_HIP(hipMemsetAsync(state_dev, 0, DecStreamState::floats(B) * sizeof(float), (hipStream_t)stream));   // h = c = 0
+    at_encodec::StreamInfo info;
+    info.B = B;
+    info.decode = true;
+    h->streams[state_dev] = info;
+    return 0;
+}
+
+size_t at_encodec_decode_stream_workspace_bytes(const at_encodec_t* h, int B, int t_new) {
+    if (B <= 0 || t_new <= 0) return 0;
+    const int sub = h ? h->sub_batch : sub_batch();
+    const size_t a = make_dec_stream_plan(B, t_new, true, sub).total_floats, b = make_dec_stream_plan(B, t_new, false, sub).total_floats;
+    return (a > b ? a : b) * sizeof(float);
+}
+
+int at_encodec_decode_stream_checked(at_encodec_t* h, const void* state_in, void* state_out, const int64_t* codes_new, int B, int K, int t_new,
+                                     float* wav_out, void* workspace, size_t workspace_bytes, at_stream_t stream, uint32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized && h->has_decoder, "model not finalized with a decoder");
+    AT_REQUIRE(state_in && state_out, "at_encodec_decode_stream_checked: null state");
+    AT_REQUIRE(state_in != state_out, "at_encodec_decode_stream_checked: state_in and state_out must be two buffers (a failed push is repeated from state_in)");
+    AT_REQUIRE(B >= 1 && t_new >= 1, "at_encodec_decode_stream_checked: need B >= 1 and t_new >= 1");
+    const auto it = h->streams.find(state_in);
+    AT_REQUIRE(it != h->streams.end(), "at_encodec_decode_stream_checked: state_in was neither reset (at_encodec_decode_stream_reset) nor written by a push of this handle");
+    const at_encodec::StreamInfo in = it->second;
+    AT_REQUIRE(in.decode, "at_encodec_decode_stream_checked: state_in is an encode stream's state (at_encodec_stream_reset)");
+    AT_REQUIRE(in.B == B, "at_encodec_decode_stream_checked: the state was reset for another B");
+    AT_REQUIRE(in.started || t_new >= kDecFirstFrames, "at_encodec_decode_stream_checked: the first push of a stream needs at least 7 frames");
+    const DecStreamCall sc{state_in, state_out, in.started};
+    if (int rc = encodec_decode_impl(h, codes_new, B, K, t_new, wav_out, workspace, workspace_bytes, stream, status_dev, &sc)) return rc;
+    at_encodec::StreamInfo out = in;
+    out.started = true;
+    h->streams[state_out] = out;
     return 0;
 }
 

@@ -1,5 +1,6 @@
 // Launchers of the EnCodec-specific kernels (encodec_kernels.hip).
 #pragma once
+#include <type_traits>
 #include "at_common.h"
 
 namespace at {
@@ -169,6 +170,15 @@ struct DecTailArgs {
     float act_scale = 0.f, wu_scale = 0.f, w3_scale = 0.f, wt_scale = 0.f;
     int* status = nullptr;
 };
+// kernel argument of the skip / stride variant (launch_seanet_dectail_skip, launch_seanet_dectail_x2_skip); the stateless kernels keep DecTailArgs
+struct DecTailSkipArgs : DecTailArgs {
+    int skip = 0;
+    long long out_stride = 0;
+};
+template <bool SKIP> using DecTailKernelArgs = typename std::conditional<SKIP, DecTailSkipArgs, DecTailArgs>::type;
+template <bool SKIP, class A> __host__ __device__ inline int dectail_skip(const A& a) {
+    if constexpr (SKIP) return a.skip; else return 0;
+}
 // decoder stage 0 on the split GEMMs (seanet_dec256.hip): u fp32 [g][L][256] -> ELU(u) pieces with two reflected front rows (the k3 conv's operand) and
 // raw u pieces in K-blocks 8..23 of the tail's operand; rows past the data zero-filled
 int launch_dec_res256_split(const float* u, int g, int L, __bf16* ac3, int Lpc, __bf16* at3, int Mpc, float scale, int* status, hipStream_t stream);
@@ -176,6 +186,10 @@ int launch_zero_piece_rows(__bf16* S, long long planes, int Lp, int row0, int ro
 int launch_seanet_dectail(const DecTailArgs& a, hipStream_t stream);
 // the same kernel with its three contractions as two-piece fp16 operand splits (seanet_dectail_x2.hip); the last conv stays fp32 on the VALU
 int launch_seanet_dectail_x2(const DecTailArgs& a, hipStream_t stream);
+// both kernels for a streaming-decode window (compile-time variants; the stateless instances above are unchanged): the first `skip` output samples of
+// each clip are neither computed past the tile that straddles `skip` nor written, and clip b's sample skip + i goes to out[b * out_stride + i]
+int launch_seanet_dectail_skip(const DecTailArgs& a, int skip, long long out_stride, hipStream_t stream);
+int launch_seanet_dectail_x2_skip(const DecTailArgs& a, int skip, long long out_stride, hipStream_t stream);
 // Same block at 128 channels (seanet_res128.hip): x [B][L][128] -> out [B][L][128]; w3 [64][3*128], wt [128][64 + 128]
 int launch_seanet_res128(const Res64Args& a, hipStream_t stream);
 
@@ -191,5 +205,22 @@ int launch_rvq_encode(const float* x, long long rows, int T, const float* codebo
                       int16_t* codes, hipStream_t stream);
 int launch_rvq_decode(const int64_t* codes, int B, int K, int T, const float* codebooks, float* z, hipStream_t stream);
 int launch_conv_last(const float* x, const float* w, const float* bias, float* out, int B, int L, hipStream_t stream);
+// the same conv for a streaming-decode window: the first `skip` samples of each clip are not written, clip b starts at out + b * out_stride
+int launch_conv_last_skip(const float* x, const float* w, const float* bias, float* out, int B, int L, int skip, long long out_stride, hipStream_t stream);
+
+// Streaming decode, state gather / scatter in one kernel (encodec_kernels.hip): per clip the rows [hist_in | new] -> win (optional) and their last
+// `keep` rows -> hist_out; the new rows come from src [B][Tn][C] or are summed from the code books for codes [B][K][Tn] (C = 128, the arithmetic
+// of launch_rvq_decode). With h_src the last row of the two LSTM outputs [B][Tn][512] goes to h_out [B][512].
+struct StreamDecStateArgs {
+    const float* hist_in = nullptr; int hist = 0;
+    const float* src = nullptr;
+    const int64_t* codes = nullptr; int K = 0; const float* codebooks = nullptr;
+    int Tn = 0, C = 0, B = 0;
+    float* win = nullptr;
+    float* hist_out = nullptr; int keep = 0;
+    const float* h_src[2] = {nullptr, nullptr};
+    float* h_out[2] = {nullptr, nullptr};
+};
+int launch_stream_dec_state(const StreamDecStateArgs& a, hipStream_t stream);
 
 }  // namespace at

@@ -331,8 +331,11 @@ int launch_rvq_decode(const int64_t* codes, int B, int K, int T, const float* co
 // Last decoder conv: ELU -> conv k7 32 -> 1 (causal reflect). [B][L][32] -> [B][L]. HBM-bound, 128 B in / 4 B out.
 // 8 lanes per output sample (4 channels each: one coalesced 128-B row per tap), 3-step shuffle reduction.
 // ------------------------------------------------------------------------------------------------------
+// SKIP (streaming decode, Extra = int skip, long long out_stride): the first `skip` samples of each clip are never written and clip b starts at
+// out + b * out_stride. The stateless instance has no extra arguments and compiles to the code it had before the variant.
+template <bool SKIP, class... Extra>
 __global__ __launch_bounds__(256) void conv_last_kernel(const float* __restrict__ x, const float* __restrict__ w /*[7][32]*/,
-                                                        const float* __restrict__ bias, float* __restrict__ out, int L, long long total) {
+                                                        const float* __restrict__ bias, float* __restrict__ out, int L, long long total, Extra... extra) {
     __shared__ f4 wsm[7 * 8];
     if (threadIdx.x < 56) wsm[threadIdx.x] = reinterpret_cast<const f4*>(w)[threadIdx.x];
     __syncthreads();
@@ -356,13 +359,82 @@ __global__ __launch_bounds__(256) void conv_last_kernel(const float* __restrict_
     acc += __shfl_xor(acc, 1);
     acc += __shfl_xor(acc, 2);
     acc += __shfl_xor(acc, 4);
-    if (live && cg == 0) out[bt] = acc + bias[0];
+    if constexpr (SKIP) {
+        [&](int skip, long long out_stride) {
+            if (live && cg == 0 && t >= skip) out[(bt - t) / L * out_stride + (t - skip)] = acc + bias[0];
+        }(extra...);
+    } else {
+        if (live && cg == 0) out[bt] = acc + bias[0];
+    }
 }
 
 int launch_conv_last(const float* x, const float* w, const float* bias, float* out, int B, int L, hipStream_t stream) {
     const long long total = (long long)B * L;
     const long long blocks = (total * 8 + 255) / 256;
-    hipLaunchKernelGGL(conv_last_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, w, bias, out, L, total);
+    hipLaunchKernelGGL((conv_last_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, bias, out, L, total);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_conv_last_skip(const float* x, const float* w, const float* bias, float* out, int B, int L, int skip, long long out_stride, hipStream_t stream) {
+    AT_REQUIRE(skip >= 0 && skip < L && out_stride >= L - skip, "conv_last: bad skip / stride");
+    const long long total = (long long)B * L;
+    const long long blocks = (total * 8 + 255) / 256;
+    hipLaunchKernelGGL((conv_last_kernel<true, int, long long>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, bias, out, L, total, skip, out_stride);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Streaming decode, the state kernel: per clip the virtual rows v = [hist_in (hist rows) | new (Tn rows)] of width C. The new rows are read from
+// `src`, or, when `codes` is given (C = 128), summed from the code books in the order of rvq_decode_kernel (bit-identical z). `win` (optional)
+// receives all rows, `hist_out` the last `keep` of them; with h_src the last row of both LSTM layers' outputs goes to h_out. One thread = one
+// float4 of one row; every store is a float4 vector store.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void stream_dec_state_kernel(StreamDecStateArgs a, long long n_rows4, long long total4) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    if (i >= n_rows4) {   // last h of layer l, clip b: [B][Tn][512] row Tn - 1 -> [B][512]
+        const long long e = i - n_rows4;
+        const int c4 = (int)(e & 127);
+        const long long lb = e >> 7;
+        const int l = (int)(lb / a.B), b = (int)(lb - (long long)l * a.B);
+        *reinterpret_cast<f4*>(a.h_out[l] + (long long)b * 512 + c4 * 4) =
+            *reinterpret_cast<const f4*>(a.h_src[l] + ((long long)b * a.Tn + (a.Tn - 1)) * 512 + c4 * 4);
+        return;
+    }
+    const int C4 = a.C >> 2, rows = a.hist + a.Tn;
+    const int c4 = (int)(i % C4);
+    const long long bv = i / C4;
+    const int b = (int)(bv / rows), v = (int)(bv - (long long)b * rows);
+    f4 val;
+    if (v < a.hist) {
+        val = *reinterpret_cast<const f4*>(a.hist_in + ((long long)b * a.hist + v) * a.C + c4 * 4);
+    } else if (a.codes) {
+        const int t = v - a.hist;
+        val = f4{0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < a.K; ++k) {
+            long long idx = a.codes[((long long)b * a.K + k) * a.Tn + t];
+            idx = idx < 0 ? 0 : (idx >= RVQ_CODES ? RVQ_CODES - 1 : idx);
+            val += *reinterpret_cast<const f4*>(a.codebooks + ((long long)k * RVQ_CODES + idx) * RVQ_D + c4 * 4);
+        }
+    } else {
+        val = *reinterpret_cast<const f4*>(a.src + ((long long)b * a.Tn + (v - a.hist)) * a.C + c4 * 4);
+    }
+    if (a.win) *reinterpret_cast<f4*>(a.win + ((long long)b * rows + v) * a.C + c4 * 4) = val;
+    const int k = v - (rows - a.keep);
+    if (a.hist_out && k >= 0) *reinterpret_cast<f4*>(a.hist_out + ((long long)b * a.keep + k) * a.C + c4 * 4) = val;
+}
+
+int launch_stream_dec_state(const StreamDecStateArgs& a, hipStream_t stream) {
+    AT_REQUIRE(a.B >= 1 && a.Tn >= 1 && a.hist >= 0 && a.C >= 4 && a.C % 4 == 0 && (a.hist == 0 || a.hist_in), "stream_dec_state: bad arguments");
+    AT_REQUIRE((a.codes != nullptr) != (a.src != nullptr), "stream_dec_state: new rows come from codes or from src");
+    AT_REQUIRE(!a.codes || (a.C == RVQ_D && a.K >= 1 && a.codebooks), "stream_dec_state: the gather needs K >= 1 code books of width 128");
+    AT_REQUIRE(!a.hist_out || (a.keep >= 1 && a.hist + a.Tn >= a.keep), "stream_dec_state: fewer rows than the next history holds");
+    AT_REQUIRE((a.h_src[0] != nullptr) == (a.h_out[0] != nullptr) && (a.h_src[1] != nullptr) == (a.h_out[1] != nullptr) &&
+               (a.h_src[0] != nullptr) == (a.h_src[1] != nullptr), "stream_dec_state: h_src / h_out come as two pairs or not at all");
+    const long long n_rows4 = (long long)a.B * (a.hist + a.Tn) * (a.C / 4), total4 = n_rows4 + (a.h_src[0] ? (long long)2 * a.B * 128 : 0);
+    hipLaunchKernelGGL(stream_dec_state_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, a, n_rows4, total4);
     AT_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -27,7 +27,10 @@ constexpr int DT_LDS_FLOATS = DT_XR_FLOATS + DT_ROWS * DT_LDU + (DT_ROWS + 2) * 
 constexpr int DT_CHUNKS = DT_XROWS * 16;
 constexpr int DT_PRE = (DT_CHUNKS + 255) / 256;
 
-__global__ __launch_bounds__(256, 2) void seanet_dectail_kernel(DecTailArgs a) {
+// SKIP (streaming decode): the tiles in front of the one that holds sample `skip` are not computed, samples below `skip` are not stored, and clip b is
+// written from out + b * out_stride (DecTailSkipArgs). The stateless instance (SKIP = false) takes the plain DecTailArgs and compiles to the code it had before the variant.
+template <bool SKIP>
+__global__ __launch_bounds__(256, 2) void seanet_dectail_kernel(DecTailKernelArgs<SKIP> a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Xs = smem;                                   // x rows; re-used for ELU(r) once the transposed conv is done
     float* Re = smem;
@@ -39,7 +42,8 @@ __global__ __launch_bounds__(256, 2) void seanet_dectail_kernel(DecTailArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, q = lane >> 4;
     const int L = a.L, Lout = 2 * L;
-    const int tiles_per_clip = (Lout + DT_TO - 1) / DT_TO;
+    const int tile0 = dectail_skip<SKIP>(a) / DT_TO;   // first tile of a clip that holds a stored sample
+    const int tiles_per_clip = (Lout + DT_TO - 1) / DT_TO - tile0;
     const long long total_tiles = (long long)a.B * tiles_per_clip;
 
     // ---- weights -> registers / LDS, once per workgroup ------------------------------------------------------------------
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void seanet_dectail_kernel(DecTailArgs a) {
     f4 pre[DT_PRE];
     auto prefetch = [&](long long tile) {
         const long long b = tile / tiles_per_clip;
-        const int t0 = (int)(tile - b * tiles_per_clip) * DT_TO;
+        const int t0 = ((int)(tile - b * tiles_per_clip) + tile0) * DT_TO;
         const float* xb = a.x + b * (long long)L * 64;
 #pragma unroll
         for (int j = 0; j < DT_PRE; ++j) {
@@ -78,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void seanet_dectail_kernel(DecTailArgs a) {
 
     for (long long tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
         const long long b = tile / tiles_per_clip;
-        const int t0 = (int)(tile - b * tiles_per_clip) * DT_TO;
+        const int t0 = ((int)(tile - b * tiles_per_clip) + tile0) * DT_TO;
         __syncthreads();   // previous tile's readers are done with every buffer
 #pragma unroll
         for (int j = 0; j < DT_PRE; ++j) {
@@ -208,7 +212,11 @@ __global__ __launch_bounds__(256, 2) void seanet_dectail_kernel(DecTailArgs a) {
                 acc += __shfl_xor(acc, 2);
                 acc += __shfl_xor(acc, 4);
                 const int tout = t0 + o;
-                if (cg == 0 && o < DT_TO && tout < Lout) a.out[b * (long long)Lout + tout] = acc + bl;
+                if constexpr (SKIP) {
+                    if (cg == 0 && o < DT_TO && tout < Lout && tout >= a.skip) a.out[b * a.out_stride + (tout - a.skip)] = acc + bl;
+                } else {
+                    if (cg == 0 && o < DT_TO && tout < Lout) a.out[b * (long long)Lout + tout] = acc + bl;
+                }
             }
         }
     }
@@ -217,10 +225,25 @@ __global__ __launch_bounds__(256, 2) void seanet_dectail_kernel(DecTailArgs a) {
 int launch_seanet_dectail(const DecTailArgs& a, hipStream_t stream) {
     AT_REQUIRE(a.L >= 8 && a.B >= 1, "fused decoder tail needs at least 8 input rows");
     const size_t lds = (size_t)DT_LDS_FLOATS * sizeof(float);
-    { static LdsAttrFlags lds_attr_0; if (int rc = set_max_dynamic_lds(lds_attr_0, seanet_dectail_kernel, lds)) return rc; }
+    { static LdsAttrFlags lds_attr_0; if (int rc = set_max_dynamic_lds(lds_attr_0, seanet_dectail_kernel<false>, lds)) return rc; }
     const long long tiles = (long long)a.B * ((2 * a.L + DT_TO - 1) / DT_TO);
     const int grid = (int)(tiles < 512 ? tiles : 512);   // two resident workgroups per CU
-    hipLaunchKernelGGL(seanet_dectail_kernel, dim3(grid), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(seanet_dectail_kernel<false>, dim3(grid), dim3(256), lds, stream, a);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_seanet_dectail_skip(const DecTailArgs& a_, int skip, long long out_stride, hipStream_t stream) {
+    DecTailSkipArgs a;
+    static_cast<DecTailArgs&>(a) = a_;
+    a.skip = skip; a.out_stride = out_stride;
+    AT_REQUIRE(a.L >= 8 && a.B >= 1, "fused decoder tail needs at least 8 input rows");
+    AT_REQUIRE(skip >= 0 && skip < 2 * a.L && out_stride >= 2 * a.L - skip, "fused decoder tail: bad skip / stride");
+    const size_t lds = (size_t)DT_LDS_FLOATS * sizeof(float);
+    { static LdsAttrFlags lds_attr_1; if (int rc = set_max_dynamic_lds(lds_attr_1, seanet_dectail_kernel<true>, lds)) return rc; }
+    const long long tiles = (long long)a.B * ((2 * a.L + DT_TO - 1) / DT_TO - skip / DT_TO);
+    const int grid = (int)(tiles < 512 ? tiles : 512);
+    hipLaunchKernelGGL(seanet_dectail_kernel<true>, dim3(grid), dim3(256), lds, stream, a);
     AT_CHECK_HIP(hipGetLastError());
     return 0;
 }

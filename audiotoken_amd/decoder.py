@@ -52,3 +52,9 @@ class AcousticDecoder(_EncodecCallable):
                                                _cabi.current_stream_handle(self.device), self._status.data_ptr())
         _cabi.check(rc, "at_encodec_decode_checked")
         return out
+
+    def new_stream(self, batch: int = 1):
+        """A stateful decoder for tokens that arrive frame by frame (audiotoken_amd/streaming.py): the concatenated ``push`` outputs are the audio
+        one-shot ``forward`` gives for the concatenated tokens, in memory bounded by the largest push. Streams of one decoder are independent."""
+        from .streaming import AcousticDecodeStream
+        return AcousticDecodeStream(self, batch)

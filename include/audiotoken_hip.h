@@ -138,6 +138,8 @@ int at_encodec_encode_stream_checked(at_encodec_t* h, const void* state_in, void
  *   the fp32 MFMA;
  *   "lstm_f16x2" 1/0 — the persistent LSTM's recurrent product on the two-piece fp16 scheme (h in (-1, 1) always fits: no range check) or on
  *   three bf16 pieces (default on; needs "lstm_x3" = 1);
+ *   "dec_skip_twin" 1/0 — TEST-ONLY twin (default 0): one-shot decode and a decode stream's first push store through the tail kernels' skip / stride
+ *   variant with skip = 0 and a dense stride; bit-identical results;
  *   "lstm_spin_limit" n >= 0 — polls of a hand-off flag before a workgroup of the persistent LSTM gives up and the status word of the
  *   *_checked entry points becomes 1 (default 2^18, i.e. 0.1-0.3 s; 0 makes the first unready poll give up — used by the tests);
  *   "subbatch" n >= 1 — clips per pass through the conv stack (default 256 or $AUDIOTOKEN_SUBBATCH): bounds
@@ -162,6 +164,37 @@ int at_encodec_decode(at_encodec_t* h, const int64_t* codes, int B, int K, int T
 /* Same, plus the device status word of at_encodec_encode_checked (the decoder runs the same persistent LSTM). */
 int at_encodec_decode_checked(at_encodec_t* h, const int64_t* codes, int B, int K, int T, float* wav, void* workspace,
                               size_t workspace_bytes, at_stream_t stream, uint32_t* status_dev);
+
+/* ---- streaming acoustic decode: the waveform of one at_encodec_decode of the concatenated tokens, frame by frame, in bounded memory -------------
+ * Every conv of the decoder is causal, so a stream carries per clip: the last 6 rows of the quantised embedding z (128 wide, the history of the
+ * k = 7 first conv), h and c of both LSTM layers, and the last 2 rows of ELU(lstm + skip) (512 wide). A push of t_new frames gathers the code-book
+ * rows of the new codes behind the carried z rows, runs the first conv over that window without padding, continues the LSTM from the carried
+ * (h, c) over the new rows and runs the upsampling stack on [2 carried rows | new rows] with the one-shot kernels; the first 640 samples of the
+ * window (an output sample n reaches back to row floor(n / 320) - 2) are never stored. The first push of a stream carries nothing and drops
+ * nothing: it IS a one-shot decode of its frames (same kernels, same bits) that also writes the state, and like one it needs t_new >= 7.
+ *   state   device memory, at_encodec_decode_stream_state_bytes(h, B) bytes (B * 3840 floats: z rows, h0, c0, h1, c1, y rows), 16-byte aligned.
+ *           The handle keeps the same host-side note per state ADDRESS as for the encode stream, with the direction: a decode state is refused by
+ *           at_encodec_encode_stream_checked and an encode state by at_encodec_decode_stream_checked.
+ *   TRANSACTION RULE: as for the encode stream — state_in != state_out; a push whose status word is non-zero left wav_out and state_out
+ *           invalid and state_in untouched, and is repeated from the same state_in after changing the options; on success the caller swaps.
+ *   codes_new device int64 [B][K][t_new]; wav_out device float [B][320 * t_new].
+ * ROUTES: a push takes every route of at_encodec_decode under the handle's options ("persistent_lstm", "lstm_pipe", "lstm_x3", "lstm_f16x2",
+ * "fused_dectail", "dec_chain", "up_f16x2", "res_f16x2", "tail_f16x2"), on windows as short as 3 rows. As for the encode stream, the three-piece
+ * bf16 recurrence has no state variant: with "lstm_f16x2" = 0 a push runs the fp32 persistent recurrence. A mid-stream push stores through the
+ * skip / stride variant of the tail kernels (compile-time; "dec_skip_twin" = 1 sends one-shot decode and first pushes through the same variant with
+ * skip = 0 and a dense stride — bit-identical, the option exists for the tests).
+ * BIT-IDENTITY to at_encodec_decode of the same handle and options holds for a stream's first push (any B, K, t_new >= 7). Later pushes run the
+ * same arithmetic on other tiles (window-relative tile boundaries select the GEMM's interior or boundary body, the LSTM's projection GEMM sees
+ * another M): they agree with one-shot decode to rounding and are held to the oracle's bar only (profiles/stream_decode.txt).
+ * Argument errors (null state, state_in == state_out, a state this handle does not know, an encode state, another B, t_new < 1, a first push
+ * with t_new < 7, a workspace below at_encodec_decode_stream_workspace_bytes, a handle finalized without a decoder) return non-zero with
+ * at_last_error set; nothing is launched and the device stays usable. */
+size_t at_encodec_decode_stream_state_bytes(const at_encodec_t* h, int B);
+int at_encodec_decode_stream_reset(at_encodec_t* h, void* state_dev, int B, at_stream_t stream);
+/* Workspace of one push of t_new frames: a one-shot decode's of (B, t_new + 2) plus the two windows, whatever was pushed before. */
+size_t at_encodec_decode_stream_workspace_bytes(const at_encodec_t* h, int B, int t_new);
+int at_encodec_decode_stream_checked(at_encodec_t* h, const void* state_in, void* state_out, const int64_t* codes_new, int B, int K, int t_new,
+                                     float* wav_out, void* workspace, size_t workspace_bytes, at_stream_t stream, uint32_t* status_dev);
 
 /* ---- semantic_m tokenizer: log-mel front-end + Wav2Vec2-BERT conformer + LayerNorm + VQ ------------------
  * Replaces reference Wav2VecBertEncoder (audiotoken/encoder.py:111-186): ctor = Wav2VecBertProcessor +
