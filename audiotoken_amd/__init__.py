@@ -1,11 +1,11 @@
 """audiotoken_amd — MI355X-native hot path of cmeraki/audiotoken behind the reference's API surface.
 
-``from audiotoken_amd import AudioToken, Tokenizers, AUDIO_EXTS, TAR_EXTS, ZIP_EXTS, read_audio``
+``from audiotoken_amd import AudioToken, Tokenizers, AUDIO_EXTS, TAR_EXTS, ZIP_EXTS, read_audio, save_audio``
 (reference audiotoken/__init__.py:1-3).
 """
 from .configs import AUDIO_EXTS, TAR_EXTS, ZIP_EXTS, Tokenizers  # noqa: F401
 
-__all__ = ["AudioToken", "KMeans", "Tokenizers", "AUDIO_EXTS", "TAR_EXTS", "ZIP_EXTS", "read_audio"]
+__all__ = ["AudioToken", "KMeans", "Tokenizers", "AUDIO_EXTS", "TAR_EXTS", "ZIP_EXTS", "read_audio", "save_audio"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "read_audio":
         from .audio_io import read_audio
         return read_audio
+    if name == "save_audio":
+        from .audio_io import save_audio
+        return save_audio
     raise AttributeError(name)

@@ -29,6 +29,11 @@ class SegmentDesc(C.Structure):
 PCM_S16, PCM_S32, PCM_F32, PCM_U8 = 0, 1, 2, 3
 
 
+class PcmRowDesc(C.Structure):
+    """Mirror of ``at_pcm_row_desc`` (include/audiotoken_hip.h): one row of at_pcm_peaks / at_pcm_pack."""
+    _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("n", C.c_int64), ("scale", C.c_float), ("reserved", C.c_int32)]
+
+
 class GemmDesc(C.Structure):
     """Mirror of ``at_gemm_desc`` (include/audiotoken_hip.h)."""
     _fields_ = [
@@ -128,6 +133,8 @@ SIGNATURES = {
     "at_clock_stamp": (C.c_int, [C.c_void_p, C.c_void_p]),
     "at_segments_zmuv_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "at_segments_from_pcm_zmuv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "at_pcm_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "at_pcm_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "at_flac_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_void_p]),
     "at_flac_decode": (C.c_int64, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64]),
     "at_op_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),

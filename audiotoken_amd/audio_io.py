@@ -303,3 +303,62 @@ def iterate_tar(x, model_sample_rate: int, chunk_size: int = 30, on_skip=None):
 def iterate_zip(x, model_sample_rate: int, chunk_size: int = 30, on_skip=None):
     """Reference ``iterate_zip`` (audiotoken/utils.py:104-136)."""
     return _iterate_archive(x, model_sample_rate, chunk_size, on_skip)
+
+
+# ---- audio output: 16-bit PCM WAV (reference ``save_audio``, audiotoken/utils.py: clamp to +-0.99, or rescale by min(0.99 / peak, 1)) --------------------------
+# The quantisation rule is this project's (torchaudio is not installed, so its float -> PCM_S rounding cannot be pinned; INTEGRATION.md): a NaN becomes 0
+# and an infinity the clamp limit (both counted as non-finite); otherwise y = x * scale in fp32, clamped to +-limit (counted as clipped when the clamp changed
+# it); q = rint(y * 32768), round half to even, stored as int16 (|q| <= 32440 at limit 0.99). The device writer (csrc/pcm_writer.hip) computes the same bits.
+PCM_LIMIT = np.float32(0.99)
+
+
+def finite_peak(x) -> np.float32:
+    """max |x| over the finite samples (0 when there is none), in float32."""
+    a = np.abs(np.asarray(x, dtype=np.float32).reshape(-1))
+    a = a[np.isfinite(a)]
+    return np.float32(a.max()) if a.size else np.float32(0.0)
+
+
+def rescale_factor(peak) -> np.float32:
+    """min(0.99 / peak, 1) in float32 (1 for a silent waveform)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = PCM_LIMIT / np.float32(peak)
+    return np.float32(1.0) if not s < np.float32(1.0) else np.float32(s)
+
+
+def pcm16_from_float(x, scale=1.0, limit=PCM_LIMIT):
+    """``(int16 samples, clipped count, non-finite count)`` of a float waveform by the rule above."""
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float32)).reshape(-1)
+    limit = np.float32(limit)
+    nan, inf = np.isnan(x), np.isinf(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = x * np.float32(scale)
+        c = np.minimum(np.maximum(y, -limit), limit)
+        bad = nan | inf
+        clipped = int(np.count_nonzero((c != y) & ~bad))
+        c = np.where(inf, np.copysign(limit, x), c)
+        c = np.where(nan, np.float32(0.0), c)
+        q = np.rint(c * np.float32(32768.0)).astype(np.int16)
+    return q, clipped, int(np.count_nonzero(bad))
+
+
+def save_audio(wav, path, sample_rate: int, rescale: bool = False):
+    """Reference ``save_audio`` for one waveform (what ``AudioToken.decode`` returns: ``[1, N]`` or ``[N]``, tensor or array): mono 16-bit PCM WAV at
+    ``sample_rate``, clamped to +-0.99 or, with ``rescale``, scaled by min(0.99 / peak, 1) first. An existing file is replaced. Returns
+    ``(clipped, non_finite)`` sample counts."""
+    from .writer import WavWriter
+    x = wav.detach().cpu().numpy() if hasattr(wav, "detach") else np.asarray(wav)
+    if x.ndim == 2 and x.shape[0] != 1:
+        raise ValueError(f"save_audio writes mono audio, got {x.shape[0]} channels")
+    if x.ndim > 2:
+        raise ValueError(f"save_audio takes [N] or [1, N], got shape {tuple(x.shape)}")
+    scale = rescale_factor(finite_peak(x)) if rescale else np.float32(1.0)
+    q, clipped, nonfinite = pcm16_from_float(x, scale)
+    w = WavWriter(path, sample_rate)
+    try:
+        w.write(q)
+        w.close()
+    except BaseException:
+        w.abort()
+        raise
+    return clipped, nonfinite

@@ -270,15 +270,16 @@ class AudioToken:
         self._encode_files(files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs)
 
     @staticmethod
-    def _input_files(audio_files, audio_dir) -> List[str]:
-        """The inputs of encode_batch_files / fit_quantizer: the given files, or every file with a known extension under ``audio_dir``, sorted."""
+    def _input_files(audio_files, audio_dir, exts=None) -> List[str]:
+        """The inputs of encode_batch_files / fit_quantizer / decode_batch_files: the given files, or every file with a known extension (``exts``; default: the
+        audio and archive extensions) under ``audio_dir``, sorted."""
         if audio_files is not None:
             files = [str(f) for f in audio_files]
         else:
             # every file under audio_dir with one of the extensions — the set the reference's `glob.iglob(f"{audio_dir}/**/*{ext}", recursive=True)` per
             # extension finds (datasets.py:47-50; glob does not descend into or match dot-names) — in ONE walk instead of fourteen, sorted (the sharding
             # below needs every rank to see the same order)
-            exts = AUDIO_EXTS + TAR_EXTS + ZIP_EXTS
+            exts = tuple(exts) if exts is not None else AUDIO_EXTS + TAR_EXTS + ZIP_EXTS
             files = []
             seen = set()    # glob follows symlinked sub-directories (datasets laid out as symlink farms); so does this walk, once per real directory
             try:            # the root counts as seen: a link cycle back to it must not list its own files a second time
@@ -604,6 +605,48 @@ class AudioToken:
             return self._decode_single(tokens_mem)
         else:
             raise ValueError(f"Unsupported input type {type(tokens)}. Should be one of: {np.ndarray, os.PathLike, Path}")
+
+    def decode_batch_files(self, batch_size: int, outdir: os.PathLike, chunk_size: Optional[int] = 30, num_workers: int = 12,
+                           token_files: Optional[List[os.PathLike]] = None, token_dir: Optional[Union[os.PathLike, Path]] = None,
+                           rescale: bool = False, **kwargs) -> None:
+        """The way back from ``encode_batch_files`` (reference scripts/detokenize_audio.py + utils.save_audio): ``.npy`` token files -> mono 16-bit PCM
+        WAV files at 24 kHz. Acoustic only. ``token_dir`` is walked once (sorted, dot-names skipped) and its relative tree is kept; ``token_files`` are
+        written flat into ``outdir``; each input becomes ``<stem>.wav``. An existing output is OVERWRITTEN — unlike the encode side, which appends:
+        appending audio to an earlier run's file has no use. A token file is int16 / int64 ``[K, T]`` or ``[1, K, T]``; one that is unreadable, has
+        another rank, more code books than the model, no frames or a code outside [0, 1023] is skipped and recorded in ``self.skipped_files`` (as is the
+        second of two inputs that map to one output name) and the run goes on. Segments mirror the encode side: every ``chunk_size * 75`` frames are
+        decoded as a clip of their own (``chunk_size=None``: the file is one clip), batched by equal K, right-padded (with the "no code" value -1: zero embedding rows) and trimmed; every batch
+        passes ``AcousticDecoder.verified``. Samples are clamped to +-0.99, or with ``rescale=True`` scaled by the FILE's min(0.99 / peak, 1) (the float rows
+        of a file stay on the device until its last row is decoded; a file holding more than ``max_held_bytes`` is skipped), rounded half to even and
+        narrowed to int16 on the device (writer.py; ``device_writer=False`` converts on the host by the same rule). ``num_workers`` files are read ahead, in
+        order. Under ``torch.distributed`` whole files are sharded by size (``shard_across_ranks=False``: this rank takes every file it was given).
+        ``self.run_summary`` / ``self.run_timings`` describe the run."""
+        if self.tokenizer_name != Tokenizers.acoustic:
+            self.load_decoder()      # raises what `decode` raises for a tokenizer without a decoder
+        assert token_files or token_dir, "Either token_files or token_dir must be provided"
+        assert not (token_files and token_dir), "Provide either token_files or token_dir, not both"
+        known = {"shard_across_ranks", "device_writer", "max_held_bytes"}
+        decoder_kwargs = {k: v for k, v in kwargs.items() if k not in known}
+        self.load_decoder(**decoder_kwargs)
+        from . import writer as Wr
+        self.skipped_files = []
+        outdir = sanitize_path(outdir)
+        files = self._input_files(token_files, token_dir, exts=(".npy",))
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and kwargs.get("shard_across_ranks", True):
+            files = self._shard_files(files)
+        inputs, taken = [], {}
+        for f in files:
+            out = Wr.output_path(f, outdir, None if token_files else str(token_dir))
+            if out in taken:
+                logger.error(f"Skipping {f}: its output {out} is already that of {taken[out]}")
+                self.skipped_files.append((f, f"duplicate output name: {out} is already written from {taken[out]}"))
+                continue
+            taken[out] = f
+            inputs.append((f, out))
+        on_gpu = torch.device(self.device).type == "cuda"
+        Wr.decode_files(self, inputs, int(batch_size), chunk_size, int(num_workers), bool(rescale), bool(kwargs.get("device_writer", on_gpu)),
+                        int(kwargs.get("max_held_bytes", Wr.DEFAULT_MAX_HELD_BYTES)), self.model_config.model_sample_rate, self.model_config.model_token_rate)
 
     def _decode_single(self, tokens: torch.Tensor) -> torch.Tensor:
         """core.py:355-359."""

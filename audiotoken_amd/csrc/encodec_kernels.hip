@@ -312,9 +312,10 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restri
     const int t = (int)(bt - b * T);
     f4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < K; ++k) {
-        long long idx = codes[(b * K + k) * T + t];
-        idx = idx < 0 ? 0 : (idx >= RVQ_CODES ? RVQ_CODES - 1 : idx);
-        acc += *reinterpret_cast<const f4*>(codebooks + ((long long)k * RVQ_CODES + idx) * RVQ_D + d4 * 4);
+        const long long raw = codes[(b * K + k) * T + t];
+        const long long idx = raw < 0 ? 0 : (raw >= RVQ_CODES ? RVQ_CODES - 1 : raw);
+        const f4 e = *reinterpret_cast<const f4*>(codebooks + ((long long)k * RVQ_CODES + idx) * RVQ_D + d4 * 4);
+        if (raw >= 0) acc += e;     // a negative code is "no code": the frame's row of z stays zero (include/audiotoken_hip.h, at_encodec_decode)
     }
     *reinterpret_cast<f4*>(z + bt * RVQ_D + d4 * 4) = acc;
 }
@@ -414,9 +415,10 @@ __global__ __launch_bounds__(256) void stream_dec_state_kernel(StreamDecStateArg
         const int t = v - a.hist;
         val = f4{0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < a.K; ++k) {
-            long long idx = a.codes[((long long)b * a.K + k) * a.Tn + t];
-            idx = idx < 0 ? 0 : (idx >= RVQ_CODES ? RVQ_CODES - 1 : idx);
-            val += *reinterpret_cast<const f4*>(a.codebooks + ((long long)k * RVQ_CODES + idx) * RVQ_D + c4 * 4);
+            const long long raw = a.codes[((long long)b * a.K + k) * a.Tn + t];
+            const long long idx = raw < 0 ? 0 : (raw >= RVQ_CODES ? RVQ_CODES - 1 : raw);
+            const f4 e = *reinterpret_cast<const f4*>(a.codebooks + ((long long)k * RVQ_CODES + idx) * RVQ_D + c4 * 4);
+            if (raw >= 0) val += e;     // as rvq_decode_kernel: a negative code adds nothing
         }
     } else {
         val = *reinterpret_cast<const f4*>(a.src + ((long long)b * a.Tn + (v - a.hist)) * a.C + c4 * 4);

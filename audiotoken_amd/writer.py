@@ -1,0 +1,493 @@
+"""Output side of ``decode_batch_files``: a tree of ``.npy`` token files -> a tree of 16-bit PCM WAV files.
+
+The mirror image of feeder.py. The split is the same one:
+
+  host    what needs no samples: reading and validating the token files (``num_workers`` files ahead, in order), the segment plan, padding the ragged
+          token rows (token bytes are ~1 / 80 of the audio bytes), the RIFF header, the file writes;
+  device  everything that touches samples: the decode itself, and the DEVICE WRITER (csrc/pcm_writer.hip: ``at_pcm_peaks`` / ``at_pcm_pack``) that clamps or
+          rescales, rounds, narrows to int16 and compacts the valid samples of the padded batch into one buffer — so ONE device-to-host copy per batch
+          carries exactly the valid samples at 2 bytes each, into pinned memory on a side stream while the device decodes the next batch and the host
+          writes the one before.
+
+Segments mirror how ``encode_batch_files`` cut the audio: every ``chunk_size``-second chunk was encoded as a clip of its own (conv padding and the LSTM
+start from zero at every chunk), so every ``chunk_size * 75`` frames are decoded as a clip of their own.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import struct
+import time
+from dataclasses import dataclass, field
+from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .audio_io import PCM_LIMIT, pcm16_from_float, rescale_factor
+from .logger import get_logger
+from .prefetch import ordered_map
+
+logger = get_logger(__name__)
+
+HOP = 320                     # samples per frame (24 kHz / 75 Hz)
+MIN_FRAMES = 7                # a one-shot decode needs 7 frames: shorter rows are padded up to it and trimmed
+PAD_CODE = -1                 # "no code" (include/audiotoken_hip.h, at_encodec_decode): a padded frame is a zero embedding row, as the reference zero-extends short inputs
+CODEBOOK_SIZE = 1024
+WAV_MAX_DATA = 0xFFFFFFFF - 36    # the RIFF size field is 32 bits: 36 header bytes + data
+DEFAULT_MAX_HELD_BYTES = 4 << 30  # rescale=True: float rows of a file that stay on the device until its last row is decoded
+
+
+# ---- token files ------------------------------------------------------------------------------------------------------------------------------------------
+class TokenFileError(Exception):
+    """A token file ``decode_batch_files`` cannot decode; the message is the reason recorded in ``AudioToken.skipped_files``."""
+
+
+def read_token_file(path, num_codebooks: int) -> np.ndarray:
+    """``[K, T]`` int64 codes of a token file (int16 or int64 ``[K, T]`` or ``[1, K, T]``), validated on the host before anything is uploaded."""
+    try:
+        arr = np.load(str(path), allow_pickle=False)
+    except Exception as e:   # noqa: BLE001 — np.load raises ValueError / OSError / EOFError / UnpicklingError depending on how the file is damaged
+        raise TokenFileError(f"unreadable token file ({type(e).__name__}: {e})") from e
+    if not isinstance(arr, np.ndarray):
+        raise TokenFileError("unreadable token file (not a single .npy array)")
+    if arr.dtype not in (np.dtype(np.int16), np.dtype(np.int64)):
+        raise TokenFileError(f"token dtype {arr.dtype} (int16 or int64 expected)")
+    if arr.ndim == 3 and arr.shape[0] == 1:
+        arr = arr[0]
+    if arr.ndim != 2:
+        raise TokenFileError(f"token array of rank {arr.ndim} with shape {tuple(arr.shape)} ([K, T] or [1, K, T] expected)")
+    K, T = arr.shape
+    if K < 1 or K > int(num_codebooks):
+        raise TokenFileError(f"{K} code books, the model has {int(num_codebooks)}")
+    if T == 0:
+        raise TokenFileError("empty token file (T = 0)")
+    lo, hi = int(arr.min()), int(arr.max())
+    if lo < 0 or hi >= CODEBOOK_SIZE:
+        raise TokenFileError(f"code {lo if lo < 0 else hi} outside [0, {CODEBOOK_SIZE - 1}]")
+    if HOP * 2 * T > WAV_MAX_DATA:
+        raise TokenFileError(f"{T} frames would pass the 4 GiB limit of a RIFF file")
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
+def output_path(token_file: str, outdir: str, token_dir: Optional[str]) -> str:
+    """``<stem>.wav``: flat in ``outdir`` for a file list, at the mirrored relative path for a directory."""
+    stem = os.path.splitext(os.path.basename(token_file))[0]
+    rel = ""
+    if token_dir is not None:
+        rel = os.path.dirname(os.path.relpath(token_file, start=str(token_dir)))
+        if rel.startswith("..") or os.path.isabs(rel):
+            rel = ""
+    return os.path.join(outdir, rel, stem + ".wav")
+
+
+# ---- the segment plan: a pure function of (K, T) per file ---------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class SegmentRow:
+    file: int        # the caller's file id
+    t0: int          # first frame of the segment inside the file
+    valid: int       # frames of the segment
+    last: bool       # the file's last segment
+
+
+@dataclass
+class BatchPlan:
+    """One decode call: ``rows`` of equal K, right-padded to ``t_max`` frames. Row b of the decoder's output starts at float ``src_off[b]`` and has
+    ``n[b]`` real samples; packed, the rows follow each other without gaps from ``dst_off[b]``."""
+    K: int
+    rows: List[SegmentRow]
+    t_max: int = 0
+    src_off: List[int] = field(default_factory=list)
+    dst_off: List[int] = field(default_factory=list)
+    n: List[int] = field(default_factory=list)
+    total: int = 0
+
+    def finish(self) -> "BatchPlan":
+        self.t_max = max(MIN_FRAMES, max(r.valid for r in self.rows))
+        self.src_off = [b * HOP * self.t_max for b in range(len(self.rows))]
+        self.n = [HOP * r.valid for r in self.rows]
+        self.dst_off = [0] * len(self.rows)
+        pos = 0
+        for b, n in enumerate(self.n):
+            self.dst_off[b] = pos
+            pos += n
+        self.total = pos
+        return self
+
+
+def chunk_frames_of(chunk_size, token_rate: int = 75) -> Optional[int]:
+    return None if chunk_size is None else max(1, int(round(chunk_size * token_rate)))
+
+
+def plan_batches(files: Iterable[Tuple[int, int, int]], batch_size: int, chunk_frames: Optional[int]) -> Iterator[BatchPlan]:
+    """``files`` = (id, K, T) in order -> the decode calls. A file is cut into segments of ``chunk_frames`` frames (None: one segment); consecutive segments of
+    equal K fill batches of up to ``batch_size`` rows; a change of K closes the batch. Lazy: a batch is yielded as soon as it is full."""
+    assert batch_size >= 1 and (chunk_frames is None or chunk_frames >= 1)
+    rows: List[SegmentRow] = []
+    K_open = None
+    for fid, K, T in files:
+        assert K >= 1 and T >= 1
+        if rows and K != K_open:
+            yield BatchPlan(K_open, rows).finish()
+            rows = []
+        K_open = K
+        step = T if chunk_frames is None else chunk_frames
+        for t0 in range(0, T, step):
+            valid = min(step, T - t0)
+            rows.append(SegmentRow(fid, t0, valid, t0 + valid == T))
+            if len(rows) == batch_size:
+                yield BatchPlan(K_open, rows).finish()
+                rows = []
+    if rows:
+        yield BatchPlan(K_open, rows).finish()
+
+
+def padded_tokens(plan: BatchPlan, tokens_of) -> torch.Tensor:
+    """The ``[B, K, t_max]`` int64 batch of a plan, rows right-padded with ``PAD_CODE``; ``tokens_of(file id)`` = that file's ``[K, T]`` array."""
+    out = np.full((len(plan.rows), plan.K, plan.t_max), PAD_CODE, dtype=np.int64)
+    for b, r in enumerate(plan.rows):
+        out[b, :, :r.valid] = tokens_of(r.file)[:, r.t0:r.t0 + r.valid]
+    return torch.from_numpy(out)
+
+
+# ---- the WAV file ---------------------------------------------------------------------------------------------------------------------------------------------
+class WavTooLarge(Exception):
+    pass
+
+
+class WavWriter:
+    """Plain RIFF PCM, mono, 16 bit. The samples go to ``<path>.part``; ``close`` patches the two header sizes and moves the file into place (replacing an
+    existing one), ``abort`` removes it: ``path`` either holds a complete file or is untouched."""
+
+    def __init__(self, path, sample_rate: int):
+        self.path = str(path)
+        self.tmp = self.path + ".part"
+        self.sample_rate = int(sample_rate)
+        self.data_bytes = 0
+        os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+        self._f = open(self.tmp, "wb")
+        self._f.write(self._header(0))
+
+    def _header(self, data_bytes: int) -> bytes:
+        sr = self.sample_rate
+        return (b"RIFF" + struct.pack("<I", 36 + data_bytes) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sr, sr * 2, 2, 16)
+                + b"data" + struct.pack("<I", data_bytes))
+
+    def write(self, pcm) -> None:
+        """``pcm``: int16 samples (an array, or a bytes-like of little-endian int16)."""
+        buf = memoryview(np.ascontiguousarray(pcm, dtype="<i2")).cast("B") if isinstance(pcm, np.ndarray) else memoryview(pcm).cast("B")
+        if self.data_bytes + len(buf) > WAV_MAX_DATA:
+            raise WavTooLarge(f"{self.path}: more than 4 GiB")
+        self._f.write(buf)
+        self.data_bytes += len(buf)
+
+    def close(self) -> None:
+        f, self._f = self._f, None
+        try:
+            f.seek(4)
+            f.write(struct.pack("<I", 36 + self.data_bytes))
+            f.seek(40)
+            f.write(struct.pack("<I", self.data_bytes))
+            f.close()
+            os.replace(self.tmp, self.path)
+        except BaseException:
+            self._f = f
+            self.abort()
+            raise
+
+    def abort(self) -> None:
+        f, self._f = self._f, None
+        try:
+            if f is not None and not f.closed:
+                f.close()
+        finally:
+            try:
+                os.remove(self.tmp)
+            except OSError:
+                pass
+
+
+# ---- float rows -> int16, on the device or (device_writer=False) on the host -------------------------------------------------------------------------------------
+PackRow = Tuple[int, int, int, float]     # (src_off, dst_off, n, scale)
+
+
+class _Packed:
+    """The int16 samples and per-row ``[clipped, non-finite]`` counts of one pack, possibly still on their way to the host."""
+
+    def __init__(self, pcm=None, counts=None, buf=None, event=None, pool=None, total=0, nrows=0, counts_at=0):
+        self._pcm, self._counts, self._buf, self._event, self._pool = pcm, counts, buf, event, pool
+        self._total, self._nrows, self._counts_at = total, nrows, counts_at
+
+    def result(self):
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+            host = self._buf.numpy()
+            self._pcm = host[:2 * self._total].view(np.int16)
+            self._counts = host[self._counts_at:self._counts_at + 8 * self._nrows].view(np.uint32).reshape(self._nrows, 2)
+        return self._pcm, self._counts
+
+    def release(self) -> None:
+        if self._buf is not None:
+            if self._event is not None:
+                self._event.synchronize()
+                self._event = None
+            self._pool.give(self._buf)
+            self._buf = self._pcm = self._counts = None
+
+
+class DeviceWriter:
+    """``at_pcm_peaks`` / ``at_pcm_pack`` on the decoder's stream, then the packed buffer's copy into pinned memory on a side stream."""
+
+    def __init__(self, device):
+        from . import _cabi
+        from .feeder import _POOL
+        self._cabi = _cabi
+        self.lib = _cabi.load()
+        self.device = torch.device(device)
+        assert self.device.type == "cuda", "the device writer needs a HIP device"
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self._pool = _POOL
+        self.bytes_downloaded = 0
+
+    def hold(self, wav: torch.Tensor):
+        return wav.reshape(-1)
+
+    def _descs(self, rows: Sequence[PackRow], src_numel: int) -> torch.Tensor:
+        for s, d, n, _ in rows:
+            assert 0 <= s and s + n <= src_numel and d >= 0 and n >= 0, "pack row outside the decoder's output"
+        arr = (self._cabi.PcmRowDesc * len(rows))(*[self._cabi.PcmRowDesc(int(s), int(d), int(n), float(sc), 0) for s, d, n, sc in rows])
+        return torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy()).to(self.device)
+
+    def peaks(self, held: torch.Tensor, rows: Sequence[PackRow]) -> np.ndarray:
+        if not rows:
+            return np.zeros(0, np.float32)
+        with torch.cuda.device(self.device):
+            descs = self._descs(rows, held.numel())
+            out = torch.empty(len(rows), dtype=torch.float32, device=self.device)
+            self._cabi.check(self.lib.at_pcm_peaks(held.data_ptr(), descs.data_ptr(), len(rows), max(r[2] for r in rows), out.data_ptr(),
+                                                   self._cabi.current_stream_handle(self.device)), "at_pcm_peaks")
+            return out.cpu().numpy()
+
+    def pack(self, held: torch.Tensor, rows: Sequence[PackRow]) -> _Packed:
+        total = sum(r[2] for r in rows)
+        if not rows or total == 0:
+            return _Packed(np.zeros(0, np.int16), np.zeros((len(rows), 2), np.uint32))
+        assert all(d + n <= total for _, d, n, _ in rows), "pack row outside the packed buffer"
+        counts_at = (2 * total + 15) // 16 * 16
+        nbytes = counts_at + 8 * len(rows)
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            descs = self._descs(rows, held.numel())
+            dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._cabi.check(self.lib.at_pcm_pack(held.data_ptr(), descs.data_ptr(), len(rows), max(r[2] for r in rows), float(PCM_LIMIT), dev.data_ptr(),
+                                                  dev.data_ptr() + counts_at, C.c_void_p(main.cuda_stream)), "at_pcm_pack")
+            packed = torch.cuda.Event()
+            packed.record(main)
+            buf = self._pool.take(nbytes)
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(packed)
+                buf[:nbytes].copy_(dev, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self.copy_stream)
+            dev.record_stream(self.copy_stream)
+        self.bytes_downloaded += nbytes
+        return _Packed(buf=buf, event=done, pool=self._pool, total=total, nrows=len(rows), counts_at=counts_at)
+
+
+class HostWriter:
+    """``device_writer=False``: the float batch comes to the host and numpy applies the same rule (audio_io.pcm16_from_float) — the comparison path."""
+
+    def __init__(self, device=None):
+        self.bytes_downloaded = 0
+
+    def hold(self, wav: torch.Tensor):
+        x = wav.detach().reshape(-1).cpu().numpy()
+        self.bytes_downloaded += x.nbytes
+        return x
+
+    def peaks(self, held: np.ndarray, rows: Sequence[PackRow]) -> np.ndarray:
+        from .audio_io import finite_peak
+        return np.array([finite_peak(held[s:s + n]) for s, _, n, _ in rows], dtype=np.float32)
+
+    def pack(self, held: np.ndarray, rows: Sequence[PackRow]) -> _Packed:
+        pcm = np.zeros(sum(r[2] for r in rows), dtype=np.int16)
+        counts = np.zeros((len(rows), 2), dtype=np.uint32)
+        for i, (s, d, n, scale) in enumerate(rows):
+            pcm[d:d + n], counts[i, 0], counts[i, 1] = pcm16_from_float(held[s:s + n], np.float32(scale))
+        return _Packed(pcm, counts)
+
+
+# ---- the run ----------------------------------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class _File:
+    path: str
+    out: str
+    tokens: Optional[np.ndarray] = None
+    rows_left: int = 0                  # segments not yet decoded
+    peak: np.float32 = np.float32(0.0)  # rescale=True: max over the rows decoded so far
+    held_bytes: int = 0
+    dropped: bool = False               # skipped after its first row was planned (max_held_bytes, a write error)
+    writer: Optional[WavWriter] = None
+    written: bool = False
+
+
+def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_size, num_workers: int, rescale: bool, device_writer: bool,
+                 max_held_bytes: int, sample_rate: int, token_rate: int) -> None:
+    """The loop of ``AudioToken.decode_batch_files``: ``inputs`` = (token file, output path) in order. ``tok`` supplies ``decoder`` (``forward`` /
+    ``verified``), ``device``, ``skipped_files``; ``run_summary`` / ``run_timings`` are left on it."""
+    start_time = time.time()
+    dec = tok.decoder
+    device = torch.device(tok.device)
+    num_codebooks = int(getattr(getattr(dec, "_h", None), "n_codebooks", tok.num_codebooks))
+    backend = DeviceWriter(device) if device_writer else HostWriter(device)
+    fb0 = getattr(dec, "fallback_batches", 0)
+    summary = tok.run_summary = {"files": 0, "segments": 0, "batches": 0, "fallback_batches": 0, "clipped_samples": 0, "nonfinite_samples": 0,
+                                 "skipped_files": 0}
+    # host seconds per stage, the keys of the encode loop: `stage` = the next batch's token files (read-ahead wait, validation, padding, upload),
+    # `encode_call` = enqueueing the decode, `device_wait` = blocked on the device (the status read of `verified`, the peaks), `save` = writing the PCM of the
+    # batches before (while the device decodes the current one)
+    rt = tok.run_timings = {"stage_s": 0.0, "encode_call_s": 0.0, "device_wait_s": 0.0, "save_s": 0.0, "batches": 0, "rows": 0}
+
+    def skipped(name, why):
+        logger.error(f"Skipping {name}: {why}")
+        tok.skipped_files.append((name, why))
+
+    files: dict = {}
+
+    def load(item):
+        i, (path, out) = item
+        try:
+            return i, path, out, read_token_file(path, num_codebooks), None
+        except TokenFileError as e:
+            return i, path, out, None, str(e)
+
+    def valid_files():
+        for i, path, out, tokens, why in ordered_map(load, list(enumerate(inputs)), num_workers):
+            if tokens is None:
+                skipped(path, why)
+                continue
+            K, T = tokens.shape
+            step = chunk_frames_of(chunk_size, token_rate)
+            files[i] = _File(path, out, tokens, rows_left=1 if step is None else (T + step - 1) // step)
+            yield i, K, T
+
+    def drop(f: _File, why: str):
+        if not f.dropped:
+            f.dropped = True
+            if f.writer is not None:
+                f.writer.abort()
+                f.writer = None
+            skipped(f.path, why)
+
+    plans = plan_batches(valid_files(), batch_size, chunk_frames_of(chunk_size, token_rate))
+    held: List[list] = []       # [plan, float rows (device tensor / host array)] decoded but not packed: rescale=True waits for the last row of a file
+    pending: List[tuple] = []   # (plan rows packed, _Packed): packed, on their way to the host, not yet written
+
+    def write_pending():
+        while pending:
+            rows, packed = pending.pop(0)
+            try:
+                pcm, counts = packed.result()
+                for j, (r, d, n) in enumerate(rows):
+                    f = files[r.file]
+                    if f.dropped:
+                        continue
+                    try:
+                        if f.writer is None:
+                            f.writer = WavWriter(f.out, sample_rate)
+                        f.writer.write(pcm[d:d + n])
+                        summary["clipped_samples"] += int(counts[j, 0])
+                        summary["nonfinite_samples"] += int(counts[j, 1])
+                        if r.last:
+                            w, f.writer = f.writer, None
+                            w.close()
+                            f.written = True
+                            summary["files"] += 1
+                    except (OSError, WavTooLarge) as e:
+                        drop(f, f"cannot write {f.out}: {type(e).__name__}: {e}")
+            finally:
+                packed.release()
+
+    def release_held():
+        """Pack every held batch whose files are all complete (clamp mode: every batch, at once), in order."""
+        while held:
+            plan, rows_f = held[0]
+            last = files[plan.rows[-1].file]
+            if rescale and last.rows_left > 0 and not last.dropped:
+                break
+            held.pop(0)
+            keep, pack_rows, pos = [], [], 0
+            for b, r in enumerate(plan.rows):
+                f = files[r.file]
+                if f.dropped:
+                    continue
+                keep.append((r, pos, plan.n[b]))
+                pack_rows.append((plan.src_off[b], pos, plan.n[b], float(rescale_factor(f.peak)) if rescale else 1.0))
+                pos += plan.n[b]
+            if keep:
+                pending.append((keep, backend.pack(rows_f, pack_rows)))
+            for r in plan.rows:
+                if r.last:      # (no later batch holds a row of it)
+                    files[r.file].tokens = None
+
+    ok = False
+    try:
+        t0 = time.perf_counter()
+        plan = next(plans, None)
+        toks = padded_tokens(plan, lambda i: files[i].tokens).to(device) if plan is not None else None
+        rt["stage_s"] += time.perf_counter() - t0
+        while plan is not None:
+            t0 = time.perf_counter()
+            wav = dec.forward(toks)                           # asynchronous on the device
+            t1 = time.perf_counter()
+            write_pending()                                   # the batches before: their copies ran behind the decode before this one
+            t2 = time.perf_counter()
+            nxt = next(plans, None)                           # the next batch's tokens are read / padded / uploaded while this one decodes
+            nxt_toks = padded_tokens(nxt, lambda i: files[i].tokens).to(device) if nxt is not None else None
+            t3 = time.perf_counter()
+            if hasattr(dec, "verified"):
+                wav = dec.verified(wav, toks)                 # the correctness ladder: no audio is accepted before the call's status was read
+            rows_f = backend.hold(wav)
+            if rescale:
+                pk = backend.peaks(rows_f, [(plan.src_off[b], 0, plan.n[b], 1.0) for b in range(len(plan.rows))])
+            for b, r in enumerate(plan.rows):
+                f = files[r.file]
+                f.rows_left -= 1
+                if rescale and not f.dropped:
+                    f.peak = max(f.peak, np.float32(pk[b]))
+                    f.held_bytes += 4 * HOP * plan.t_max
+                    if f.held_bytes > max_held_bytes:
+                        drop(f, f"rescale=True holds the file's float rows on the device until its last row: more than max_held_bytes = {max_held_bytes}")
+            held.append([plan, rows_f])
+            del wav, rows_f
+            release_held()
+            t4 = time.perf_counter()
+            rt["encode_call_s"] += t1 - t0; rt["save_s"] += t2 - t1; rt["stage_s"] += t3 - t2; rt["device_wait_s"] += t4 - t3
+            rt["batches"] += 1; rt["rows"] += len(plan.rows)
+            summary["batches"] += 1; summary["segments"] += len(plan.rows)
+            plan, toks = nxt, nxt_toks
+        t0 = time.perf_counter()
+        write_pending()
+        rt["save_s"] += time.perf_counter() - t0
+        ok = True
+    finally:
+        # also when a decode raised: what was verified and packed before it belongs in its files; then every file still open is incomplete and is removed
+        try:
+            if not ok:
+                write_pending()
+        except Exception as e:   # noqa: BLE001 — must not mask the exception that ended the run
+            logger.error(f"decode_batch_files: writing the batches before the failure failed too: {type(e).__name__}: {e}")
+        for _, packed in pending:
+            packed.release()
+        for f in files.values():
+            if f.writer is not None:
+                f.writer.abort()
+                f.writer = None
+        summary["fallback_batches"] = getattr(dec, "fallback_batches", 0) - fb0
+        summary["skipped_files"] = len(tok.skipped_files)
+        rt["total_s"] = time.time() - start_time
+        rt["bytes_downloaded"] = backend.bytes_downloaded
+    if tok.skipped_files:
+        logger.error(f"decode_batch_files: {len(tok.skipped_files)} input(s) were skipped and have NO audio file (AudioToken.skipped_files): "
+                     + "; ".join(f"{p} ({why})" for p, why in tok.skipped_files[:8]) + (" ..." if len(tok.skipped_files) > 8 else ""))

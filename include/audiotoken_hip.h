@@ -158,7 +158,10 @@ int at_encodec_profile_read(at_encodec_t* h, char* names, size_t names_cap, floa
 size_t at_encodec_decode_workspace_bytes(const at_encodec_t* h, int B, int T);
 
 /* Replaces AcousticDecoder.forward (audiotoken/decoder.py:66-76): codes device int64 [B][K][T] ->
- * wav device float32 [B*320*T] (the reference's [1, B*320*T] row). */
+ * wav device float32 [B*320*T] (the reference's [1, B*320*T] row). A NEGATIVE code means "no code": it adds no code-book row, so a frame whose K codes
+ * are all negative enters the decoder as a zero embedding row. That is how a clip shorter than the 7 frames a decode needs is extended
+ * (decode_batch_files): the reference zero-extends a short input in front of its first reflect padding, and frames behind a clip's end never reach earlier
+ * samples (the decoder is causal). Codes above 1023 are clamped to 1023. */
 int at_encodec_decode(at_encodec_t* h, const int64_t* codes, int B, int K, int T, float* wav, void* workspace,
                       size_t workspace_bytes, at_stream_t stream);
 /* Same, plus the device status word of at_encodec_encode_checked (the decoder runs the same persistent LSTM). */
@@ -334,6 +337,28 @@ int at_segments_from_pcm(const at_segment_desc* descs_dev, int nseg, int seg_len
 size_t at_segments_zmuv_workspace_bytes(int nseg, int max_chunk_out_len);
 int at_segments_from_pcm_zmuv(const at_segment_desc* descs_dev, int nseg, int seg_len, int max_chunk_out_len, float pad_value, float eps, float* segments,
                               float* masks, void* workspace, size_t workspace_bytes, at_stream_t stream);
+
+/* ---- output side of decode_batch_files: the decoder's float32 batch -> compacted 16-bit PCM ------------------------------------------
+ * One descriptor per row (built on the host; the array lives in device memory):
+ *   src_off   first sample of the row, in floats from `src` (the padded decoder output [B][320 T_max]: src_off = b * 320 * T_max)
+ *   dst_off   first sample of the row in the packed output, in int16 elements from `dst` (rows follow each other without gaps)
+ *   n         samples of the row (320 * valid frames)
+ *   scale     multiplies every finite sample before the clamp (1, or the file's min(0.99 / peak, 1) computed in fp32 on the host)
+ * The entry points trust the descriptors: every [src_off, src_off + n) must lie inside `src` and every [dst_off, dst_off + n) inside `dst`.
+ * at_pcm_peaks: peaks[r] = max |x| over the FINITE samples of row r (0 for a row without one); an integer atomic max on the bit pattern, so the result does
+ * not depend on scheduling. at_pcm_pack, per sample: NaN -> 0 and +-infinity -> +-limit (both counted as non-finite); otherwise y = x * scale in fp32,
+ * c = min(max(y, -limit), limit), counted as clipped when c != y; q = rint(c * 32768) (round half to even) stored as int16. counts: uint32 [nrows][2] =
+ * {clipped, non-finite} per row, zeroed by the call. limit in (0, 32767 / 32768]; max_n >= every row's n (it sizes the grid). Rows whose source and destination
+ * are 16-byte aligned (offsets that are multiples of 8 samples from aligned bases) take 16-byte loads and stores; any other row is still converted correctly.
+ * Both are stream-ordered and do not allocate; arguments are validated before the device is touched. The reference has no counterpart (it converts on the
+ * host: audiotoken/utils.py save_audio). */
+typedef struct at_pcm_row_desc {
+    int64_t src_off, dst_off, n;
+    float scale;
+    int32_t reserved;
+} at_pcm_row_desc;
+int at_pcm_peaks(const float* src, const at_pcm_row_desc* rows_dev, int nrows, int64_t max_n, float* peaks, at_stream_t stream);
+int at_pcm_pack(const float* src, const at_pcm_row_desc* rows_dev, int nrows, int64_t max_n, float limit, int16_t* dst, uint32_t* counts, at_stream_t stream);
 
 /* ---- measurement aid (bench.py): the clock the chip held over a stretch of the stream ----------------------------------------------------------------
  * slots_dev: device uint64 [16][2], zeroed by the caller. One tiny launch writes {s_memtime (shader cycles), s_memrealtime (100 MHz)} into slot [xcc] for every
