@@ -523,7 +523,8 @@ EncPlan make_plan(int B, int N, int sub) {
 // A frame of the LSTM's input depends on samples back to 320 t - 478 (conv0 6, four blocks 2 each at their rate, strided convs 2, 4, 5, 8), so two
 // frames are the smallest frame-aligned context; the first two output frames of a window [context | new] are dropped.
 constexpr int kHop = 320, kStreamCtx = 2 * kHop, kStreamDrop = 2, kStreamHist = 6;
-constexpr int kStreamFirstFrames = 7;   // a stream's first push (unless final) fills the final conv's history and takes its reflected front rows from real rows
+constexpr int kFinPad = 6;              // reflected front rows of the final k = 7 conv; a clip of <= 6 frames is zero-extended to 7 rows first (the reference's rule)
+constexpr int kStreamFirstFrames = 7;  // a stream's first push (unless final) fills the final conv's history and takes its reflected front rows from real rows
 struct StreamState {
     float *ctx, *h[2], *c[2], *yhist;
     StreamState(void* base, int B) {
@@ -1143,7 +1144,9 @@ static int encodec_encode_impl(at_encodec_t* h, const float* wav, const float* m
                 if (int rc = resblock(h->res[s], x, ws + p.off_h[s], r, L, g, stream, EPI_ELU)) return rc;
                 prof.end(stream);
             }
-            prof.begin(kDown[s], 1, stream);
+            // stage-3 strided conv as a split GEMM; behind the fp32 block (no chain3) a stand-alone pass splits its input first: two launches
+            const bool down3_gemm = s == 3 && h->down256_x3 && h->bf16x3 && h->down3_s && L % 8 == 0 && L >= 16;
+            prof.begin(kDown[s], down3_gemm && !chain3 ? 2 : 1, stream);
             if (s == 1 && h->fused_down64 && L % 4 == 0) {
                 Down64Args da;
                 da.x = r; da.out = out; da.w = h->down[1].w; da.b = h->down[1].b; da.B = g; da.L = L;
@@ -1165,7 +1168,7 @@ static int encodec_encode_impl(at_encodec_t* h, const float* wav, const float* m
                 if (int rc = launch_gemm_bf16x3(ga, stream)) return rc;
                 if (chain3)
                     if (int rc = launch_reflect_front(ga.S2, g, 16, 1, p.Lpc, 2, stream, cnp)) return rc;
-            } else if (s == 3 && h->down256_x3 && h->bf16x3 && h->down3_s && L % 8 == 0 && L >= 16) {
+            } else if (down3_gemm) {
                 __bf16* s3 = reinterpret_cast<__bf16*>(ws + p.off_s3);
                 if (!chain3)
                     if (int rc = launch_split_phase_major(r, g, L, 256, 8, p.Lp3, s3, stream)) return rc;
@@ -1217,8 +1220,16 @@ static int encodec_encode_impl(at_encodec_t* h, const float* wav, const float* m
         prof.end(stream);
         yw = ywm; embw = ws + sp.off_embw; yp = reinterpret_cast<__bf16*>(ws + sp.off_yp);
     }
-    prof.begin("final_conv", 1, stream);
-    if (h->bf16x3 && h->fin_f16x2 && h->fin_f && Ty > 6) {
+    const bool short_fin = Ty <= kFinPad;   // fewer rows than the k = 7 conv reflects (one-shot clips of 321..1920 samples; mid-stream Ty >= 7)
+    prof.begin("final_conv", short_fin ? 2 : 1, stream);
+    if (short_fin) {
+        // the reference's short-input rule (pad1d_reflect): zero-extend the rows to pad + 1 = 7, reflect on that copy, keep the first Ty outputs.
+        // The copy [B][7][512] lives in the gate buffer, which the LSTM has finished with (B * T * 2048 floats, T >= 2).
+        float* yz = ws + p.off_xg;
+        AT_CHECK_HIP(hipMemsetAsync(yz, 0, (size_t)B * (kFinPad + 1) * kH * sizeof(float), stream));
+        if (int rc = launch_copy_rows(yw, (long long)Ty * kH, yz, (long long)(kFinPad + 1) * kH, Ty, kH, B, stream)) return rc;
+        if (int rc = conv_gemm(h->fin, yz, (long long)(kFinPad + 1) * kH, kFinPad + 1, embw, (long long)Ty * kDim, Ty, B, PRO_NONE, nullptr, 0, stream)) return rc;
+    } else if (h->bf16x3 && h->fin_f16x2 && h->fin_f) {
         // y = ELU(lstm + skip) -> two fp16 pieces in windowed layout (6 reflected front rows), then the k = 7 conv as a windowed split GEMM
         int* range_status = h->range_tab + 2 * AS_FINAL;
         if (int rc = launch_split_windowed(yw, B, Ty, kH, 1, 6, Lpf, yp, stream, XB_SCHEME_F16X2, XB_F16_ACT_SCALE, range_status)) return rc;

@@ -58,7 +58,9 @@ int at_encodec_num_codebooks(const at_encodec_t* h);
 size_t at_encodec_workspace_bytes(const at_encodec_t* h, int B, int N);
 
 /* Replaces AcousticEncoder.forward (audiotoken/encoder.py:44-57).
- *   wav   device float32 [B][N]           (24 kHz mono, any N >= 1 with N > 9 so reflect padding is defined)
+ *   wav   device float32 [B][N]           (24 kHz mono, any N >= 321: the stage-3 strided conv reflects 8 of its ceil(N/40) input rows, and a
+ *                                          shorter clip is refused with "clip too short for the strided convs". Clips of 321..1920 samples, T = 2..6
+ *                                          frames, follow the reference's short-input rule in the final conv: rows zero-extended to 7, then reflected)
  *   mask  device float32 [B][N] or NULL   — ignored, exactly as the reference ignores attention_mask
  *   n_q   number of codebooks in {1..loaded}; the reference derives it from the bandwidth (encoder.py:50-52)
  *   codes device int16   [B][n_q][T], T = ceil(N/320) returned through *T_out (may be NULL)
@@ -96,6 +98,7 @@ int at_encodec_encode_checked(at_encodec_t* h, const float* wav, const float* ma
  *           buffers what does not fill a frame yet (AcousticStream in audiotoken_amd/streaming.py does).
  *   final   != 0: the last samples of the stream, any n_new >= 0; the one-shot path's right-edge padding applies inside the window and
  *           T = ceil(n_new / 320). The stream is finished: a further push from state_out is an error until at_encodec_stream_reset.
+ *           A stream whose FIRST push is the final one is a one-shot encode: it needs n_new >= 321 like at_encodec_encode.
  *   codes   device int16 [B][n_q][T], T returned through *T_out (n_new / 320, or ceil for the final push); emb_out optional [B][T][128].
  * BIT-IDENTITY: where the one-shot call and the pushes select the same kernels (an even total length with the stage-1 / stage-2 / stage-3
  * lengths divisible by 4 / 5 / 8, i.e. any multiple of 320, pushed in multiples of 320) codes and embeddings are bit-identical to

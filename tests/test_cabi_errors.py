@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from audiotoken_amd import _cabi, weights as W
+from tests import parity as P
 
 
 def test_token_count_helpers_match_the_reference_formulas():
@@ -55,6 +56,38 @@ def test_encode_argument_validation(cuda_device):
     assert "decoder" in _cabi.last_error()
     assert lib.at_encodec_encode(h, wav.data_ptr(), None, B, N, 8, codes.data_ptr(), None, None, ws.data_ptr(), nbytes, st) == 0
     torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_clip_below_the_minimum_length_is_refused(cuda_device):
+    """N = 320 (L[3] = 8: the stage-3 strided conv would reflect all of its input) returns an error with a message; nothing is written,
+    and the handle encodes the shortest valid clip (N = 321, T = 2) to the oracle's ids right afterwards."""
+    from audiotoken_amd.configs import AcousticEncoderConfig
+    from audiotoken_amd.encoder import AcousticEncoder
+    from oracle import encodec_ref as R
+    w = W.synth_encodec_weights(seed=0, with_decoder=False)
+    enc = AcousticEncoder(AcousticEncoderConfig(bandwidth=6), device="cuda:0", weights=w)
+    lib, h = enc._h.lib, enc._h.handle
+    B = 2
+    wav = torch.from_numpy(W.synth_waveform(B, 321, 24000, seed=7321)).cuda()
+    codes = torch.full((B, 8, 2), -1, dtype=torch.int16, device="cuda")
+    nbytes = lib.at_encodec_workspace_bytes(h, B, 321)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    st = _cabi.current_stream_handle(torch.device("cuda:0"))
+    short = wav[:, :320].contiguous()
+    for n, message in ((320, "too short for the strided convs"), (9, "N >= 10")):
+        assert lib.at_encodec_encode(h, short.data_ptr(), None, B, n, 8, codes.data_ptr(), None, None, ws.data_ptr(), nbytes, st) != 0
+        assert message in _cabi.last_error(), (n, _cabi.last_error())
+    torch.cuda.synchronize()
+    assert bool((codes == -1).all()), "a refused call must not write codes"
+    with pytest.raises(_cabi.HipLibraryError, match="too short"):
+        enc(short)
+    t_out = C.c_int(0)
+    assert lib.at_encodec_encode(h, wav.data_ptr(), None, B, 321, 8, codes.data_ptr(), C.byref(t_out), None, ws.data_ptr(), nbytes, st) == 0, _cabi.last_error()
+    torch.cuda.synchronize()
+    assert t_out.value == 2
+    ref, margins = R.acoustic_encode(w, wav.cpu(), 8, return_margins=True)
+    P.assert_rvq_equal_or_explained(codes.cpu(), ref, margins, P.RVQ_TIE, "N=321 after a refused call")
 
 
 @pytest.mark.gpu
