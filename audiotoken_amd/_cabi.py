@@ -34,6 +34,23 @@ class PcmRowDesc(C.Structure):
     _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("n", C.c_int64), ("scale", C.c_float), ("reserved", C.c_int32)]
 
 
+class FlacRowDesc(C.Structure):
+    """Mirror of ``at_flac_row_desc`` (include/audiotoken_hip.h): one row of at_flac_encode_rows."""
+    _fields_ = [("src_off", C.c_int64), ("n", C.c_int64), ("first_block", C.c_int32), ("scale", C.c_float)]
+
+
+class FlacBlock(C.Structure):
+    """Mirror of ``at_flac_block`` (include/audiotoken_hip.h): one block record of the FLAC encoders."""
+    _fields_ = [("first", C.c_int64), ("byte_off", C.c_int64), ("row", C.c_int32), ("n", C.c_int32), ("kind", C.c_int32), ("order", C.c_int32),
+                ("porder", C.c_int32), ("nbytes", C.c_int32)]
+
+
+FLAC_BLOCK = 4096
+FLAC_CONSTANT, FLAC_VERBATIM, FLAC_FIXED = 0, 1, 2
+FLAC_BLOCK_DTYPE = np.dtype([("first", "<i8"), ("byte_off", "<i8"), ("row", "<i4"), ("n", "<i4"), ("kind", "<i4"), ("order", "<i4"), ("porder", "<i4"),
+                             ("nbytes", "<i4")])
+
+
 class GemmDesc(C.Structure):
     """Mirror of ``at_gemm_desc`` (include/audiotoken_hip.h)."""
     _fields_ = [
@@ -135,6 +152,12 @@ SIGNATURES = {
     "at_segments_from_pcm_zmuv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "at_pcm_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "at_pcm_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "at_flac_encode_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "at_flac_encode_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "at_flac_encode_pcm16": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64]),
+    "at_flac_write_frames": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "at_flac_streaminfo": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "at_flac_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_void_p]),
     "at_flac_decode": (C.c_int64, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64]),
     "at_op_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),

@@ -342,23 +342,60 @@ def pcm16_from_float(x, scale=1.0, limit=PCM_LIMIT):
     return q, clipped, int(np.count_nonzero(bad))
 
 
-def save_audio(wav, path, sample_rate: int, rescale: bool = False):
+def save_audio(wav, path, sample_rate: int, rescale: bool = False, audio_format: Optional[str] = None):
     """Reference ``save_audio`` for one waveform (what ``AudioToken.decode`` returns: ``[1, N]`` or ``[N]``, tensor or array): mono 16-bit PCM WAV at
     ``sample_rate``, clamped to +-0.99 or, with ``rescale``, scaled by min(0.99 / peak, 1) first. An existing file is replaced. Returns
-    ``(clipped, non_finite)`` sample counts."""
-    from .writer import WavWriter
+    ``(clipped, non_finite)`` sample counts. ``audio_format``: "wav" or "flac"; None = FLAC when ``path`` ends in ``.flac``, otherwise WAV. FLAC holds the
+    same samples: compressed by the host encoder for host data, by the device encoder (csrc/flac_encode.hip) for a tensor on a HIP device."""
+    from . import writer as Wr
+    if audio_format is None:
+        audio_format = "flac" if str(path).lower().endswith(".flac") else "wav"
+    if audio_format not in Wr.AUDIO_FORMATS:
+        raise ValueError(f"audio_format must be one of {Wr.AUDIO_FORMATS}, got {audio_format!r}")
+    shape = tuple(wav.shape) if hasattr(wav, "shape") else np.asarray(wav).shape
+    if len(shape) == 2 and shape[0] != 1:
+        raise ValueError(f"save_audio writes mono audio, got {shape[0]} channels")
+    if len(shape) > 2:
+        raise ValueError(f"save_audio takes [N] or [1, N], got shape {shape}")
+    if audio_format == "flac" and hasattr(wav, "is_cuda") and wav.is_cuda:
+        return _save_flac_device(wav, path, sample_rate, rescale)
     x = wav.detach().cpu().numpy() if hasattr(wav, "detach") else np.asarray(wav)
-    if x.ndim == 2 and x.shape[0] != 1:
-        raise ValueError(f"save_audio writes mono audio, got {x.shape[0]} channels")
-    if x.ndim > 2:
-        raise ValueError(f"save_audio takes [N] or [1, N], got shape {tuple(x.shape)}")
     scale = rescale_factor(finite_peak(x)) if rescale else np.float32(1.0)
     q, clipped, nonfinite = pcm16_from_float(x, scale)
-    w = WavWriter(path, sample_rate)
+    w = Wr.open_writer(path, sample_rate, audio_format)
     try:
-        w.write(q)
+        if audio_format == "flac":
+            recs, data = Wr.flac_encode_pcm16([q])
+            w.write(*Wr.flac_frames(recs, data, sample_rate, [0]))
+        else:
+            w.write(q)
         w.close()
     except BaseException:
         w.abort()
         raise
     return clipped, nonfinite
+
+
+def _save_flac_device(wav, path, sample_rate: int, rescale: bool):
+    """``save_audio`` of a device tensor as FLAC: peak, quantisation and compression on the device (the writer of ``decode_batch_files``)."""
+    import torch
+    from . import writer as Wr
+    x = wav.detach().reshape(-1).to(torch.float32).contiguous()
+    backend = Wr.DeviceFlacWriter(x.device, sample_rate)
+    with torch.cuda.device(x.device):
+        row = (0, 0, x.numel(), 1.0)
+        if rescale:
+            row = (0, 0, x.numel(), float(rescale_factor(backend.peaks(x, [row])[0])))
+        packed = backend.pack(x, [row])
+    w = Wr.FlacWriter(path, sample_rate)
+    try:
+        counts = packed.result()[-1]
+        out = int(counts[0, 0]), int(counts[0, 1])
+        packed.write_row(w, 0, 0, x.numel())
+        w.close()
+    except BaseException:
+        w.abort()
+        raise
+    finally:
+        packed.release()
+    return out

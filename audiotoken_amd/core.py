@@ -608,9 +608,10 @@ class AudioToken:
 
     def decode_batch_files(self, batch_size: int, outdir: os.PathLike, chunk_size: Optional[int] = 30, num_workers: int = 12,
                            token_files: Optional[List[os.PathLike]] = None, token_dir: Optional[Union[os.PathLike, Path]] = None,
-                           rescale: bool = False, **kwargs) -> None:
+                           rescale: bool = False, audio_format: str = "wav", **kwargs) -> None:
         """The way back from ``encode_batch_files`` (reference scripts/detokenize_audio.py + utils.save_audio): ``.npy`` token files -> mono 16-bit PCM
-        WAV files at 24 kHz. Acoustic only. ``token_dir`` is walked once (sorted, dot-names skipped) and its relative tree is kept; ``token_files`` are
+        WAV files at 24 kHz, or with ``audio_format="flac"`` FLAC files of the same samples (``<stem>.flac``; compressed on the device, csrc/flac_encode.hip;
+        anything but "wav" / "flac" raises ValueError before a decoder is loaded). Acoustic only. ``token_dir`` is walked once (sorted, dot-names skipped) and its relative tree is kept; ``token_files`` are
         written flat into ``outdir``; each input becomes ``<stem>.wav``. An existing output is OVERWRITTEN — unlike the encode side, which appends:
         appending audio to an earlier run's file has no use. A token file is int16 / int64 ``[K, T]`` or ``[1, K, T]``; one that is unreadable, has
         another rank, more code books than the model, no frames or a code outside [0, 1023] is skipped and recorded in ``self.skipped_files`` (as is the
@@ -620,7 +621,10 @@ class AudioToken:
         of a file stay on the device until its last row is decoded; a file holding more than ``max_held_bytes`` is skipped), rounded half to even and
         narrowed to int16 on the device (writer.py; ``device_writer=False`` converts on the host by the same rule). ``num_workers`` files are read ahead, in
         order. Under ``torch.distributed`` whole files are sharded by size (``shard_across_ranks=False``: this rank takes every file it was given).
-        ``self.run_summary`` / ``self.run_timings`` describe the run."""
+        ``self.run_summary`` / ``self.run_timings`` describe the run (``run_summary["audio_bytes"]``: the bytes of the files written)."""
+        from . import writer as Wr
+        if audio_format not in Wr.AUDIO_FORMATS:
+            raise ValueError(f"audio_format must be one of {Wr.AUDIO_FORMATS}, got {audio_format!r}")
         if self.tokenizer_name != Tokenizers.acoustic:
             self.load_decoder()      # raises what `decode` raises for a tokenizer without a decoder
         assert token_files or token_dir, "Either token_files or token_dir must be provided"
@@ -628,7 +632,6 @@ class AudioToken:
         known = {"shard_across_ranks", "device_writer", "max_held_bytes"}
         decoder_kwargs = {k: v for k, v in kwargs.items() if k not in known}
         self.load_decoder(**decoder_kwargs)
-        from . import writer as Wr
         self.skipped_files = []
         outdir = sanitize_path(outdir)
         files = self._input_files(token_files, token_dir, exts=(".npy",))
@@ -637,7 +640,7 @@ class AudioToken:
             files = self._shard_files(files)
         inputs, taken = [], {}
         for f in files:
-            out = Wr.output_path(f, outdir, None if token_files else str(token_dir))
+            out = Wr.output_path(f, outdir, None if token_files else str(token_dir), audio_format)
             if out in taken:
                 logger.error(f"Skipping {f}: its output {out} is already that of {taken[out]}")
                 self.skipped_files.append((f, f"duplicate output name: {out} is already written from {taken[out]}"))
@@ -646,7 +649,8 @@ class AudioToken:
             inputs.append((f, out))
         on_gpu = torch.device(self.device).type == "cuda"
         Wr.decode_files(self, inputs, int(batch_size), chunk_size, int(num_workers), bool(rescale), bool(kwargs.get("device_writer", on_gpu)),
-                        int(kwargs.get("max_held_bytes", Wr.DEFAULT_MAX_HELD_BYTES)), self.model_config.model_sample_rate, self.model_config.model_token_rate)
+                        int(kwargs.get("max_held_bytes", Wr.DEFAULT_MAX_HELD_BYTES)), self.model_config.model_sample_rate, self.model_config.model_token_rate,
+                        audio_format)
 
     def _decode_single(self, tokens: torch.Tensor) -> torch.Tensor:
         """core.py:355-359."""

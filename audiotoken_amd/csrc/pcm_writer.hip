@@ -19,6 +19,7 @@
 // on the bit pattern (non-negative floats order like unsigned integers), so the result does not depend on arrival order.
 #include "at_common.h"
 #include "../../include/audiotoken_hip.h"
+#include "pcm_quant.h"
 
 #include <cmath>
 
@@ -35,17 +36,6 @@ struct PcmRow {
 
 constexpr int PCM_PER_THREAD = 8;
 constexpr int PCM_TILE = 256 * PCM_PER_THREAD;
-
-// cnt: clipped samples in the low half, non-finite samples in the high half (at most 8 per thread, 512 per wave)
-__device__ __forceinline__ int pcm_quant(float x, float scale, float limit, unsigned& cnt) {
-    const float ax = fabsf(x);
-    const bool nan = x != x, inf = ax == INFINITY;
-    const float y = x * scale;
-    const float c = fminf(fmaxf(y, -limit), limit);
-    cnt += (nan || inf) ? 0x10000u : (c != y ? 1u : 0u);
-    const float v = nan ? 0.0f : (inf ? copysignf(limit, x) : c);
-    return (int)rintf(v * 32768.0f);
-}
 
 __device__ __forceinline__ unsigned pack2(int lo, int hi) { return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16); }
 

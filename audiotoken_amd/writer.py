@@ -1,4 +1,5 @@
-"""Output side of ``decode_batch_files``: a tree of ``.npy`` token files -> a tree of 16-bit PCM WAV files.
+"""Output side of ``decode_batch_files``: a tree of ``.npy`` token files -> a tree of 16-bit PCM WAV files, or of FLAC files
+(``audio_format="flac"``: the same samples, compressed on the device by csrc/flac_encode.hip, framed on the host).
 
 The mirror image of feeder.py. The split is the same one:
 
@@ -35,6 +36,9 @@ MIN_FRAMES = 7                # a one-shot decode needs 7 frames: shorter rows a
 PAD_CODE = -1                 # "no code" (include/audiotoken_hip.h, at_encodec_decode): a padded frame is a zero embedding row, as the reference zero-extends short inputs
 CODEBOOK_SIZE = 1024
 WAV_MAX_DATA = 0xFFFFFFFF - 36    # the RIFF size field is 32 bits: 36 header bytes + data
+FLAC_MAX_SAMPLES = (1 << 36) - 1  # STREAMINFO's sample count and the frame header's coded number have 36 bits
+FLAC_BLOCK = 4096                 # samples per block (include/audiotoken_hip.h: AT_FLAC_BLOCK); every row ends on one shorter block
+AUDIO_FORMATS = ("wav", "flac")
 DEFAULT_MAX_HELD_BYTES = 4 << 30  # rescale=True: float rows of a file that stay on the device until its last row is decoded
 
 
@@ -43,7 +47,7 @@ class TokenFileError(Exception):
     """A token file ``decode_batch_files`` cannot decode; the message is the reason recorded in ``AudioToken.skipped_files``."""
 
 
-def read_token_file(path, num_codebooks: int) -> np.ndarray:
+def read_token_file(path, num_codebooks: int, audio_format: str = "wav") -> np.ndarray:
     """``[K, T]`` int64 codes of a token file (int16 or int64 ``[K, T]`` or ``[1, K, T]``), validated on the host before anything is uploaded."""
     try:
         arr = np.load(str(path), allow_pickle=False)
@@ -65,20 +69,22 @@ def read_token_file(path, num_codebooks: int) -> np.ndarray:
     lo, hi = int(arr.min()), int(arr.max())
     if lo < 0 or hi >= CODEBOOK_SIZE:
         raise TokenFileError(f"code {lo if lo < 0 else hi} outside [0, {CODEBOOK_SIZE - 1}]")
-    if HOP * 2 * T > WAV_MAX_DATA:
+    if audio_format == "wav" and HOP * 2 * T > WAV_MAX_DATA:
         raise TokenFileError(f"{T} frames would pass the 4 GiB limit of a RIFF file")
+    if audio_format == "flac" and HOP * T > FLAC_MAX_SAMPLES:
+        raise TokenFileError(f"{T} frames would pass FLAC's limit of 2^36 - 1 samples")
     return np.ascontiguousarray(arr, dtype=np.int64)
 
 
-def output_path(token_file: str, outdir: str, token_dir: Optional[str]) -> str:
-    """``<stem>.wav``: flat in ``outdir`` for a file list, at the mirrored relative path for a directory."""
+def output_path(token_file: str, outdir: str, token_dir: Optional[str], audio_format: str = "wav") -> str:
+    """``<stem>.wav`` (``<stem>.flac``): flat in ``outdir`` for a file list, at the mirrored relative path for a directory."""
     stem = os.path.splitext(os.path.basename(token_file))[0]
     rel = ""
     if token_dir is not None:
         rel = os.path.dirname(os.path.relpath(token_file, start=str(token_dir)))
         if rel.startswith("..") or os.path.isabs(rel):
             rel = ""
-    return os.path.join(outdir, rel, stem + ".wav")
+    return os.path.join(outdir, rel, stem + "." + audio_format)
 
 
 # ---- the segment plan: a pure function of (K, T) per file ---------------------------------------------------------------------------------------------------
@@ -207,6 +213,109 @@ class WavWriter:
                 pass
 
 
+# ---- the FLAC file ------------------------------------------------------------------------------------------------------------------------------------------------
+class FlacTooLarge(Exception):
+    pass
+
+
+def flac_encode_pcm16(rows: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+    """The HOST twin of the device encoder (``at_flac_encode_pcm16``): int16 rows -> ``(block records, compacted subframe bytes)`` in the layout
+    ``at_flac_encode_rows`` produces (records in row order, ``byte_off`` the exclusive prefix sum of ``nbytes``). ctypes releases the GIL."""
+    from . import _cabi
+    lib = _cabi.load()
+    rows = [np.ascontiguousarray(r, dtype=np.int16).reshape(-1) for r in rows]
+    nblocks = sum((len(r) + FLAC_BLOCK - 1) // FLAC_BLOCK for r in rows)
+    cap = nblocks + 2 * sum(len(r) for r in rows)
+    recs = np.zeros(nblocks, dtype=_cabi.FLAC_BLOCK_DTYPE)
+    data = np.zeros(max(cap, 1), dtype=np.uint8)
+    b = off = 0
+    for j, r in enumerate(rows):
+        nb = lib.at_flac_encode_pcm16(r.ctypes.data, len(r), j, recs.ctypes.data + b * recs.itemsize, nblocks - b, data.ctypes.data, cap, off)
+        if nb < 0:
+            raise _cabi.HipLibraryError(f"at_flac_encode_pcm16 failed: {_cabi.last_error()}")
+        b += nb
+        if nb:
+            off = int(recs["byte_off"][b - 1]) + int(recs["nbytes"][b - 1])
+    return recs, data[:off]
+
+
+def flac_frames(recs: np.ndarray, data: np.ndarray, sample_rate: int, first_sample_of_row) -> Tuple[np.ndarray, np.ndarray]:
+    """``at_flac_write_frames``: the records' frames (header + CRC-8, subframe, CRC-16) back to back, and the call's stats for ``FlacWriter.write``."""
+    from . import _cabi
+    lib = _cabi.load()
+    if len(recs) == 0:
+        return np.zeros(0, dtype=np.uint8), np.zeros(7, dtype=np.int64)
+    recs = np.ascontiguousarray(recs)
+    first = np.ascontiguousarray(first_sample_of_row, dtype=np.int64)
+    cap = int(recs["nbytes"].sum()) + 18 * len(recs)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    stats = np.zeros(7, dtype=np.int64)
+    n = lib.at_flac_write_frames(recs.ctypes.data, len(recs), data.ctypes.data, len(data), int(sample_rate), first.ctypes.data, len(first), out.ctypes.data, cap,
+                                 stats.ctypes.data)
+    if n < 0:
+        raise _cabi.HipLibraryError(f"at_flac_write_frames failed: {_cabi.last_error()}")
+    return out[:n], stats
+
+
+class FlacWriter:
+    """FLAC (RFC 9639), mono, 16 bit, variable block size; the ``WavWriter`` contract. The frames go to ``<path>.part`` behind 42 reserved bytes; ``close``
+    writes the stream head there (STREAMINFO: block and frame size ranges, the sample count; MD5 zero = not computed) and moves the file into place,
+    ``abort`` removes it: ``path`` either holds a complete file or is untouched. ``samples`` is the index the next row's first sample gets."""
+
+    def __init__(self, path, sample_rate: int):
+        self.path = str(path)
+        self.tmp = self.path + ".part"
+        self.sample_rate = int(sample_rate)
+        self.samples = 0
+        self.data_bytes = 42
+        self._min_frame = self._max_frame = self._min_block = self._max_block = self._last_block = 0
+        os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+        self._f = open(self.tmp, "wb")
+        self._f.write(bytes(42))
+
+    def write(self, frames, stats) -> None:
+        """``frames`` / ``stats``: what ``at_flac_write_frames`` returned for the next blocks of the stream (coded from sample ``self.samples`` on)."""
+        min_frame, max_frame, min_block, max_block, last_block, nframes, nsamples = (int(x) for x in stats)
+        if nframes == 0:
+            return
+        if self.samples + nsamples > FLAC_MAX_SAMPLES:
+            raise FlacTooLarge(f"{self.path}: more than 2^36 - 1 samples")
+        self._f.write(memoryview(frames).cast("B"))
+        self.data_bytes += len(frames)
+        # STREAMINFO's minimum is over the blocks but the stream's last: the last block so far stops being the last
+        for b in (self._last_block, min_block):
+            if b:
+                self._min_block = b if not self._min_block else min(self._min_block, b)
+        self._max_block = max(self._max_block, max_block)
+        self._last_block = last_block
+        self._min_frame = min_frame if not self._min_frame else min(self._min_frame, min_frame)
+        self._max_frame = max(self._max_frame, max_frame)
+        self.samples += nsamples
+
+    def close(self) -> None:
+        from . import _cabi
+        f, self._f = self._f, None
+        try:
+            head = (C.c_uint8 * 42)()
+            _cabi.check(_cabi.load().at_flac_streaminfo(self.sample_rate, self._min_block or self._last_block, self._max_block, self._min_frame,
+                                                       self._max_frame, self.samples, head), "at_flac_streaminfo")
+            f.seek(0)
+            f.write(bytes(head))
+            f.close()
+            os.replace(self.tmp, self.path)
+        except BaseException:
+            self._f = f
+            self.abort()
+            raise
+
+    def abort(self) -> None:
+        WavWriter.abort(self)
+
+
+def open_writer(path, sample_rate: int, audio_format: str):
+    return FlacWriter(path, sample_rate) if audio_format == "flac" else WavWriter(path, sample_rate)
+
+
 # ---- float rows -> int16, on the device or (device_writer=False) on the host -------------------------------------------------------------------------------------
 PackRow = Tuple[int, int, int, float]     # (src_off, dst_off, n, scale)
 
@@ -227,6 +336,10 @@ class _Packed:
             self._counts = host[self._counts_at:self._counts_at + 8 * self._nrows].view(np.uint32).reshape(self._nrows, 2)
         return self._pcm, self._counts
 
+    def write_row(self, writer, j: int, d: int, n: int) -> None:
+        """Row ``j`` of the pack (``n`` samples from packed sample ``d``) into its file's writer."""
+        writer.write(self.result()[0][d:d + n])
+
     def release(self) -> None:
         if self._buf is not None:
             if self._event is not None:
@@ -234,6 +347,56 @@ class _Packed:
                 self._event = None
             self._pool.give(self._buf)
             self._buf = self._pcm = self._counts = None
+
+
+class _FlacPacked:
+    """The block records, compacted subframe bytes and per-row counts of one FLAC pack. From the device the records and counts come first; ``result`` —
+    where the host may wait, one batch later — reads the total from them and brings EXACTLY the compacted bytes."""
+
+    def __init__(self, recs=None, data=None, counts=None, sample_rate=0, owner=None, head=None, head_event=None, dev=None, bytes_at=0, nblocks=0, nrows=0):
+        self._recs, self._data, self._counts, self.sample_rate = recs, data, counts, sample_rate
+        self._owner, self._head, self._event, self._dev, self._bytes_at, self._nblocks, self._nrows = owner, head, head_event, dev, bytes_at, nblocks, nrows
+        self._body = None
+        self._row_at = None
+
+    def result(self):
+        if self._event is not None:
+            o = self._owner
+            self._event.synchronize()
+            self._event = None
+            host = self._head.numpy()
+            from . import _cabi
+            self._recs = host[:40 * self._nblocks].view(_cabi.FLAC_BLOCK_DTYPE)
+            self._counts = host[40 * self._nblocks:40 * self._nblocks + 8 * self._nrows].view(np.uint32).reshape(self._nrows, 2)
+            total = int(self._recs["byte_off"][-1]) + int(self._recs["nbytes"][-1])
+            assert 0 < total <= self._dev.numel() - self._bytes_at, "the device encoder's byte count is outside its buffer"
+            self._body = o._pool.take(total)
+            with torch.cuda.device(o.device), torch.cuda.stream(o.copy_stream):
+                self._body[:total].copy_(self._dev[self._bytes_at:self._bytes_at + total], non_blocking=True)
+            o.copy_stream.synchronize()
+            self._dev = None
+            o.bytes_downloaded += total
+            self._data = self._body.numpy()[:total]
+        if self._row_at is None:
+            self._row_at = np.searchsorted(self._recs["row"], np.arange(self._counts.shape[0] + 1))      # records are in row order
+        return self._recs, self._data, self._counts
+
+    def write_row(self, writer, j: int, d: int, n: int) -> None:
+        recs, data, _ = self.result()
+        mine = recs[self._row_at[j]:self._row_at[j + 1]]
+        assert int(mine["n"].sum()) == n, "the encoder's blocks do not add up to the row"
+        first = np.zeros(self._counts.shape[0], dtype=np.int64)
+        first[j] = writer.samples
+        writer.write(*flac_frames(mine, data, self.sample_rate, first))
+
+    def release(self) -> None:
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+        for buf in (self._head, self._body):
+            if buf is not None:
+                self._owner._pool.give(buf)
+        self._head = self._body = self._dev = self._recs = self._data = self._counts = None
 
 
 class DeviceWriter:
@@ -295,6 +458,56 @@ class DeviceWriter:
         return _Packed(buf=buf, event=done, pool=self._pool, total=total, nrows=len(rows), counts_at=counts_at)
 
 
+def _flac_rows(rows: Sequence["PackRow"]):
+    """(descriptor tuples (src_off, n, first_block, scale), blocks) of a pack's rows."""
+    out, nblocks = [], 0
+    for s, _, n, sc in rows:
+        out.append((int(s), int(n), nblocks, float(sc)))
+        nblocks += (int(n) + FLAC_BLOCK - 1) // FLAC_BLOCK
+    return out, nblocks
+
+
+class DeviceFlacWriter(DeviceWriter):
+    """``audio_format="flac"``: ``hold`` / ``peaks`` as the PCM writer; ``pack`` launches ``at_flac_encode_rows`` on the decoder's stream and sends the block
+    records and counts to pinned memory on the side stream; the compacted bytes follow in ``_FlacPacked.result``."""
+
+    def __init__(self, device, sample_rate: int):
+        super().__init__(device)
+        self.sample_rate = int(sample_rate)
+
+    def pack(self, held: torch.Tensor, rows: Sequence[PackRow]) -> _FlacPacked:
+        total = sum(r[2] for r in rows)
+        if not rows or total == 0:
+            return _FlacPacked(np.zeros(0, self._cabi.FLAC_BLOCK_DTYPE), np.zeros(0, np.uint8), np.zeros((len(rows), 2), np.uint32), self.sample_rate)
+        descs, nblocks = _flac_rows(rows)
+        for s, n, _, _ in descs:
+            assert 0 <= s and n >= 0 and s + n <= held.numel(), "pack row outside the decoder's output"
+        head_bytes = 40 * nblocks + 8 * len(rows)
+        bytes_at = (head_bytes + 15) // 16 * 16
+        cap = nblocks + 2 * total                                          # the worst case: every block VERBATIM
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            arr = (self._cabi.FlacRowDesc * len(descs))(*[self._cabi.FlacRowDesc(*d) for d in descs])
+            descs_dev = torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy()).to(self.device)
+            dev = torch.empty(bytes_at + cap, dtype=torch.uint8, device=self.device)
+            ws_bytes = int(self.lib.at_flac_encode_workspace_bytes(nblocks))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            self._cabi.check(self.lib.at_flac_encode_rows(held.data_ptr(), descs_dev.data_ptr(), len(rows), nblocks, float(PCM_LIMIT), dev.data_ptr(),
+                                                          dev.data_ptr() + bytes_at, cap, dev.data_ptr() + 40 * nblocks, ws.data_ptr(), ws_bytes,
+                                                          C.c_void_p(main.cuda_stream)), "at_flac_encode_rows")
+            packed = torch.cuda.Event()
+            packed.record(main)
+            head = self._pool.take(head_bytes)
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(packed)
+                head[:head_bytes].copy_(dev[:head_bytes], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self.copy_stream)
+            dev.record_stream(self.copy_stream)
+        self.bytes_downloaded += head_bytes
+        return _FlacPacked(sample_rate=self.sample_rate, owner=self, head=head, head_event=done, dev=dev, bytes_at=bytes_at, nblocks=nblocks, nrows=len(rows))
+
+
 class HostWriter:
     """``device_writer=False``: the float batch comes to the host and numpy applies the same rule (audio_io.pcm16_from_float) — the comparison path."""
 
@@ -318,6 +531,23 @@ class HostWriter:
         return _Packed(pcm, counts)
 
 
+class HostFlacWriter(HostWriter):
+    """``device_writer=False`` with ``audio_format="flac"``: numpy quantises, the host twin of the encoder (``at_flac_encode_pcm16``) compresses."""
+
+    def __init__(self, device=None, sample_rate: int = 0):
+        super().__init__(device)
+        self.sample_rate = int(sample_rate)
+
+    def pack(self, held: np.ndarray, rows: Sequence[PackRow]) -> _FlacPacked:
+        counts = np.zeros((len(rows), 2), dtype=np.uint32)
+        pcm = []
+        for i, (s, _, n, scale) in enumerate(rows):
+            q, counts[i, 0], counts[i, 1] = pcm16_from_float(held[s:s + n], np.float32(scale))
+            pcm.append(q)
+        recs, data = flac_encode_pcm16(pcm)
+        return _FlacPacked(recs, data, counts, self.sample_rate)
+
+
 # ---- the run ----------------------------------------------------------------------------------------------------------------------------------------------------
 @dataclass
 class _File:
@@ -328,22 +558,26 @@ class _File:
     peak: np.float32 = np.float32(0.0)  # rescale=True: max over the rows decoded so far
     held_bytes: int = 0
     dropped: bool = False               # skipped after its first row was planned (max_held_bytes, a write error)
-    writer: Optional[WavWriter] = None
+    writer: Optional[object] = None     # WavWriter / FlacWriter
     written: bool = False
 
 
 def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_size, num_workers: int, rescale: bool, device_writer: bool,
-                 max_held_bytes: int, sample_rate: int, token_rate: int) -> None:
+                 max_held_bytes: int, sample_rate: int, token_rate: int, audio_format: str = "wav") -> None:
     """The loop of ``AudioToken.decode_batch_files``: ``inputs`` = (token file, output path) in order. ``tok`` supplies ``decoder`` (``forward`` /
     ``verified``), ``device``, ``skipped_files``; ``run_summary`` / ``run_timings`` are left on it."""
     start_time = time.time()
     dec = tok.decoder
     device = torch.device(tok.device)
     num_codebooks = int(getattr(getattr(dec, "_h", None), "n_codebooks", tok.num_codebooks))
-    backend = DeviceWriter(device) if device_writer else HostWriter(device)
+    assert audio_format in AUDIO_FORMATS
+    if audio_format == "flac":
+        backend = DeviceFlacWriter(device, sample_rate) if device_writer else HostFlacWriter(device, sample_rate)
+    else:
+        backend = DeviceWriter(device) if device_writer else HostWriter(device)
     fb0 = getattr(dec, "fallback_batches", 0)
     summary = tok.run_summary = {"files": 0, "segments": 0, "batches": 0, "fallback_batches": 0, "clipped_samples": 0, "nonfinite_samples": 0,
-                                 "skipped_files": 0}
+                                 "skipped_files": 0, "audio_bytes": 0}
     # host seconds per stage, the keys of the encode loop: `stage` = the next batch's token files (read-ahead wait, validation, padding, upload),
     # `encode_call` = enqueueing the decode, `device_wait` = blocked on the device (the status read of `verified`, the peaks), `save` = writing the PCM of the
     # batches before (while the device decodes the current one)
@@ -358,7 +592,7 @@ def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_
     def load(item):
         i, (path, out) = item
         try:
-            return i, path, out, read_token_file(path, num_codebooks), None
+            return i, path, out, read_token_file(path, num_codebooks, audio_format), None
         except TokenFileError as e:
             return i, path, out, None, str(e)
 
@@ -388,15 +622,15 @@ def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_
         while pending:
             rows, packed = pending.pop(0)
             try:
-                pcm, counts = packed.result()
+                counts = packed.result()[-1]
                 for j, (r, d, n) in enumerate(rows):
                     f = files[r.file]
                     if f.dropped:
                         continue
                     try:
                         if f.writer is None:
-                            f.writer = WavWriter(f.out, sample_rate)
-                        f.writer.write(pcm[d:d + n])
+                            f.writer = open_writer(f.out, sample_rate, audio_format)
+                        packed.write_row(f.writer, j, d, n)
                         summary["clipped_samples"] += int(counts[j, 0])
                         summary["nonfinite_samples"] += int(counts[j, 1])
                         if r.last:
@@ -404,7 +638,8 @@ def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_
                             w.close()
                             f.written = True
                             summary["files"] += 1
-                    except (OSError, WavTooLarge) as e:
+                            summary["audio_bytes"] += (44 if audio_format == "wav" else 0) + w.data_bytes
+                    except (OSError, WavTooLarge, FlacTooLarge) as e:
                         drop(f, f"cannot write {f.out}: {type(e).__name__}: {e}")
             finally:
                 packed.release()

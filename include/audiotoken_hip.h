@@ -363,6 +363,54 @@ typedef struct at_pcm_row_desc {
 int at_pcm_peaks(const float* src, const at_pcm_row_desc* rows_dev, int nrows, int64_t max_n, float* peaks, at_stream_t stream);
 int at_pcm_pack(const float* src, const at_pcm_row_desc* rows_dev, int nrows, int64_t max_n, float limit, int16_t* dst, uint32_t* counts, at_stream_t stream);
 
+/* ---- FLAC output (RFC 9639): the decoder's float32 batch -> FLAC subframes on the device, framed on the host --------------------------
+ * The stream is mono, 16 bit, variable block size; every row is cut into blocks of AT_FLAC_BLOCK samples plus one shorter last block, one subframe per block.
+ * The sample value is the one of at_pcm_pack (same scale, limit, NaN / infinity handling and counts). The subframe rule is stated in DESIGN.md section 14 and
+ * at the top of csrc/flac_encode.hip; it is integer arithmetic throughout, so the device encoder and the host twin write IDENTICAL bytes.
+ * Row descriptor (built on the host; the array lives in device memory):
+ *   src_off      first sample of the row, in floats from `src`
+ *   n            samples of the row; the row has ceil(n / 4096) blocks
+ *   first_block  index of the row's first block among the launch's blocks: the exclusive prefix sum of the rows' block counts
+ *   scale        multiplies every finite sample before the clamp
+ * Block record, one per block in row order:
+ *   first        first sample of the block inside its row;  n  its samples (1 .. 4096)
+ *   kind         AT_FLAC_CONSTANT / AT_FLAC_VERBATIM / AT_FLAC_FIXED;  order  the FIXED predictor order (else 0);  porder  the Rice partition order (else 0)
+ *   nbytes       bytes of the subframe (zero-padded to a byte);  byte_off  its place in `bytes`: the exclusive prefix sum of nbytes in record order
+ *
+ * at_flac_encode_rows: blocks[nblocks], the subframes compacted back to back into `bytes`, counts uint32 [nrows][2] = {clipped, non-finite} per row (zeroed by the
+ * call). nblocks must be the sum of the rows' block counts. The worst case is 1 + 2 n bytes per block: size `bytes` (bytes_cap) by nblocks + 2 * sum(n); a
+ * subframe that would pass bytes_cap is not written. workspace: at_flac_encode_workspace_bytes(nblocks) bytes of device memory, 16-byte aligned. Stream-ordered,
+ * does not allocate; arguments are validated before the device is touched; the descriptors are trusted as those of at_pcm_pack are.
+ *
+ * at_flac_encode_pcm16: the HOST twin for one row of int16 samples (plain C++): records blocks[0 .. ceil(n / 4096)) with `row` and byte offsets counted from
+ * `byte_off`, subframes written to bytes + byte_off onwards (bytes_cap >= byte_off + blocks + 2 n). Returns the number of blocks, or -1.
+ *
+ * at_flac_write_frames: host. Frames the records in order: frame header (variable block size: the coded number is first_sample_of_row[row] + first; block-size
+ * code 12 for 4096, else 6 / 7 with the 8- / 16-bit n - 1 field; sample-rate code of the RFC's table, 0 for a rate outside it; mono; 16 bit) with its CRC-8,
+ * the subframe, the table-driven CRC-16. `out` needs 18 + nbytes bytes per frame. Returns the bytes written or -1; stats[7] = {min frame bytes, max frame
+ * bytes, min block size over all blocks BUT the call's last (0 when there is one block), max block size, the last block's size, frames, samples}.
+ *
+ * at_flac_streaminfo: host. The 42-byte stream head: "fLaC", a last-metadata-block STREAMINFO header and its 34 bytes (mono, 16 bit, MD5 all zero = not computed). */
+enum { AT_FLAC_BLOCK = 4096 };
+enum { AT_FLAC_CONSTANT = 0, AT_FLAC_VERBATIM = 1, AT_FLAC_FIXED = 2 };
+typedef struct at_flac_row_desc {
+    int64_t src_off, n;
+    int32_t first_block;
+    float scale;
+} at_flac_row_desc;
+typedef struct at_flac_block {
+    int64_t first, byte_off;
+    int32_t row, n, kind, order, porder, nbytes;
+} at_flac_block;
+size_t at_flac_encode_workspace_bytes(int nblocks);
+int at_flac_encode_rows(const float* src, const at_flac_row_desc* rows_dev, int nrows, int nblocks, float limit, at_flac_block* blocks, uint8_t* bytes,
+                        int64_t bytes_cap, uint32_t* counts, void* workspace, size_t workspace_bytes, at_stream_t stream);
+int64_t at_flac_encode_pcm16(const int16_t* samples, int64_t n, int row, at_flac_block* blocks, int64_t blocks_cap, uint8_t* bytes, int64_t bytes_cap,
+                             int64_t byte_off);
+int64_t at_flac_write_frames(const at_flac_block* blocks, int nblocks, const uint8_t* bytes, int64_t bytes_len, int sample_rate, const int64_t* first_sample_of_row,
+                             int nrows, uint8_t* out, int64_t cap, int64_t* stats);
+int at_flac_streaminfo(int sample_rate, int min_block, int max_block, int min_frame, int max_frame, int64_t total_samples, uint8_t* out42);
+
 /* ---- measurement aid (bench.py): the clock the chip held over a stretch of the stream ----------------------------------------------------------------
  * slots_dev: device uint64 [16][2], zeroed by the caller. One tiny launch writes {s_memtime (shader cycles), s_memrealtime (100 MHz)} into slot [xcc] for every
  * XCD a wave of it ran on. Between two stamps A, B on one stream: held clock = (B.memtime - A.memtime) / (B.memrealtime - A.memrealtime) x 100 MHz per XCD
