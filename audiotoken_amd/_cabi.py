@@ -97,6 +97,10 @@ SIGNATURES = {
     "at_encodec_decode_stream_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "at_encodec_decode_stream_checked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "at_encodec_stream_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_encodec_stream_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "at_encodec_decode_stream_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_encodec_decode_stream_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "at_w2vbert_create": (C.c_void_p, [C.c_int]),
     "at_w2vbert_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "at_w2vbert_finalize": (C.c_int, [C.c_void_p]),

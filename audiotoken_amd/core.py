@@ -128,6 +128,14 @@ class AudioToken:
         self.load_encoder()
         return self.encoder.new_stream(batch)
 
+    def stream_pool(self, slots: int = 1):
+        """Up to ``slots`` acoustic streams that start and finish on their own (``AcousticStreamPool``: ``open`` / ``push({id: samples})`` / ``flush`` /
+        ``close``), batched per call by phase and length. Acoustic only, as ``stream()``."""
+        if self.tokenizer_name != Tokenizers.acoustic:
+            raise ValueError(f"streaming is available for Tokenizers.acoustic only (EnCodec is causal); {self.tokenizer_name} has no streaming form")
+        self.load_encoder()
+        return self.encoder.new_stream_pool(slots)
+
     def encode(self, audio: Union[torch.Tensor, np.ndarray, os.PathLike, bytes, Path], chunk_size: Optional[int] = None,
                stream: bool = False) -> torch.Tensor:
         """core.py:120-185. ``(1, num_samples)`` array/tensor or a path -> tokens ``(1, K, T)`` on the CPU
@@ -248,7 +256,7 @@ class AudioToken:
 
     def encode_batch_files(self, batch_size: int, outdir: os.PathLike, chunk_size: int = 30, num_workers: int = 12,
                            audio_files: Optional[List[os.PathLike]] = None, audio_dir: Optional[Union[os.PathLike, Path]] = None,
-                           **dataloader_kwargs) -> None:
+                           stream: bool = False, **dataloader_kwargs) -> None:
         """core.py:198-289. Files -> ``chunk_size``-second segments -> batches -> encoder -> per-row trimmed
         ``<stem>.npy`` (append semantics as in the reference). ``num_workers`` files are decoded ahead of the device, in order (the reference's
         DataLoader workers; 0 = inline). On a HIP device, for the tokenizers without a host-side transform (acoustic, semantic_m), the samples never become
@@ -257,7 +265,14 @@ class AudioToken:
         resampling conv1d) releases the GIL — or spawned worker PROCESSES with ``worker_processes=True`` (the reference's arrangement; archives are always
         streamed by a thread). Under ``torch.distributed`` every rank takes whole files, balanced by size (distributed.shard_by_size): all chunks of a file stay
         on one rank, preserving the append order (``shard_across_ranks=False``: this rank takes every file it was given — for callers that have already
-        split the work, e.g. one directory per rank)."""
+        split the work, e.g. one directory per rank).
+        ``stream=True`` (acoustic only): every file is ONE clip — its token file is the ``[K, ceil(N / 320)]`` that
+        ``encode(path, chunk_size, stream=True)`` returns, not the concatenation of per-chunk clips. Up to ``batch_size`` files are live at once, one slot of
+        a stream pool each; per tick every live file pushes its next ``chunk_size`` seconds and the new frames are appended to its ``.npy``. A file that is
+        not at the model's rate is still resampled chunk by chunk (``process_audio_chunks``), so its resampling seams remain: for such a file "the whole
+        file" means the concatenated resampled chunks. Plain audio files only: an archive is recorded in ``skipped_files``."""
+        if stream and self.tokenizer_name != Tokenizers.acoustic:
+            raise ValueError(f"streaming is available for Tokenizers.acoustic only (EnCodec is causal); {self.tokenizer_name} has no streaming form")
         self.load_encoder()
         self.skipped_files = []
         assert audio_files or audio_dir, "Either audio_files or audio_dir must be provided"
@@ -267,7 +282,10 @@ class AudioToken:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dataloader_kwargs.get("shard_across_ranks", True):
             files = self._shard_files(files)
-        self._encode_files(files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs)
+        if stream:
+            self._encode_files_streamed(files, int(batch_size), outdir, chunk_size, int(num_workers), audio_files, audio_dir)
+        else:
+            self._encode_files(files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs)
 
     @staticmethod
     def _input_files(audio_files, audio_dir, exts=None) -> List[str]:
@@ -418,6 +436,101 @@ class AudioToken:
                 logger.error(f"encode_batch_files: end-of-run bookkeeping failed: {type(e).__name__}: {e}")
         rt["total_s"] = time.time() - start_time
         logger.debug(f"Encoding batch files took: {time.time() - start_time:.2f}s")
+        if self.skipped_files:
+            logger.error(f"encode_batch_files: {len(self.skipped_files)} input(s) were skipped and have NO token file (AudioToken.skipped_files): "
+                         + "; ".join(f"{p} ({why})" for p, why in self.skipped_files[:8]) + (" ..." if len(self.skipped_files) > 8 else ""))
+
+    def _encode_files_streamed(self, files, batch_size: int, outdir, chunk_size, num_workers: int, audio_files, audio_dir) -> None:
+        """``encode_batch_files(stream=True)``: ticks over a stream pool (writer.plan_encode_stream_ticks). A tick: every live file's next chunk is pushed,
+        the files whose chunks are exhausted are flushed (their slots go to the next files, in order), the tick's new frames come to the host in ONE copy
+        and are appended to the token files."""
+        from .audio_io import AudioDecodeError, process_audio_chunks
+        from .configs import AudioConfig
+        from .prefetch import ordered_map
+        from .writer import plan_encode_stream_ticks
+        start_time = time.time()
+        sr, rate = self.model_config.model_sample_rate, self.model_config.model_token_rate
+        self.feeder_timings = None
+        rt = self.run_timings = {"stage_s": 0.0, "encode_call_s": 0.0, "device_wait_s": 0.0, "save_s": 0.0, "batches": 0, "rows": 0}
+
+        def skipped(name, why):
+            logger.error(f"Skipping {name}: {why}")
+            self.skipped_files.append((name, why))
+
+        def load(path: str):
+            """One file's chunks, decoded ``num_workers`` files ahead: (path, [samples [n] per chunk] or None, reason)."""
+            if not path.endswith(AUDIO_EXTS):
+                return path, None, ("stream=True takes plain audio files: archives are not streamed" if path.endswith(TAR_EXTS + ZIP_EXTS)
+                                    else "unsupported extension")
+            try:
+                return path, [chunk[0] for chunk, _ in process_audio_chunks(path, sr, chunk_size)], None
+            except AudioDecodeError as e:
+                return path, None, str(e)
+
+        opened: list = []     # position in the tick plan -> [path, chunks]
+
+        def chunk_counts():
+            for path, chunks, why in ordered_map(load, [str(f) for f in files], num_workers):
+                if chunks is None:
+                    skipped(path, why)
+                elif sum(int(c.shape[-1]) for c in chunks) < 321:   # the library's rule for a clip (a stream whose first push is its last is a one-shot encode)
+                    skipped(path, "fewer than 321 samples")
+                else:
+                    opened.append([path, chunks])
+                    yield [int(c.shape[-1]) for c in chunks]
+
+        def save(path: str, codes: torch.Tensor):
+            pointer = AudioConfig(file_name=path, length_seconds=codes.shape[-1] / rate, model_token_rate=rate)
+            if audio_files is not None:
+                save_audio_tokens(codes, pointer, str(outdir))
+            else:
+                save_rel_audio_tokens(codes, pointer, str(outdir), str(audio_dir))
+
+        pool = self.encoder.new_stream_pool(batch_size)
+        sids: dict = {}
+        try:
+            ticks = plan_encode_stream_ticks(chunk_counts(), batch_size)
+            while True:
+                t0 = time.perf_counter()
+                tick = next(ticks, None)        # opens (waits for) the files that take the free slots
+                if tick is None:
+                    break
+                feed = {}
+                for r in tick:
+                    if r.file not in sids:
+                        sids[r.file] = pool.open()
+                    chunks = opened[r.file][1]
+                    feed[sids[r.file]], chunks[r.t0] = chunks[r.t0], None
+                t1 = time.perf_counter()
+                out = pool.push(feed)           # every group's status word is read in there: the tokens are verified when it returns
+                last = [r.file for r in tick if r.last]
+                fin = pool.flush([sids[i] for i in last]) if last else {}
+                t2 = time.perf_counter()
+                parts = []
+                for r in tick:
+                    sid = sids[r.file]
+                    parts.append(torch.cat([out[sid], fin[sid]], dim=-1) if sid in fin else out[sid])
+                host = torch.cat(parts, dim=-1).cpu()   # ONE device-to-host copy per tick
+                t3 = time.perf_counter()
+                pos = 0
+                for r, p in zip(tick, parts):
+                    t = p.shape[-1]
+                    if t:
+                        save(opened[r.file][0], host[:, pos:pos + t])
+                    pos += t
+                for i in last:
+                    del sids[i]
+                    opened[i] = None
+                t4 = time.perf_counter()
+                rt["stage_s"] += t1 - t0; rt["encode_call_s"] += t2 - t1; rt["device_wait_s"] += t3 - t2; rt["save_s"] += t4 - t3
+                rt["batches"] += 1; rt["rows"] += len(tick)
+        finally:
+            try:
+                self._end_of_run()
+                self.run_summary["library_pushes"] = pool.library_pushes
+            except Exception as e:   # bookkeeping must not mask the exception that ended the run
+                logger.error(f"encode_batch_files: end-of-run bookkeeping failed: {type(e).__name__}: {e}")
+        rt["total_s"] = time.time() - start_time
         if self.skipped_files:
             logger.error(f"encode_batch_files: {len(self.skipped_files)} input(s) were skipped and have NO token file (AudioToken.skipped_files): "
                          + "; ".join(f"{p} ({why})" for p, why in self.skipped_files[:8]) + (" ..." if len(self.skipped_files) > 8 else ""))
@@ -573,6 +686,14 @@ class AudioToken:
         self.load_decoder(**kwargs)
         return self.decoder.new_stream(batch)
 
+    def decode_stream_pool(self, slots: int = 1, **kwargs):
+        """Up to ``slots`` acoustic decode streams that start and finish on their own (``AcousticDecodeStreamPool``), batched per call by phase, K and
+        number of frames. Acoustic only, as ``decode_stream()``."""
+        if self.tokenizer_name != Tokenizers.acoustic:
+            raise ValueError(f"streaming decode is available for Tokenizers.acoustic only; {self.tokenizer_name} has no streaming form")
+        self.load_decoder(**kwargs)
+        return self.decoder.new_stream_pool(slots)
+
     def decode(self, tokens: Union[torch.Tensor, np.ndarray, os.PathLike, Path], chunk_size: Optional[int] = None, stream: bool = False,
                **kwargs) -> torch.Tensor:
         """core.py:317-353: tokens ``(B, K, T)`` -> audio ``(1, B*320*T)`` on the CPU.
@@ -608,7 +729,7 @@ class AudioToken:
 
     def decode_batch_files(self, batch_size: int, outdir: os.PathLike, chunk_size: Optional[int] = 30, num_workers: int = 12,
                            token_files: Optional[List[os.PathLike]] = None, token_dir: Optional[Union[os.PathLike, Path]] = None,
-                           rescale: bool = False, audio_format: str = "wav", **kwargs) -> None:
+                           rescale: bool = False, audio_format: str = "wav", stream: bool = False, **kwargs) -> None:
         """The way back from ``encode_batch_files`` (reference scripts/detokenize_audio.py + utils.save_audio): ``.npy`` token files -> mono 16-bit PCM
         WAV files at 24 kHz, or with ``audio_format="flac"`` FLAC files of the same samples (``<stem>.flac``; compressed on the device, csrc/flac_encode.hip;
         anything but "wav" / "flac" raises ValueError before a decoder is loaded). Acoustic only. ``token_dir`` is walked once (sorted, dot-names skipped) and its relative tree is kept; ``token_files`` are
@@ -621,7 +742,10 @@ class AudioToken:
         of a file stay on the device until its last row is decoded; a file holding more than ``max_held_bytes`` is skipped), rounded half to even and
         narrowed to int16 on the device (writer.py; ``device_writer=False`` converts on the host by the same rule). ``num_workers`` files are read ahead, in
         order. Under ``torch.distributed`` whole files are sharded by size (``shard_across_ranks=False``: this rank takes every file it was given).
-        ``self.run_summary`` / ``self.run_timings`` describe the run (``run_summary["audio_bytes"]``: the bytes of the files written)."""
+        ``self.run_summary`` / ``self.run_timings`` describe the run (``run_summary["audio_bytes"]``: the bytes of the files written).
+        ``stream=True``: the way back from ``encode_batch_files(stream=True)`` — every token file is decoded as ONE clip (what
+        ``decode(tokens, chunk_size, stream=True)`` returns for it), up to ``batch_size`` files at a time through a decode stream pool, ``chunk_size * 75``
+        frames per file and tick; outputs, skipping rules and ``rescale`` are those above."""
         from . import writer as Wr
         if audio_format not in Wr.AUDIO_FORMATS:
             raise ValueError(f"audio_format must be one of {Wr.AUDIO_FORMATS}, got {audio_format!r}")
@@ -650,7 +774,7 @@ class AudioToken:
         on_gpu = torch.device(self.device).type == "cuda"
         Wr.decode_files(self, inputs, int(batch_size), chunk_size, int(num_workers), bool(rescale), bool(kwargs.get("device_writer", on_gpu)),
                         int(kwargs.get("max_held_bytes", Wr.DEFAULT_MAX_HELD_BYTES)), self.model_config.model_sample_rate, self.model_config.model_token_rate,
-                        audio_format)
+                        audio_format, bool(stream))
 
     def _decode_single(self, tokens: torch.Tensor) -> torch.Tensor:
         """core.py:355-359."""

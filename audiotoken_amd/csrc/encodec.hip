@@ -1656,6 +1656,61 @@ int at_encodec_decode_stream_checked(at_encodec_t* h, const void* state_in, void
     return 0;
 }
 
+// Stream pools (stream_pool.hip): rows of a state moved between a pool of S slots and a staging state of B rows. Everything is checked on the host,
+// from the caller's host copy of the slot list, before the device is touched.
+namespace {
+const int kEncPlaneWidths[] = {kStreamCtx, kH, kH, kH, kH, kStreamHist * kH};   // StreamState: ctx, h0, c0, h1, c1, yhist
+const int kDecPlaneWidths[] = {kDecHist * kDim, kH, kH, kH, kH, kDecCtx * kH};  // DecStreamState: zhist, h0, c0, h1, c1, yctx
+
+int stream_pool_copy(at_encodec_t* h, bool decode, bool gather, const void* pool, int S, const void* state, int B, const int32_t* slots_dev,
+                     const int32_t* slots_host, at_stream_t stream) {
+    AT_REQUIRE(h && h->finalized && (!decode || h->has_decoder), decode ? "model not finalized with a decoder" : "model not finalized");
+    AT_REQUIRE(pool && state && slots_dev && slots_host, "stream pool: null pool, state or slot list");
+    AT_REQUIRE(pool != state, "stream pool: the staging state and the pool must be two buffers");
+    AT_REQUIRE(B >= 1 && B <= S, "stream pool: need 1 <= B <= S");
+    const auto pit = h->streams.find(pool);
+    AT_REQUIRE(pit != h->streams.end() && pit->second.B == S && pit->second.decode == decode,
+               "stream pool: the pool was not reset for S streams of this direction by this handle (at_encodec_stream_reset / at_encodec_decode_stream_reset)");
+    at_encodec::StreamInfo note;
+    if (!gather) {
+        const auto sit = h->streams.find(state);
+        AT_REQUIRE(sit != h->streams.end(), "stream pool: state_in was neither reset nor written by a push or a gather of this handle");
+        note = sit->second;
+        AT_REQUIRE(note.B == B && note.decode == decode, "stream pool: state_in is a state of another B or direction");
+        AT_REQUIRE(!note.finished, "stream pool: state_in is a finished stream's state");
+    }
+    if (int rc = check_pool_slots(slots_host, B, S)) return rc;
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    const int* widths = decode ? kDecPlaneWidths : kEncPlaneWidths;
+    if (int rc = launch_stream_pool_copy(gather ? pool : state, const_cast<void*>(gather ? state : pool), slots_dev, widths, 6, B, S, gather, (hipStream_t)stream)) return rc;
+    if (gather) {   // the staging state now holds B streams in mid-stream: the push accepts it as such
+        note.B = B;
+        note.started = true;
+        note.decode = decode;
+        h->streams[state] = note;
+    }
+    return 0;
+}
+}  // namespace
+
+int at_encodec_stream_gather(at_encodec_t* h, const void* pool, int S, const int32_t* slots_dev, const int32_t* slots_host, int B, void* state_out,
+                             at_stream_t stream) {
+    return stream_pool_copy(h, false, true, pool, S, state_out, B, slots_dev, slots_host, stream);
+}
+int at_encodec_stream_scatter(at_encodec_t* h, const void* state_in, int B, const int32_t* slots_dev, const int32_t* slots_host, void* pool, int S,
+                              at_stream_t stream) {
+    return stream_pool_copy(h, false, false, pool, S, state_in, B, slots_dev, slots_host, stream);
+}
+int at_encodec_decode_stream_gather(at_encodec_t* h, const void* pool, int S, const int32_t* slots_dev, const int32_t* slots_host, int B, void* state_out,
+                                    at_stream_t stream) {
+    return stream_pool_copy(h, true, true, pool, S, state_out, B, slots_dev, slots_host, stream);
+}
+int at_encodec_decode_stream_scatter(at_encodec_t* h, const void* state_in, int B, const int32_t* slots_dev, const int32_t* slots_host, void* pool, int S,
+                                     at_stream_t stream) {
+    return stream_pool_copy(h, true, false, pool, S, state_in, B, slots_dev, slots_host, stream);
+}
+
 int at_op_gemm(const at_gemm_desc* d, at_stream_t stream) {
     AT_REQUIRE(d != nullptr, "null descriptor");
     GemmArgs a;

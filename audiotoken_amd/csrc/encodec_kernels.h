@@ -223,4 +223,12 @@ struct StreamDecStateArgs {
 };
 int launch_stream_dec_state(const StreamDecStateArgs& a, hipStream_t stream);
 
+// Stream pools (stream_pool.hip). A stream state is a list of n_planes planes [rows][widths[p]] floats that follow each other (widths multiples of 4);
+// gather: row b of every plane of dst (a B-row state) = row slots_dev[b] of src's plane (an S-row pool); scatter (gather = false): row slots_dev[b] of
+// dst's plane (the pool) = row b of src's (the B-row state), the pool's other rows untouched. The caller has checked the slots on the host.
+constexpr int kPoolMaxPlanes = 6;
+// host only: slots_host holds B distinct slots in [0, S), 1 <= B <= S (reads exactly B entries); 0, or -1 with the error text set
+int check_pool_slots(const int32_t* slots_host, int B, int S);
+int launch_stream_pool_copy(const void* src, void* dst, const int* slots_dev, const int* widths, int n_planes, int B, int S, bool gather, hipStream_t stream);
+
 }  // namespace at

@@ -58,3 +58,9 @@ class AcousticDecoder(_EncodecCallable):
         one-shot ``forward`` gives for the concatenated tokens, in memory bounded by the largest push. Streams of one decoder are independent."""
         from .streaming import AcousticDecodeStream
         return AcousticDecodeStream(self, batch)
+
+    def new_stream_pool(self, slots: int = 1):
+        """Up to ``slots`` decode streams that start and finish on their own (audiotoken_amd/streaming.py, AcousticDecodeStreamPool); the streams of
+        one call with the same phase, K and number of frames share one library push."""
+        from .streaming import AcousticDecodeStreamPool
+        return AcousticDecodeStreamPool(self, slots)

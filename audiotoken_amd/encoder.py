@@ -169,6 +169,12 @@ class AcousticEncoder(_EncodecCallable):
         from .streaming import AcousticStream
         return AcousticStream(self, batch)
 
+    def new_stream_pool(self, slots: int = 1):
+        """Up to ``slots`` streams that start and finish on their own (audiotoken_amd/streaming.py, AcousticStreamPool): each gives the tokens of its
+        own audio, and the streams of one call that are in the same phase with the same length share one library push."""
+        from .streaming import AcousticStreamPool
+        return AcousticStreamPool(self, slots)
+
 
 # ======================================================================================================
 # semantic_m: Wav2Vec2-BERT + VQ

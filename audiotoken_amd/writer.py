@@ -148,6 +148,44 @@ def plan_batches(files: Iterable[Tuple[int, int, int]], batch_size: int, chunk_f
         yield BatchPlan(K_open, rows).finish()
 
 
+def plan_ticks(lengths: Iterable[int], batch_size: int, step: Optional[int]) -> Iterator[List[SegmentRow]]:
+    """The tick plan of a streamed run, shared by both directions: ``lengths`` = units per file in order (frames of a token file, chunks of
+    an audio file), at most ``batch_size`` files live at once, every live file contributes its next ``step`` units per tick (None: all of them). A file
+    whose units are exhausted leaves with that tick, and its place goes to the next file at the start of the next one. A tick is the list of its rows in
+    file order; ``SegmentRow.file`` counts the files from 0. Lazy: the next length is read only when a place is free."""
+    assert batch_size >= 1 and (step is None or step >= 1)
+    it = enumerate(lengths)
+    live: List[list] = []     # [file, units, position]
+    while True:
+        while len(live) < batch_size:
+            nxt = next(it, None)
+            if nxt is None:
+                break
+            assert nxt[1] >= 1, "a file without units has no tick"
+            live.append([nxt[0], int(nxt[1]), 0])
+        if not live:
+            return
+        tick = []
+        for f in live:
+            valid = f[1] - f[2] if step is None else min(step, f[1] - f[2])
+            tick.append(SegmentRow(f[0], f[2], valid, f[2] + valid == f[1]))
+            f[2] += valid
+        live = [f for f in live if f[2] < f[1]]
+        yield tick
+
+
+def plan_stream_ticks(files: Iterable[Tuple[int, int]], batch_size: int, chunk_frames: Optional[int]) -> Iterator[List[SegmentRow]]:
+    """``decode_batch_files(stream=True)``: ``files`` = (K, T) in order -> ticks of (file, first frame, frames, last). K plays no part in who is live: the
+    pool forms one group per (phase, K, frames) inside a tick."""
+    return plan_ticks((T for _, T in files), batch_size, chunk_frames)
+
+
+def plan_encode_stream_ticks(files: Iterable[Sequence[int]], batch_size: int) -> Iterator[List[SegmentRow]]:
+    """``encode_batch_files(stream=True)``: ``files`` = the sample counts of every file's chunks, known once the file is opened -> ticks of (file, chunk
+    index, 1, last): one chunk per live file and tick."""
+    return plan_ticks((len(chunks) for chunks in files), batch_size, 1)
+
+
 def padded_tokens(plan: BatchPlan, tokens_of) -> torch.Tensor:
     """The ``[B, K, t_max]`` int64 batch of a plan, rows right-padded with ``PAD_CODE``; ``tokens_of(file id)`` = that file's ``[K, T]`` array."""
     out = np.full((len(plan.rows), plan.K, plan.t_max), PAD_CODE, dtype=np.int64)
@@ -563,9 +601,14 @@ class _File:
 
 
 def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_size, num_workers: int, rescale: bool, device_writer: bool,
-                 max_held_bytes: int, sample_rate: int, token_rate: int, audio_format: str = "wav") -> None:
+                 max_held_bytes: int, sample_rate: int, token_rate: int, audio_format: str = "wav", stream: bool = False) -> None:
     """The loop of ``AudioToken.decode_batch_files``: ``inputs`` = (token file, output path) in order. ``tok`` supplies ``decoder`` (``forward`` /
-    ``verified``), ``device``, ``skipped_files``; ``run_summary`` / ``run_timings`` are left on it."""
+    ``verified``), ``device``, ``skipped_files``; ``run_summary`` / ``run_timings`` are left on it.
+
+    ``stream=True``: every file is ONE clip. Up to ``batch_size`` files are live, one slot of a decode stream pool each
+    (``decoder.new_stream_pool``); per tick (``plan_stream_ticks``) every live file pushes its next ``chunk_size * 75`` frames and the pool batches the rows of
+    equal phase, K and length. The audio of a tick goes through the same writers as a batch's; a file below 7 frames is padded with ``PAD_CODE`` and
+    trimmed, as the segments of the chunked route are."""
     start_time = time.time()
     dec = tok.decoder
     device = torch.device(tok.device)
@@ -614,7 +657,7 @@ def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_
                 f.writer = None
             skipped(f.path, why)
 
-    plans = plan_batches(valid_files(), batch_size, chunk_frames_of(chunk_size, token_rate))
+    plans = plan_batches(valid_files() if not stream else (), batch_size, chunk_frames_of(chunk_size, token_rate))   # (the streamed run has ticks instead)
     held: List[list] = []       # [plan, float rows (device tensor / host array)] decoded but not packed: rescale=True waits for the last row of a file
     pending: List[tuple] = []   # (plan rows packed, _Packed): packed, on their way to the host, not yet written
 
@@ -648,8 +691,8 @@ def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_
         """Pack every held batch whose files are all complete (clamp mode: every batch, at once), in order."""
         while held:
             plan, rows_f = held[0]
-            last = files[plan.rows[-1].file]
-            if rescale and last.rows_left > 0 and not last.dropped:
+            # (batches are in file order, so only the LAST row's file can be incomplete; a tick of a streamed run has a row of every live file)
+            if rescale and any(files[r.file].rows_left > 0 and not files[r.file].dropped for r in (plan.rows if stream else plan.rows[-1:])):
                 break
             held.pop(0)
             keep, pack_rows, pos = [], [], 0
@@ -665,6 +708,71 @@ def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_
             for r in plan.rows:
                 if r.last:      # (no later batch holds a row of it)
                     files[r.file].tokens = None
+
+    def run_ticks():
+        """The streamed run. A tick: upload and push the live files' next frames (the pool reads every group's status word: the audio is verified when
+        ``push`` returns), write what the ticks before packed, then hold / pack this tick's audio as a batch's."""
+        pool = dec.new_stream_pool(batch_size)
+        order: List[int] = []      # position in the tick plan -> file id
+
+        def shapes():
+            for i, K, T in valid_files():
+                order.append(i)
+                yield K, T
+
+        sids: dict = {}
+        for tick in plan_stream_ticks(shapes(), batch_size, chunk_frames_of(chunk_size, token_rate)):
+            t0 = time.perf_counter()
+            rows, feed, trim = [], {}, {}
+            for r in tick:
+                i = order[r.file]
+                f = files[i]
+                f.rows_left -= 1
+                if f.dropped:
+                    if i in sids:
+                        pool.close(sids.pop(i))
+                    continue
+                if i not in sids:
+                    sids[i] = pool.open()
+                x = f.tokens[:, r.t0:r.t0 + r.valid]
+                if r.last and r.t0 + r.valid < MIN_FRAMES:     # the whole file is below a first push's 7 frames: "no code" frames behind it, cut off again below
+                    trim[i] = HOP * (r.t0 + r.valid)
+                    x = np.concatenate([x, np.full((x.shape[0], MIN_FRAMES - (r.t0 + r.valid)), PAD_CODE, dtype=np.int64)], axis=1)
+                feed[sids[i]] = torch.from_numpy(np.ascontiguousarray(x))
+                rows.append(SegmentRow(i, r.t0, r.valid, r.last))
+            t1 = time.perf_counter()
+            out = pool.push(feed) if feed else {}
+            outs = [out[sids[r.file]][:trim.get(r.file)] for r in rows]
+            done = [sids.pop(r.file) for r in rows if r.last]
+            if done:
+                pool.flush(done)                                # started streams hold nothing: this frees their slots
+            t2 = time.perf_counter()
+            write_pending()
+            t3 = time.perf_counter()
+            emitted = [(r, o) for r, o in zip(rows, outs) if o.numel() > 0]    # (a file's first ticks emit nothing while it holds fewer than 7 frames)
+            if emitted:
+                plan = BatchPlan(0, [r for r, _ in emitted])
+                plan.n = [int(o.numel()) for _, o in emitted]
+                plan.src_off = plan.dst_off = [sum(plan.n[:b]) for b in range(len(plan.n))]
+                plan.total = sum(plan.n)
+                rows_f = backend.hold(torch.cat([o for _, o in emitted]))
+                if rescale:
+                    pk = backend.peaks(rows_f, [(plan.src_off[b], 0, plan.n[b], 1.0) for b in range(len(plan.rows))])
+                    for b, r in enumerate(plan.rows):
+                        f = files[r.file]
+                        f.peak = max(f.peak, np.float32(pk[b]))
+                        f.held_bytes += 4 * plan.n[b]
+                        if f.held_bytes > max_held_bytes:
+                            drop(f, f"rescale=True holds the file's float rows on the device until its last row: more than max_held_bytes = {max_held_bytes}")
+                held.append([plan, rows_f])
+                del rows_f
+            del out, outs, emitted
+            release_held()
+            t4 = time.perf_counter()
+            rt["stage_s"] += t1 - t0; rt["encode_call_s"] += t2 - t1; rt["save_s"] += t3 - t2; rt["device_wait_s"] += t4 - t3
+            rt["batches"] += 1; rt["rows"] += len(rows)
+            summary["batches"] += 1; summary["segments"] += len(rows)
+        summary["library_pushes"] = pool.library_pushes
 
     ok = False
     try:
@@ -702,6 +810,8 @@ def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_
             rt["batches"] += 1; rt["rows"] += len(plan.rows)
             summary["batches"] += 1; summary["segments"] += len(plan.rows)
             plan, toks = nxt, nxt_toks
+        if stream:
+            run_ticks()
         t0 = time.perf_counter()
         write_pending()
         rt["save_s"] += time.perf_counter() - t0

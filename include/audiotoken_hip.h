@@ -202,6 +202,36 @@ size_t at_encodec_decode_stream_workspace_bytes(const at_encodec_t* h, int B, in
 int at_encodec_decode_stream_checked(at_encodec_t* h, const void* state_in, void* state_out, const int64_t* codes_new, int B, int K, int t_new,
                                      float* wav_out, void* workspace, size_t workspace_bytes, at_stream_t stream, uint32_t* status_dev);
 
+/* ---- stream pools: rows of a stream state that start and finish on their own ---------------------------------------------
+ * The B rows of one push advance in lockstep, but WHICH streams form those rows may change from push to push. A pool is an ordinary stream state for S
+ * streams (at_encodec_stream_state_bytes(h, S) / at_encodec_decode_stream_state_bytes(h, S) bytes, zeroed and made known to the handle by the matching
+ * *_stream_reset with B = S); stream i lives in row ("slot") i of every plane of the state. The pushes themselves are unchanged: they run on staging states
+ * of B rows, and two copies move rows between the pool and the staging states.
+ *   gather    row b of every plane of state_out (a B-stream state, *_stream_state_bytes(h, B) bytes) = row slots[b] of the pool's plane. The handle notes
+ *             state_out as (B, started, not finished), so the next push accepts it as a mid-stream state.
+ *   scatter   the inverse, from a state this handle knows (reset, gathered or written by a push) that is not finished: row slots[b] of the pool's planes =
+ *             row b of state_in's. The pool's other rows are not touched.
+ *   slots     B distinct slots in [0, S), given twice: slots_host (host memory) is what the call validates, slots_dev (device int32 [B], uploaded by the
+ *             caller as the feeder uploads its descriptors) is what the kernel reads. The two must hold the same numbers; the kernel skips a row whose
+ *             device slot lies outside [0, S).
+ * TRANSACTION RULE for the pool: gather(pool -> staging_in); push staging_in -> staging_out with the unchanged *_stream_checked; read the status word and,
+ * when it is non-zero, repeat the push from staging_in as for any stream; only after a push that succeeded scatter(staging_out -> pool). A failed push
+ * therefore never reaches the pool. Rows that start a stream need no gather (reset the staging state instead), rows on their final encode push no scatter
+ * (the slot is free afterwards). Streams that are pushed together through a pool give bit for bit what the same rows give as one lockstep stream of B: the
+ * copies are exact and the push is the same call.
+ * Each call is stream-ordered, one launch of a pure copy kernel (23 040 bytes per encode stream, 15 360 per decode stream), and neither synchronises nor
+ * allocates device memory. Argument errors (a null pointer, B < 1, B > S, a slot outside [0, S), a duplicate slot, a pool this handle did not reset for S
+ * streams of that direction, a state_in it does not know or of another B or direction or finished, state == pool) return non-zero with at_last_error set;
+ * nothing is launched and the device stays usable. */
+int at_encodec_stream_gather(at_encodec_t* h, const void* pool, int S, const int32_t* slots_dev, const int32_t* slots_host, int B, void* state_out,
+                             at_stream_t stream);
+int at_encodec_stream_scatter(at_encodec_t* h, const void* state_in, int B, const int32_t* slots_dev, const int32_t* slots_host, void* pool, int S,
+                              at_stream_t stream);
+int at_encodec_decode_stream_gather(at_encodec_t* h, const void* pool, int S, const int32_t* slots_dev, const int32_t* slots_host, int B, void* state_out,
+                                    at_stream_t stream);
+int at_encodec_decode_stream_scatter(at_encodec_t* h, const void* state_in, int B, const int32_t* slots_dev, const int32_t* slots_host, void* pool, int S,
+                                     at_stream_t stream);
+
 /* ---- semantic_m tokenizer: log-mel front-end + Wav2Vec2-BERT conformer + LayerNorm + VQ ------------------
  * Replaces reference Wav2VecBertEncoder (audiotoken/encoder.py:111-186): ctor = Wav2VecBertProcessor +
  * Wav2Vec2BertModel.from_pretrained + VectorQuantize(dim=1024, codebook_size=2048) (:112-161); forward =
