@@ -29,6 +29,13 @@ class SegmentDesc(C.Structure):
 PCM_S16, PCM_S32, PCM_F32, PCM_U8 = 0, 1, 2, 3
 
 
+class ResampleRow(C.Structure):
+    """Mirror of ``at_resample_row`` (include/audiotoken_hip.h): one row of at_resample_rows."""
+    _fields_ = [("pcm", C.c_void_p), ("table", C.c_void_p), ("src_base", C.c_int64), ("src_len", C.c_int64), ("src_total", C.c_int64),
+                ("out_start", C.c_int64), ("out_len", C.c_int32), ("fmt", C.c_int32), ("scale", C.c_float), ("o", C.c_int32), ("n", C.c_int32),
+                ("width", C.c_int32), ("final", C.c_int32), ("reserved", C.c_int32), ("dst_off", C.c_int64)]
+
+
 class PcmRowDesc(C.Structure):
     """Mirror of ``at_pcm_row_desc`` (include/audiotoken_hip.h): one row of at_pcm_peaks / at_pcm_pack."""
     _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("n", C.c_int64), ("scale", C.c_float), ("reserved", C.c_int32)]
@@ -152,6 +159,8 @@ SIGNATURES = {
     "at_hubert_range_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
     "at_segments_from_pcm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "at_clock_stamp": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "at_resample_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_resample_rows_check": (C.c_int, [C.c_void_p, C.c_int]),
     "at_segments_zmuv_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "at_segments_from_pcm_zmuv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "at_pcm_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),

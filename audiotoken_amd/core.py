@@ -120,31 +120,39 @@ class AudioToken:
             x = D.probe_batch(self.model_config.model_sample_rate, self.device, self.transform_func)
             self.rank_probe = D.ranks_agree_on_probe(lambda w: self.encoder(w, torch.ones_like(w)), x, dev, dist, str(self.tokenizer_name))
 
-    def stream(self, batch: int = 1):
+    def stream(self, batch: int = 1, sample_rate: Optional[int] = None):
         """A streaming acoustic encoder (``AcousticStream``: ``push`` / ``flush`` / ``reset``) for audio that arrives in pieces; the concatenated
-        tokens are those of one-shot ``encode``. The semantic tokenizers are not causal and have no streaming form."""
+        tokens are those of one-shot ``encode``. The semantic tokenizers are not causal and have no streaming form.
+        ``sample_rate``: ``push`` takes raw samples at that rate (float32 or int16, torch or numpy); they are resampled on the device as ONE signal
+        (DESIGN.md §16), so the tokens are those of the whole signal resampled once, whatever the pushes. None: float samples at the model's rate."""
         if self.tokenizer_name != Tokenizers.acoustic:
             raise ValueError(f"streaming is available for Tokenizers.acoustic only (EnCodec is causal); {self.tokenizer_name} has no streaming form")
         self.load_encoder()
-        return self.encoder.new_stream(batch)
+        return self.encoder.new_stream(batch) if sample_rate is None else self.encoder.new_stream(batch, sample_rate=sample_rate)
 
     def stream_pool(self, slots: int = 1):
         """Up to ``slots`` acoustic streams that start and finish on their own (``AcousticStreamPool``: ``open`` / ``push({id: samples})`` / ``flush`` /
-        ``close``), batched per call by phase and length. Acoustic only, as ``stream()``."""
+        ``close``), batched per call by phase and length. Acoustic only, as ``stream()``. ``open(sample_rate=r)`` opens a stream that is pushed raw
+        samples at ``r`` Hz; streams of different rates in one call share one resample launch."""
         if self.tokenizer_name != Tokenizers.acoustic:
             raise ValueError(f"streaming is available for Tokenizers.acoustic only (EnCodec is causal); {self.tokenizer_name} has no streaming form")
         self.load_encoder()
         return self.encoder.new_stream_pool(slots)
 
     def encode(self, audio: Union[torch.Tensor, np.ndarray, os.PathLike, bytes, Path], chunk_size: Optional[int] = None,
-               stream: bool = False) -> torch.Tensor:
+               stream: bool = False, resample: str = "chunk") -> torch.Tensor:
         """core.py:120-185. ``(1, num_samples)`` array/tensor or a path -> tokens ``(1, K, T)`` on the CPU
         (``(K, sum T)`` when a path is encoded with ``chunk_size`` — the reference drops the batch dim there).
         ``stream=True`` with a path and ``chunk_size`` (acoustic only) pushes the chunks through ONE stream instead of encoding each as a clip of
-        its own: the result is the whole file's ``(1, K, ceil(N/320))`` in the memory of one chunk."""
+        its own: the result is the whole file's ``(1, K, ceil(N/320))`` in the memory of one chunk. A file that is not at the model's rate is resampled
+        chunk by chunk on the host with ``resample="chunk"`` (the reference's seams); ``resample="file"`` (needs ``stream=True``) keeps its PCM on the
+        device and resamples it as ONE signal: the tokens of the whole file resampled once, whatever ``chunk_size``."""
+        self._check_resample(resample, stream)
         if stream:
             if not (isinstance(audio, (os.PathLike, Path)) and chunk_size is not None):
                 raise ValueError("stream=True needs a path and a chunk_size (arrays and whole files are encoded one-shot)")
+            if resample == "file":
+                return self._encode_resident(audio, chunk_size)
             from .audio_io import process_audio_chunks
             st = self.stream(1)
             parts = [st.push(chunk) for chunk, _ in process_audio_chunks(audio, self.model_config.model_sample_rate, chunk_size)]
@@ -171,6 +179,29 @@ class AudioToken:
             raise NotImplementedError("Encoding bytes not supported yet")
         else:
             raise ValueError(f"Unsupported input type {type(audio)}. Should be one of: {np.ndarray, os.PathLike, bytes, Path}")
+
+    @staticmethod
+    def _check_resample(resample, stream: bool) -> None:
+        if resample not in ("chunk", "file"):
+            raise ValueError(f"resample must be 'chunk' (every chunk resampled on its own) or 'file' (the file resampled as one signal), not {resample!r}")
+        if resample == "file" and not stream:
+            raise ValueError("resample='file' needs stream=True: only a streamed encode carries a file across its chunks")
+
+    def _encode_resident(self, path, chunk_size) -> torch.Tensor:
+        """``encode(path, chunk_size, stream=True, resample="file")``: the file's PCM on the device once, one resample launch and one push per tick."""
+        from .audio_io import AudioDecodeError
+        from .resample_stream import ResidentFiles
+        st = self.stream(1)
+        why = []
+        src = ResidentFiles(self.device, self.model_config.model_sample_rate, chunk_size, 0, lambda name, reason: why.append(reason),
+                            max_file_bytes=self.kwargs.get("max_file_bytes", 4 << 30))
+        files = list(src.open_all([str(path)]))
+        if len(files) != 1:
+            raise AudioDecodeError(why[0] if why else f"{path}: one audio file expected, found {len(files)}")
+        parts = [st.push(src.chunks([(files[0], c)])[0][None]) for c in range(files[0].ticks)]
+        parts.append(st.flush())
+        src.finish()
+        return torch.cat([p.cpu() for p in parts], dim=-1)
 
     def _encode_single(self, audio: torch.Tensor) -> torch.Tensor:
         """core.py:187-196."""
@@ -256,7 +287,7 @@ class AudioToken:
 
     def encode_batch_files(self, batch_size: int, outdir: os.PathLike, chunk_size: int = 30, num_workers: int = 12,
                            audio_files: Optional[List[os.PathLike]] = None, audio_dir: Optional[Union[os.PathLike, Path]] = None,
-                           stream: bool = False, **dataloader_kwargs) -> None:
+                           stream: bool = False, resample: str = "chunk", **dataloader_kwargs) -> None:
         """core.py:198-289. Files -> ``chunk_size``-second segments -> batches -> encoder -> per-row trimmed
         ``<stem>.npy`` (append semantics as in the reference). ``num_workers`` files are decoded ahead of the device, in order (the reference's
         DataLoader workers; 0 = inline). On a HIP device, for the tokenizers without a host-side transform (acoustic, semantic_m), the samples never become
@@ -270,7 +301,12 @@ class AudioToken:
         ``encode(path, chunk_size, stream=True)`` returns, not the concatenation of per-chunk clips. Up to ``batch_size`` files are live at once, one slot of
         a stream pool each; per tick every live file pushes its next ``chunk_size`` seconds and the new frames are appended to its ``.npy``. A file that is
         not at the model's rate is still resampled chunk by chunk (``process_audio_chunks``), so its resampling seams remain: for such a file "the whole
-        file" means the concatenated resampled chunks. Plain audio files only: an archive is recorded in ``skipped_files``."""
+        file" means the concatenated resampled chunks. Plain audio files only: an archive is recorded in ``skipped_files``.
+        ``resample="file"`` (needs ``stream=True``) removes those seams: the device feeder's decoders read the files ahead in their storage
+        format, a live file's PCM stays on the device from its first tick to its flush, and every tick ONE launch resamples the next chunk of every live
+        file at file-global positions — the token file is that of the whole file resampled once. Archive members stream like files. A file whose PCM
+        exceeds ``max_file_bytes`` (keyword, default 4 GiB) or that is not mono is recorded in ``skipped_files``."""
+        self._check_resample(resample, stream)
         if stream and self.tokenizer_name != Tokenizers.acoustic:
             raise ValueError(f"streaming is available for Tokenizers.acoustic only (EnCodec is causal); {self.tokenizer_name} has no streaming form")
         self.load_encoder()
@@ -283,7 +319,8 @@ class AudioToken:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dataloader_kwargs.get("shard_across_ranks", True):
             files = self._shard_files(files)
         if stream:
-            self._encode_files_streamed(files, int(batch_size), outdir, chunk_size, int(num_workers), audio_files, audio_dir)
+            self._encode_files_streamed(files, int(batch_size), outdir, chunk_size, int(num_workers), audio_files, audio_dir, resample,
+                                        dataloader_kwargs.get("max_file_bytes", 4 << 30))
         else:
             self._encode_files(files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs)
 
@@ -440,10 +477,12 @@ class AudioToken:
             logger.error(f"encode_batch_files: {len(self.skipped_files)} input(s) were skipped and have NO token file (AudioToken.skipped_files): "
                          + "; ".join(f"{p} ({why})" for p, why in self.skipped_files[:8]) + (" ..." if len(self.skipped_files) > 8 else ""))
 
-    def _encode_files_streamed(self, files, batch_size: int, outdir, chunk_size, num_workers: int, audio_files, audio_dir) -> None:
+    def _encode_files_streamed(self, files, batch_size: int, outdir, chunk_size, num_workers: int, audio_files, audio_dir, resample: str = "chunk",
+                               max_file_bytes: int = 4 << 30) -> None:
         """``encode_batch_files(stream=True)``: ticks over a stream pool (writer.plan_encode_stream_ticks). A tick: every live file's next chunk is pushed,
         the files whose chunks are exhausted are flushed (their slots go to the next files, in order), the tick's new frames come to the host in ONE copy
-        and are appended to the token files."""
+        and are appended to the token files. ``resample="file"``: a file's units are the ticks of its resident PCM (resample_stream.ResidentFiles) and a
+        tick's chunks come out of one resample launch."""
         from .audio_io import AudioDecodeError, process_audio_chunks
         from .configs import AudioConfig
         from .prefetch import ordered_map
@@ -469,7 +508,17 @@ class AudioToken:
 
         opened: list = []     # position in the tick plan -> [path, chunks]
 
+        resident = None
+        if resample == "file":
+            from .resample_stream import ResidentFiles
+            resident = ResidentFiles(self.device, sr, chunk_size, num_workers, skipped, max_file_bytes=max_file_bytes, min_samples=321)
+
         def chunk_counts():
+            if resident is not None:
+                for f in resident.open_all(files):    # [name, the file on the device]: its PCM is released with this entry, after its flush
+                    opened.append([f.name, f])
+                    yield range(f.ticks)
+                return
             for path, chunks, why in ordered_map(load, [str(f) for f in files], num_workers):
                 if chunks is None:
                     skipped(path, why)
@@ -499,8 +548,12 @@ class AudioToken:
                 for r in tick:
                     if r.file not in sids:
                         sids[r.file] = pool.open()
-                    chunks = opened[r.file][1]
-                    feed[sids[r.file]], chunks[r.t0] = chunks[r.t0], None
+                    if resident is None:
+                        chunks = opened[r.file][1]
+                        feed[sids[r.file]], chunks[r.t0] = chunks[r.t0], None
+                if resident is not None:
+                    for r, x in zip(tick, resident.chunks([(opened[r.file][1], r.t0) for r in tick])):
+                        feed[sids[r.file]] = x
                 t1 = time.perf_counter()
                 out = pool.push(feed)           # every group's status word is read in there: the tokens are verified when it returns
                 last = [r.file for r in tick if r.last]
@@ -528,6 +581,9 @@ class AudioToken:
             try:
                 self._end_of_run()
                 self.run_summary["library_pushes"] = pool.library_pushes
+                if resident is not None:
+                    self.run_summary["resample_launches"] = resident.resampler.launches
+                    resident.finish()
             except Exception as e:   # bookkeeping must not mask the exception that ended the run
                 logger.error(f"encode_batch_files: end-of-run bookkeeping failed: {type(e).__name__}: {e}")
         rt["total_s"] = time.time() - start_time

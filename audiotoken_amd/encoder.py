@@ -163,11 +163,19 @@ class AcousticEncoder(_EncodecCallable):
             return codes, emb
         return codes
 
-    def new_stream(self, batch: int = 1):
+    def resampler(self):
+        """The encoder's device resampler (resample_stream.DeviceResampler: its tables live on the device once per rate), made on first use."""
+        if getattr(self, "_resampler", None) is None:
+            from .resample_stream import DeviceResampler
+            self._resampler = DeviceResampler(self.device, self.config.model_sample_rate)
+        return self._resampler
+
+    def new_stream(self, batch: int = 1, sample_rate: Optional[int] = None):
         """A stateful encoder for audio that arrives in pieces (audiotoken_amd/streaming.py): ``push`` / ``flush`` give the tokens one-shot
-        ``forward`` gives for the concatenated audio, in memory bounded by the largest push. Streams of one encoder are independent."""
+        ``forward`` gives for the concatenated audio, in memory bounded by the largest push. Streams of one encoder are independent.
+        ``sample_rate``: the pushes are raw samples at that rate, resampled on the device as one signal."""
         from .streaming import AcousticStream
-        return AcousticStream(self, batch)
+        return AcousticStream(self, batch, sample_rate=sample_rate)
 
     def new_stream_pool(self, slots: int = 1):
         """Up to ``slots`` streams that start and finish on their own (audiotoken_amd/streaming.py, AcousticStreamPool): each gives the tokens of its

@@ -24,6 +24,7 @@ from . import weights as W
 
 HOP = W.ENCODEC_HOP          # 320 samples per frame
 FIRST_PUSH_FRAMES = 7        # the library's minimum for the first push of a stream (include/audiotoken_hip.h)
+SAMPLE_RATE = 24_000         # EnCodec's rate: what a stream without an encoder (push_fn) resamples to
 
 
 class AcousticStream:
@@ -35,12 +36,23 @@ class AcousticStream:
     f16x2 again; bit 0: the LSTM route is switched for the rest of the handle's life). Reading the status word synchronises once per push.
 
     ``push_fn(samples [B, n], final) -> codes [B, n_q, t]`` replaces the device call (the host-side buffering is tested with a stub).
+
+    ``sample_rate``: the stream takes RAW samples at that rate (float32 or int16, torch or numpy) and resamples them on the device at stream-global
+    positions, carrying the source tail across pushes (resample_stream.py): the tokens are those of the whole signal resampled
+    once. The resampled samples enter the residual buffering below like pushed ones. None: samples are float at the model's rate, as ever.
     """
 
-    def __init__(self, encoder=None, batch: int = 1, push_fn: Optional[Callable] = None, n_q: Optional[int] = None):
+    def __init__(self, encoder=None, batch: int = 1, push_fn: Optional[Callable] = None, n_q: Optional[int] = None, sample_rate: Optional[int] = None,
+                 resampler=None):
         assert batch >= 1, "batch must be >= 1"
         self._enc = encoder
         self.batch = int(batch)
+        self._rate = None
+        if sample_rate is not None:
+            from . import resample_stream as RS
+            model_rate = encoder.config.model_sample_rate if encoder is not None else SAMPLE_RATE
+            self._rate = RS.RateState(sample_rate, model_rate, self.batch)
+            self._resampler = resampler if resampler is not None else (encoder.resampler() if encoder is not None else RS.HostResampler(model_rate))
         self.n_q = int(n_q if n_q is not None else encoder.n_q)
         self._push_fn = push_fn if push_fn is not None else self._device_push
         self._state = None
@@ -59,6 +71,8 @@ class AcousticStream:
         self._started = False
         self._finished = False
         self.frames_emitted = 0
+        if self._rate is not None:
+            self._rate.reset()
         if self._state is not None:
             enc = self._enc
             with torch.cuda.device(enc.device):
@@ -81,7 +95,23 @@ class AcousticStream:
             samples = samples.to(device=self._enc.device, dtype=torch.float32)
         return samples
 
+    def _resampled(self, samples, final: bool) -> torch.Tensor:
+        """Raw samples at the stream's rate (None: none, the flush) -> what they add to the signal at the model's rate, float32 [B, m]. The source tail
+        moves on here; the result goes into ``_held`` at once, so it outlives a push of the library that fails."""
+        rs = self._rate
+        window, n_new = rs.window(samples, self._enc.device if self._enc is not None else None)
+        from .resample_stream import plan_push
+        plan = plan_push(rs.pos, n_new, final)
+        out = torch.stack(self._resampler.run(rs.jobs(window, plan))) if plan.out_len else window.new_zeros((self.batch, 0), dtype=torch.float32)
+        rs.advance(window, plan)
+        self._held = out if self._held is None else torch.cat([self._held, out], dim=1)
+        return out[:, :0]
+
     def push(self, samples: torch.Tensor) -> torch.Tensor:
+        if self._rate is not None:
+            if self._finished:
+                raise RuntimeError("AcousticStream: push after flush(); call reset() to start a new stream")
+            samples = self._resampled(samples, False)
         samples = self._check(samples)
         held = samples if self._held is None else torch.cat([self._held, samples], dim=1)
         n = held.shape[1] // HOP * HOP
@@ -99,6 +129,8 @@ class AcousticStream:
         """The last frame(s): what is held goes out with the one-shot path's right-edge padding. The stream is finished afterwards."""
         if self._finished:
             raise RuntimeError("AcousticStream: flush() twice; call reset() to start a new stream")
+        if self._rate is not None:
+            self._resampled(None, True)
         held = self._held
         self._held = None
         self._finished = True
@@ -244,10 +276,11 @@ class AcousticDecodeStream:
 # ======================================================================================================================================================
 class _Row:
     """Host-side record of one open stream of a pool."""
-    __slots__ = ("slot", "held", "started")
+    __slots__ = ("slot", "held", "started", "rate")
 
     def __init__(self, slot: int):
         self.slot = slot
+        self.rate = None                           # encode: resample_stream.RateState of a stream opened with a sample rate of its own
         self.held: Optional[torch.Tensor] = None   # encode: samples [< 320 (or < the first push's minimum)]; decode: tokens [K, < 7]
         self.started = False
 
@@ -376,13 +409,18 @@ class AcousticStreamPool(_StreamPool):
     that never started is the one-shot case and needs at least 321 samples, as the library says.
 
     ``push_fn(samples [B, n], final, started) -> codes [B, n_q, t]``; ``keep_embeddings``: ``last_embeddings = {sid: [t, 128]}`` of the last call.
+
+    ``open(sample_rate=r)``: that stream takes raw samples at ``r`` Hz (float32 or int16, torch or numpy), resampled on the device at stream-global
+    positions (resample_stream.py). All such streams of one ``push`` / ``flush`` call, whatever their rates, share ONE resample
+    launch; what it gives enters the streams' ``held`` samples before any library push, so it outlives one that fails.
     """
     _WHAT = "acoustic stream pool push"
     _LIB = "at_encodec_stream"
 
     def __init__(self, encoder=None, slots: int = 1, push_fn: Optional[Callable] = None, gather_fn: Optional[Callable] = None,
-                 scatter_fn: Optional[Callable] = None, owner=None, n_q: Optional[int] = None):
+                 scatter_fn: Optional[Callable] = None, owner=None, n_q: Optional[int] = None, resampler=None):
         self.n_q = int(n_q if n_q is not None else encoder.n_q)
+        self._resampler = resampler
         self.keep_embeddings = False
         self.last_embeddings: Dict[int, torch.Tensor] = {}
         self._emb = None
@@ -391,6 +429,40 @@ class AcousticStreamPool(_StreamPool):
     def _empty(self, like: torch.Tensor) -> torch.Tensor:
         dev = self._model.device if self._model is not None else like.device
         return torch.empty((self.n_q, 0), dtype=torch.int16, device=dev)
+
+    def open(self, sample_rate: Optional[int] = None) -> int:
+        """A new stream in the lowest free slot; its id. ``sample_rate``: the rate of the raw samples it will be pushed (None: float at the model's rate)."""
+        rate = None
+        if sample_rate is not None:
+            from . import resample_stream as RS
+            model_rate = self._model.config.model_sample_rate if self._model is not None else SAMPLE_RATE
+            rate = RS.RateState(sample_rate, model_rate, 1)
+            if self._resampler is None:
+                self._resampler = self._model.resampler() if self._model is not None else RS.HostResampler(model_rate)
+        sid = super().open()
+        self._rows[sid].rate = rate
+        return sid
+
+    def _resample(self, rows: Dict[int, "_Row"], samples: Dict[int, Optional[torch.Tensor]], final: bool) -> Dict[int, torch.Tensor]:
+        """The rows with a rate of their own: ONE launch turns their raw samples (None: none, the flush) into what they add at the model's rate, and
+        their source tails move on. ``{sid: float32 [m]}``."""
+        from .resample_stream import plan_push
+        dev = self._model.device if self._model is not None else None
+        todo, jobs = [], []
+        for sid, row in rows.items():
+            if row.rate is None:
+                continue
+            x = samples[sid]
+            window, n_new = row.rate.window(None if x is None else _row_samples(x), dev)
+            plan = plan_push(row.rate.pos, n_new, final)
+            todo.append((sid, row, window, plan))
+            jobs.extend(row.rate.jobs(window, plan))
+        outs = self._resampler.run(jobs) if jobs else []
+        res = {}
+        for (sid, row, window, plan), y in zip(todo, outs):
+            row.rate.advance(window, plan)
+            res[sid] = y
+        return res
 
     def _run(self, ids: List[int], xs: List[torch.Tensor], started: bool, final: bool, out: Dict[int, torch.Tensor]) -> None:
         x = torch.stack(xs).contiguous()
@@ -406,6 +478,13 @@ class AcousticStreamPool(_StreamPool):
         self.last_embeddings = {}
         groups: Dict[tuple, List[int]] = {}
         held: Dict[int, torch.Tensor] = {}
+        rows = {sid: self._row(sid, "push") for sid in sorted(samples)}
+        if any(row.rate is not None for row in rows.values()):
+            samples = dict(samples)
+            for sid, y in self._resample(rows, samples, False).items():   # into `held` first: the source tail has moved on
+                row = rows[sid]
+                row.held = y if row.held is None else torch.cat([row.held, y])
+                samples[sid] = y[:0]
         for sid in sorted(samples):
             row, x = self._row(sid, "push"), samples[sid]
             assert x.dim() == 1, "samples of a stream must be [n]"
@@ -434,6 +513,10 @@ class AcousticStreamPool(_StreamPool):
         self.last_embeddings = {}
         groups: Dict[tuple, List[int]] = {}
         rows = {sid: self._row(sid, "flush") for sid in sids}
+        if any(row.rate is not None for row in rows.values()):
+            for sid, y in self._resample(rows, {sid: None for sid in rows}, True).items():
+                row = rows[sid]
+                row.held = y if row.held is None else torch.cat([row.held, y])
         for sid, row in rows.items():
             n = 0 if row.held is None else row.held.shape[0]
             if n == 0:
@@ -465,6 +548,14 @@ class AcousticStreamPool(_StreamPool):
         _cabi.check(rc, "at_encodec_encode_stream_checked")
         assert t_out.value == T, (t_out.value, T)
         return codes
+
+
+def _row_samples(x):
+    """Raw samples [n] of one pool stream as the one-row batch [1, n] a RateState takes."""
+    import numpy as np
+    x = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    assert x.dim() == 1, "samples of a stream must be [n]"
+    return x[None]
 
 
 class AcousticDecodeStreamPool(_StreamPool):

@@ -371,6 +371,33 @@ size_t at_segments_zmuv_workspace_bytes(int nseg, int max_chunk_out_len);
 int at_segments_from_pcm_zmuv(const at_segment_desc* descs_dev, int nseg, int seg_len, int max_chunk_out_len, float pad_value, float eps, float* segments,
                               float* masks, void* workspace, size_t workspace_bytes, at_stream_t stream);
 
+/* ---- stateful resampling of streamed audio: the rule of at_segments_from_pcm at GLOBAL sample positions -------------------------------
+ * A signal of L source samples has outputs j in [0, ceil(n L / o)): with f = j / n, p = j % n, base = f o - width,
+ *   y[j] = sum over k in [lo_p, hi_p), ascending, of one fmaf(K[p][k], x[base + k], acc),   x[s] = 0 for s < 0 or s >= L
+ * (table, phases and tap ranges as in at_segment_desc; the sample conversion too). A row evaluates `out_len` consecutive outputs from a WINDOW of the signal,
+ * so a signal pushed in pieces, each with the tail of the one before in front, gets the samples of resampling it once. One descriptor per row:
+ *   pcm        device pointer to the window's samples in format `fmt`; table: as in at_segment_desc, NULL = native rate (o = n = 1, width = 0: conversion only)
+ *   src_base   global index of pcm[0] (negative for a window that opens with stored zeros before the signal); src_len: samples of the window
+ *   src_total  L, read when `final` is non-zero: taps at s >= L are zeros. A row that is not final may only have taps inside its window
+ *   out_start  global j of the row's first output; out_len outputs are written to out + dst_off (floats), nothing else is touched
+ * at_resample_rows: ONE launch for all rows (they may differ in rate, format and length); stream-ordered, no allocation; it trusts the descriptors.
+ * at_resample_rows_check: host code over a HOST copy of the descriptors, to be called before every launch: 0, or a negative code with at_last_error set for
+ * a null pointer, nrows < 1, a negative length or offset, an unknown fmt, o / n / width that do not belong together (o and n coprime, width =
+ * ceil(6 o / (0.99 min(o, n))), a table exactly when o != n), a row that is not final with a tap (k in [0, 2 width + o)) outside its window, a final row
+ * with a tap inside [0, src_total) but outside its window, or outputs past ceil(n src_total / o). */
+typedef struct at_resample_row {
+    const void* pcm;
+    const float* table;
+    int64_t src_base, src_len, src_total, out_start;
+    int32_t out_len, fmt;
+    float scale;
+    int32_t o, n, width, final;
+    int32_t reserved;
+    int64_t dst_off;
+} at_resample_row;
+int at_resample_rows(const at_resample_row* rows_dev, int nrows, float* out, at_stream_t stream);
+int at_resample_rows_check(const at_resample_row* rows_host, int nrows);
+
 /* ---- output side of decode_batch_files: the decoder's float32 batch -> compacted 16-bit PCM ------------------------------------------
  * One descriptor per row (built on the host; the array lives in device memory):
  *   src_off   first sample of the row, in floats from `src` (the padded decoder output [B][320 T_max]: src_off = b * 320 * T_max)
