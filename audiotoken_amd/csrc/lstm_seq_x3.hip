@@ -331,7 +331,7 @@ int launch_lstm_seq_x3(const LstmSeqArgs& a_in, hipStream_t stream) {
     const bool st = a.h_init != nullptr;
     AT_REQUIRE(st == (a.c_init != nullptr) && st == (a.c_final != nullptr), "lstm_seq_x3: h_init, c_init and c_final go together");
     // the three-piece bf16 kernel sits at 255 of 256 registers: the state branch would spill, so carried state exists on the fp16 scheme only
-    // (lstm_skip in encodec.hip routes a streaming call with "lstm_f16x2" = 0 to the fp32 persistent kernel)
+    // (lstm_route in encodec_plan.h routes a streaming call with "lstm_f16x2" = 0 to the fp32 persistent kernel)
     AT_REQUIRE(!st || a.w_scale_f16 > 0.f, "lstm_seq_x3: carried state needs the two-piece fp16 scheme");
     const int rc = st ? launch_lx<SchemeF16x2, true>(a, a.w_scale_f16, LX_H_SCALE, stream)
                       : (a.w_scale_f16 > 0.f ? launch_lx<SchemeF16x2, false>(a, a.w_scale_f16, LX_H_SCALE, stream) : launch_lx<SchemeBf16x3, false>(a, 1.0f, 1.0f, stream));

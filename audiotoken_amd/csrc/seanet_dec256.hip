@@ -1,4 +1,4 @@
-// Decoder stage 0 (256 channels at 8 T rows per clip) on the split GEMMs, as the encoder's stage-3 block (encodec.hip "chain3"): the block's k3 conv
+// Decoder stage 0 (256 channels at 8 T rows per clip) on the split GEMMs, as the encoder's stage-3 block (encodec_encode.hip, "chain3"): the block's k3 conv
 // (256 -> 128) and its tail ([ELU(h) | u] 384 -> 256) are windowed / plain launches of gemm_f16x2_tg on two-piece fp16 operands instead of two fp32-MFMA
 // GEMMs (1.54 ms for 64 clips x 10 s, 99 TFLOP/s). This file holds the one pass that feeds them from the transposed conv's fp32 output u [g][L][256]:
 //   ac3  [2][g][16][Lpc][16]   ELU(u) pieces, row t at index t + 2, the two front rows = the causal conv's reflect padding (u[2], u[1])

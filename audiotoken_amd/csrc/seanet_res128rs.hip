@@ -61,7 +61,7 @@ __global__ __launch_bounds__(512, 1) void seanet_res128rs_kernel(Res64Args a) {
     constexpr int NP = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds_raw[];
     PT* Xb = reinterpret_cast<PT*>(rs_lds_raw);          // [3][4 planes][34][144]
-    PT* Hb = Xb + 3 * RS_XBUF;                           // [2][2 pieces][32][80]
+    PT* Hb = Xb + 3 * RS_XBUF;                           // [2][2 pieces][32][64]: dense rows, 16-byte chunks swizzled (rs_hoff)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int role_t = __builtin_amdgcn_readfirstlane(wave >> 2);   // 0: conv3 wave, 1: tail wave
     const int w = wave & 3;

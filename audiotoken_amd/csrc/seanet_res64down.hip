@@ -100,6 +100,7 @@ __global__ __launch_bounds__(RD_THREADS, 1) void seanet_res64down_kernel(ResDown
     typedef SC::V8 V8;
     typedef SC::V4 V4;
     constexpr int NP = SC::NP;
+    static_assert(SC::NP == 2, "RD_XBUF and RD_LDS_BYTES count two pieces per operand");
     extern __shared__ __attribute__((aligned(16))) unsigned char rd_lds_raw[];
     PT* Xs = reinterpret_cast<PT*>(rd_lds_raw);   // [2 buffers][split(ELU(x)) | split(x)][NP]
     PT* Hs = Xs + 2 * RD_XBUF;                    // split(ELU(conv3 + b3))

@@ -1,7 +1,7 @@
 // What the handles of the two semantic tokenizers (at_hubert in hubert.hip, at_w2vbert in w2vbert.hip) have in common, stated once: tensor staging, the
 // device arena and its packed export / import replay (packed_model.h), the lazy weight splits per scheme, the range table, the common options and the
 // reports. A model file keeps what is its own: weight pointers, LayerW, Plan, the site names, the model part of finalize, the list of weights it splits
-// and the encode body. HostTensor, stage_tensor and device_exists also serve the acoustic handle (encodec.hip).
+// and the encode body. HostTensor, stage_tensor and device_exists also serve the acoustic handle (encodec_handle.h).
 #pragma once
 #include <map>
 #include <string>

@@ -1,6 +1,6 @@
 // Stream pools: rows of a stream state moved between a pool of S slots and a staging state of B rows.
 //
-// Both stream states (encodec.hip: StreamState, DecStreamState) are lists of planes [rows][w] that follow each other: a plane of an R-row state starts
+// Both stream states (encodec_plan.h: StreamState, DecStreamState) are lists of planes [rows][w] that follow each other: a plane of an R-row state starts
 // R * (sum of the widths before it) floats behind the state's base. One kernel copies row src_row(b) of every plane of the source to row dst_row(b) of
 // the same plane of the destination, for b < B: gather reads row slots[b] of an S-row pool into row b of a B-row state, scatter is the inverse.
 // A pure copy on 16-byte loads and stores (every width is a multiple of 4 floats, so every row start is 16-byte aligned when the bases are): no LDS,

@@ -1,6 +1,6 @@
 """Route model of the acoustic encoder's length-selected kernel dispatch, and the table of clip lengths that reaches every route.
 
-``encodec_encode_impl`` (audiotoken_amd/csrc/encodec.hip) picks its kernels from the clip length alone. With L[0] = N and
+``enc_route`` (audiotoken_amd/csrc/encodec_plan.h) picks the kernels of ``encodec_encode_impl`` (encodec_encode.hip) from the clip length alone. With L[0] = N and
 L[s+1] = ceil(L[s] / (2, 4, 5, 8)[s]) (``make_plan``), five predicates choose the route:
 
   a  N % 2 == 0                    `fused0`:      seanet_stage0* fused          | conv0_kernel + GEMM block + GEMM strided conv
@@ -10,8 +10,7 @@ L[s+1] = ceil(L[s] / (2, 4, 5, 8)[s]) (``make_plan``), five predicates choose th
                                    split_phase_major + split GEMM               | GEMM resblock + fp32 strided conv
   e  T = L[4] > 6                  final k = 7 conv as windowed f16x2 split GEMM | zero-extended rows + fp32 conv_gemm (the reference's short-input rule)
 
-(the `fused0`, `stage1`, `down2_gemm`, `chain3` and `s == 3 && ... L % 8 == 0 && L >= 16` conditions of the stage loop, and `Ty > 6` in front of
-the final conv). All 32 combinations are reachable; N < 321 (L[3] <= 8) is refused.
+(the `fused0`, `stage1_fused`, `down2_gemm`, `chain3` and `down3_gemm` fields of `EncRoute`, and `fin`: `Ty > 6`). All 32 combinations are reachable; N < 321 (L[3] <= 8) is refused.
 
 Plain helper for tests/test_acoustic_routes_cpu.py and tests/test_acoustic_routes_gpu.py — not a conftest, no fixtures.
 """
@@ -86,7 +85,7 @@ def waveform(N: int, batch: int = B):
 
 def expected_launches(sig):
     """{profile group: launch count} of the conv stack and the final conv that the signature predicts for ONE sub-batch; a group that must
-    not appear maps to 0. (encodec.hip: the prof.begin calls of the stage loop.)"""
+    not appear maps to 0. (encodec_encode.hip: the prof.begin calls of the stage functions.)"""
     a, b, c, d, e = sig
     chain3 = c and d
     return {
