@@ -581,8 +581,15 @@ bool relpos_attention_w8_eligible(int T, int heads, long long rows_pad, long lon
     return T >= 1 && T <= 4096 /* 64 tile bits */ && rows_pad * heads * 64 * 8 < (1ll << 32) /* one descriptor over the four planes */ && w8_lds_bytes(T, relpos) <= (size_t)W8_LDS_MAX && rows_pad >= B * T && (long long)T * heads * 64 * 2 < (1ll << 31);
 }
 
-int launch_relpos_attention_w8(const float* qkv, const float* amask, const __bf16* dist_pieces, float dist_scale, float* ctx, int B, int T, hipStream_t stream,
-                               int heads, int* status, __bf16* ctx_pieces, long long rows_pad, const __bf16* kv_pieces) {
+int launch_relpos_attention_w8(const AttnArgs& a, hipStream_t stream) {
+    const float *qkv = a.qkv, *amask = a.amask;
+    float* const ctx = a.ctx;
+    const int B = a.B, T = a.T, heads = a.heads;
+    int* const status = a.status;
+    __bf16* const ctx_pieces = a.ctx_pieces;
+    const long long rows_pad = a.rows_pad;
+    const __bf16 *kv_pieces = a.kv_pieces, *dist_pieces = a.dist.p;
+    const float dist_scale = a.dist.s;
     AT_REQUIRE(kv_pieces != nullptr && relpos_attention_w8_eligible(T, heads, rows_pad, B, dist_pieces != nullptr),
                "relpos_attention_w8: needs pre-split k / v and a clip whose key-bias table fits LDS (T <= 1728 with rel-pos)");
     const long long nblk = (long long)((T + W8_QB - 1) / W8_QB) * heads * B;

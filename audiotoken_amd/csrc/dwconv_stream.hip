@@ -179,7 +179,12 @@ __global__ __launch_bounds__(1024, 1) void dwconv_stream_kernel(const float* __r
 }
 
 int launch_dwconv_stream(const float* g, const float* w, const float* gamma, const float* beta, float* out, int B, int T, hipStream_t stream,
-                         __bf16* pieces, long long rows_pad, int scheme, float scale, int* status) {
+                         const SplitOut& split) {
+    __bf16* const pieces = split.pieces;
+    const long long rows_pad = split.rows_pad;
+    const int scheme = split.scheme;
+    const float scale = split.scale;
+    int* const status = split.status;
     // time segments: enough workgroups for every CU (one resident workgroup of 16 waves each), segment length a multiple of the 8-row iteration
     const int cus = device_cus();
     int nseg = (cus + B - 1) / B;

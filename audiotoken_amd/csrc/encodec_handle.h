@@ -26,11 +26,6 @@ struct ConvW {
     const float* b = nullptr;
     int cin = 0, cout = 0, k = 0, stride = 1;
 };
-// a weight as K-blocked 16-bit pieces (two fp16 pieces of w * s, s a power of two; or three bf16 pieces, s = 1)
-struct SplitW {
-    const piece_t* p = nullptr;
-    float s = 1.f;
-};
 // one 2-layer LSTM: fp32 weights in gate-interleaved rows, and with bf16x3 the input projections as operand pieces
 struct LstmW {
     const float *wih[2] = {}, *whh[2] = {}, *bih[2] = {}, *bhh[2] = {};

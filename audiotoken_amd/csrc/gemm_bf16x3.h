@@ -22,6 +22,20 @@ constexpr int XB_STATUS_NONFINITE = 4;
 // 16-bit storage of one operand piece (bf16 bits or fp16 bits, by scheme)
 typedef __bf16 piece_t;
 inline int xb_pieces(int scheme) { return scheme == XB_SCHEME_F16X2 ? 2 : 3; }
+// a weight as K-blocked 16-bit pieces (two fp16 pieces of w * s, s a power of two; or three bf16 pieces, s = 1)
+struct SplitW {
+    const piece_t* p = nullptr;
+    float s = 1.f;
+};
+// Where a kernel with an fp32 output writes it as the K-blocked operand pieces [NP][K/16][rows_pad][16] of `scheme` (times `scale`) for the next GEMM,
+// and the range site that hears about values outside fp16. Default-constructed: fp32 output only.
+struct SplitOut {
+    piece_t* pieces = nullptr;
+    long long rows_pad = 0;
+    int scheme = XB_SCHEME_BF16X3;
+    float scale = 1.0f;
+    int* status = nullptr;
+};
 // power-of-two scale that puts max |w| into [2^14, 2^15) (1 for an all-zero tensor)
 float xb_weight_scale(float max_abs);
 // The provable activation scale of a LayerNorm-fed split site (round 5). A normalised row has Euclidean norm <= sqrt(D), so |LN(x)_k| <= sqrt(D) |gamma_k| +

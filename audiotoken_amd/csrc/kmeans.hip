@@ -813,8 +813,8 @@ int at_kmeans_layernorm(const float* x, float* y, int64_t rows, int D, int split
     // the semantic_m quantiser step's kernel: fp32 rows and fp16 operand pieces in one pass (the pieces go to the workspace and are not used)
     const long long rows_pad = (rows + 7) / 8 * 8;
     AT_REQUIRE(workspace && workspace_bytes >= (size_t)rows_pad * D * 2 * sizeof(piece_t), "at_kmeans_layernorm: workspace >= round_up(rows, 8) * D * 4 bytes");
-    return launch_layernorm_split(x, nullptr, nullptr, nullptr, y, static_cast<piece_t*>(workspace), rows, rows_pad, D, XB_SCHEME_F16X2, XB_F16_ACT_SCALE,
-                                  nullptr, (hipStream_t)stream);
+    return launch_layernorm_split(x, nullptr, nullptr, nullptr, y, rows, D, SplitOut{static_cast<piece_t*>(workspace), rows_pad, XB_SCHEME_F16X2, XB_F16_ACT_SCALE, nullptr},
+                                  (hipStream_t)stream);
 }
 
 int at_kmeans_row_d2(const at_kmeans_t* h, double* out, at_stream_t stream) {

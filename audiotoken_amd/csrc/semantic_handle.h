@@ -1,7 +1,7 @@
 // What the handles of the two semantic tokenizers (at_hubert in hubert.hip, at_w2vbert in w2vbert.hip) have in common, stated once: tensor staging, the
-// device arena and its packed export / import replay (packed_model.h), the lazy weight splits per scheme, the range table, the common options and the
-// reports. A model file keeps what is its own: weight pointers, LayerW, Plan, the site names, the model part of finalize, the list of weights it splits
-// and the encode body. HostTensor, stage_tensor and device_exists also serve the acoustic handle (encodec_handle.h).
+// device arena and its packed export / import replay (packed_model.h), the lazy weight splits per scheme, the range table, the common options, the
+// reports, the split-GEMM helper that owns the f16x2 scale rule (split_gemm_args) and the finalize helpers. A model file keeps what is its own: weight
+// pointers, LayerW, Plan, the site names, the model part of finalize, the list of weights it splits and the encode stages. HostTensor, stage_tensor and device_exists also serve the acoustic handle (encodec_handle.h).
 #pragma once
 #include <map>
 #include <string>
@@ -107,13 +107,55 @@ const float* reserve(SemanticHandle* h, size_t n_floats);
 // the staged tensor `name` of exactly `shape` uploaded (import: reserved); on failure nullptr, the error set and ok = false
 const float* take(SemanticHandle* h, const std::string& name, std::vector<int64_t> shape, bool& ok);
 
+// a tensor that finalize repacks on the host. `fill(v)` writes the repacked floats into v (n zeros) and returns 0, or sets the error and returns non-zero
+// (the staged tensor is missing); import: the next n floats of the blob, `fill` is not called. *dst = nullptr when the device allocation failed: the caller
+// names that error.
+template <class Fill>
+int take_repacked(SemanticHandle* h, size_t n, const float** dst, Fill&& fill) {
+    if (h->arena.importing) { *dst = reserve(h, n); return 0; }
+    std::vector<float> v(n, 0.f);
+    if (int rc = fill(v)) return rc;
+    *dst = upload(h, v);
+    return 0;
+}
+// the three [hid][hid] projections prefix + names[j] + ".weight" / ".bias" as ONE [3 hid][hid] weight and [3 hid] bias (one GEMM, one pass over the
+// LayerNorm output): two allocations, weight then bias. *w / *b = nullptr when a device allocation failed.
+int take_qkv(SemanticHandle* h, const std::string& prefix, const char* const names[3], int hid, const float** w, const float** b);
+// |row|^2 of the n rows of a code book [n][d], summed in fp32 in index order (the e2 / c2 term of the quantisers' expanded distance)
+std::vector<float> code_norms(const std::vector<float>& codes, int n, int d);
+// the provable f16x2 scale of the split site fed by LayerNorm(D; gamma, beta), from the recorded max |gamma|, max |beta| (xb_ln_site_scale, gemm_bf16x3.h)
+float ln_site_scale(const SemanticHandle* h, const float* gamma, const float* beta, int D);
+
 // ---- weight splits, for the model's split_model() ------------------------------------------------------------------------------------------
 // the fp16 scheme's power-of-two scale of the uploaded tensor `src`, from its recorded max |w|
 int weight_scale(SemanticHandle* h, const float* src, float* scale_out);
-// W [n][k] as pieces of `scheme`, rows padded to n_pad (0: n) with zeros: allocate, set *scale_out (f16x2 only), split unless importing (the pieces are in the blob)
-int split_one(SemanticHandle* h, int scheme, const float* src, int n, int k, const piece_t** dst, float* scale_out, int n_pad = 0, int win_cblocks = 0,
-              int win_stride = 1);
+// W [n][k] as pieces of `scheme`, rows padded to n_pad (0: n) with zeros: allocate, set dst->s (f16x2 only; bf16x3 keeps 1), split unless importing (the
+// pieces are in the blob)
+int split_one(SemanticHandle* h, int scheme, const float* src, int n, int k, SplitW* dst, int n_pad = 0, int win_cblocks = 0, int win_stride = 1);
 int split_weights(SemanticHandle* h, int scheme);   // split_model() once per scheme, recorded in split_seq
+
+// ---- split GEMMs, for the model's encode stages ---------------------------------------------------------------------------------------------
+inline int scheme_of(int arith) { return arith == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3; }
+// The split arithmetic of one part of a model (a layer, or the front end / quantiser): its scheme and its row of the range table (nullptr: no range sites)
+struct SplitCtx {
+    int scheme;
+    int* row;
+    int* site(int k) const { return row ? row + 2 * k : nullptr; }
+    // the scale activations are multiplied by before they are split: `f16` on the fp16 scheme, 1 on bf16x3 (full fp32 exponent range)
+    float act(float f16 = XB_F16_ACT_SCALE) const { return scheme == XB_SCHEME_F16X2 ? f16 : 1.0f; }
+    SplitOut out(piece_t* pieces, long long rows_pad, float f16_scale, int* status) const { return SplitOut{pieces, rows_pad, scheme, act(f16_scale), status}; }
+};
+// A plain linear layer acc = A . W^T on the split GEMM (gemm_bf16x3.hip): A as pieces that were split with a_scale, W with its scale; values the epilogue
+// splits again are multiplied by out_scale and their range verdict goes to `status`. THE place of the f16x2 scale rule: acc_scale = 1 / (s_a s_w),
+// split_scale = s_out. Every scale is 1 on bf16x3 (SplitCtx::act, SplitW::s), where 1 / (1 * 1) is exact: no scheme branch. The caller adds the bias and
+// where the output goes (C / R / S) and, for a windowed conv, the window description.
+Bf16x3Args split_gemm_args(int scheme, const piece_t* A, float a_scale, const SplitW& w, long long M, int N, int K, long long Mpad, int epi, int* status,
+                           float out_scale);
+// The fused q / k / v projection of an f16x2 layer (XB_EPI_QKV): q as fp32 rows of C [M][3 hid], k and v as row-major fp16 pieces in kvs
+int qkv_split_gemm(const SplitCtx& c, int kv_site, const piece_t* A, float a_scale, const SplitW& w, const float* bias, int hid, long long M, long long Mpad,
+                   float* C, piece_t* kvs, hipStream_t stream);
+// The quantisers' score GEMM dots [M][n_codes] = LN(x) . E^T against a code book split into n_codes rows of pieces
+int score_split_gemm(const SplitCtx& c, const piece_t* A, const SplitW& codes, int n_codes, int K, long long M, long long Mpad, float* dots, hipStream_t stream);
 
 // ---- bodies of the exported at_<model>_* functions; `fn` is the exported function's name where an error text carries it -------------------------------
 int sem_finalize(SemanticHandle* h);

@@ -79,24 +79,57 @@ const float* take(SemanticHandle* h, const std::string& name, std::vector<int64_
     return d;
 }
 
-// ---- weight splits ----------------------------------------------------------------------------------------------------------------------------
-static int scheme_of(int arith) { return arith == ARITH_F16X2 ? XB_SCHEME_F16X2 : XB_SCHEME_BF16X3; }
+int take_qkv(SemanticHandle* h, const std::string& prefix, const char* const names[3], int hid, const float** w, const float** b) {
+    const size_t hh = (size_t)hid * hid;
+    if (h->arena.importing) {
+        *w = reserve(h, 3 * hh);
+        *b = reserve(h, (size_t)3 * hid);
+        return 0;
+    }
+    std::vector<float> wv(3 * hh), bv((size_t)3 * hid);
+    for (int j = 0; j < 3; ++j) {
+        const HostTensor* wt = find(h, prefix + names[j] + ".weight");
+        const HostTensor* bt = find(h, prefix + names[j] + ".bias");
+        AT_REQUIRE(wt && bt && wt->shape == (std::vector<int64_t>{hid, hid}) && bt->shape == (std::vector<int64_t>{hid}),
+                   "attention projection tensors missing or mis-shaped");
+        std::memcpy(&wv[j * hh], wt->data.data(), hh * sizeof(float));
+        std::memcpy(&bv[(size_t)j * hid], bt->data.data(), hid * sizeof(float));
+    }
+    *w = upload(h, wv);
+    *b = upload(h, bv);
+    return 0;
+}
+std::vector<float> code_norms(const std::vector<float>& codes, int n, int d) {
+    std::vector<float> e2(n);
+    for (int i = 0; i < n; ++i) {
+        float acc = 0.f;
+        for (int k = 0; k < d; ++k) { const float v = codes[(size_t)i * d + k]; acc += v * v; }
+        e2[i] = acc;
+    }
+    return e2;
+}
+float ln_site_scale(const SemanticHandle* h, const float* gamma, const float* beta, int D) {
+    auto mx = [&](const float* d) { auto it = h->wmax.find(d); return it == h->wmax.end() ? 0.f : it->second; };
+    return xb_ln_site_scale(mx(gamma), mx(beta), D);
+}
 
+// ---- weight splits ----------------------------------------------------------------------------------------------------------------------------
 int weight_scale(SemanticHandle* h, const float* src, float* scale_out) {
     auto it = h->wmax.find(src);
     AT_REQUIRE(it != h->wmax.end(), "weight maximum not recorded");
     *scale_out = xb_weight_scale(it->second);
     return 0;
 }
-int split_one(SemanticHandle* h, int scheme, const float* src, int n, int k, const piece_t** dst, float* scale_out, int n_pad, int win_cblocks, int win_stride) {
+int split_one(SemanticHandle* h, int scheme, const float* src, int n, int k, SplitW* dst, int n_pad, int win_cblocks, int win_stride) {
     if (!n_pad) n_pad = n;
     piece_t* d = static_cast<piece_t*>(h->arena.alloc((size_t)xb_pieces(scheme) * n_pad * k * sizeof(piece_t)));
     if (!d) return -1;
+    float s = 1.0f;
     if (scheme == XB_SCHEME_F16X2)
-        if (int rc = weight_scale(h, src, scale_out)) return rc;
+        if (int rc = weight_scale(h, src, &s)) return rc;
     if (!h->arena.importing)
-        if (int rc = launch_split_blocked(src, k, n, n_pad, k, d, nullptr, scheme, scheme == XB_SCHEME_F16X2 ? *scale_out : 1.0f, nullptr, win_cblocks, win_stride)) return rc;
-    *dst = d;
+        if (int rc = launch_split_blocked(src, k, n, n_pad, k, d, nullptr, scheme, s, nullptr, win_cblocks, win_stride)) return rc;
+    *dst = SplitW{d, s};
     return 0;
 }
 int split_weights(SemanticHandle* h, int scheme) {
@@ -106,6 +139,29 @@ int split_weights(SemanticHandle* h, int scheme) {
     h->split_done[scheme] = true;
     h->split_seq.push_back(scheme);
     return 0;
+}
+
+// ---- split GEMMs --------------------------------------------------------------------------------------------------------------------------------
+Bf16x3Args split_gemm_args(int scheme, const piece_t* A, float a_scale, const SplitW& w, long long M, int N, int K, long long Mpad, int epi, int* status,
+                           float out_scale) {
+    Bf16x3Args a;
+    a.A = A; a.W = w.p; a.M = (int)M; a.N = N; a.K = K; a.Mpad = (int)Mpad; a.epi = epi;
+    a.scheme = scheme; a.status = status;
+    a.acc_scale = 1.0f / (a_scale * w.s); a.split_scale = out_scale;
+    return a;
+}
+int qkv_split_gemm(const SplitCtx& c, int kv_site, const piece_t* A, float a_scale, const SplitW& w, const float* bias, int hid, long long M, long long Mpad,
+                   float* C, piece_t* kvs, hipStream_t stream) {
+    // the k / v pieces always use XB_F16_ACT_SCALE, whatever the layer's site scales: the attention kernels divide by that fixed 16
+    Bf16x3Args a = split_gemm_args(c.scheme, A, a_scale, w, M, 3 * hid, hid, Mpad, XB_EPI_QKV, c.site(kv_site), XB_F16_ACT_SCALE);
+    a.bias = bias; a.C = C; a.ldc = 3 * hid; a.S = kvs; a.Spad = (int)Mpad; a.qkv_hid = hid;
+    return launch_gemm_bf16x3(a, stream);
+}
+int score_split_gemm(const SplitCtx& c, const piece_t* A, const SplitW& codes, int n_codes, int K, long long M, long long Mpad, float* dots, hipStream_t stream) {
+    // the VQ / k-means operand has no range site: a non-affine LayerNorm row is bounded by sqrt(D) <= 32, and x 16 cannot leave the fp16 range
+    Bf16x3Args a = split_gemm_args(c.scheme, A, c.act(), codes, M, n_codes, K, Mpad, XB_EPI_LINEAR, nullptr, c.act());
+    a.C = dots; a.ldc = n_codes; a.ldr = n_codes;
+    return launch_gemm_bf16x3(a, stream);
 }
 
 // ---- finalize, and the finalized model as one device blob (packed_model.h) ---------------------------------------------------------------------

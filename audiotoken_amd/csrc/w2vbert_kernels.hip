@@ -438,8 +438,13 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __res
 }
 
 // y = LN(x; gamma, beta) as fp32 rows (y == x allowed: a wave reads its rows first) and out = split(LN(y; gamma2, beta2)): layernorm_split_kernel<.., DOUBLE>
-int launch_layernorm2_split(const float* x, const float* gamma, const float* beta, float* y, const float* gamma2, const float* beta2, __bf16* out, long long rows,
-                            long long rows_pad, int D, int scheme, float scale, int* status, hipStream_t stream) {
+int launch_layernorm2_split(const float* x, const float* gamma, const float* beta, float* y, const float* gamma2, const float* beta2, long long rows, int D,
+                            const SplitOut& split, hipStream_t stream) {
+    __bf16* const out = split.pieces;
+    const long long rows_pad = split.rows_pad;
+    const int scheme = split.scheme;
+    const float scale = split.scale;
+    int* const status = split.status;
     AT_REQUIRE(D == LNS_D && rows_pad >= rows && rows_pad % LNS_ROWS == 0 && out && y, "layernorm2_split: D must be 1024, rows_pad a multiple of 8");
     const unsigned blocks = (unsigned)(rows_pad / LNS_ROWS);
     if (scheme == XB_SCHEME_F16X2)
@@ -452,8 +457,13 @@ int launch_layernorm2_split(const float* x, const float* gamma, const float* bet
     return 0;
 }
 
-int launch_layernorm_split(const float* x, const float* gamma, const float* beta, const float* row_mask, float* y, __bf16* out, long long rows, long long rows_pad,
-                           int D, int scheme, float scale, int* status, hipStream_t stream) {
+int launch_layernorm_split(const float* x, const float* gamma, const float* beta, const float* row_mask, float* y, long long rows, int D, const SplitOut& split,
+                           hipStream_t stream) {
+    __bf16* const out = split.pieces;
+    const long long rows_pad = split.rows_pad;
+    const int scheme = split.scheme;
+    const float scale = split.scale;
+    int* const status = split.status;
     AT_REQUIRE((D == LNS_D || D == 768) && rows_pad >= rows && rows_pad % LNS_ROWS == 0 && out, "layernorm_split: D must be 1024 or 768, rows_pad a multiple of 8");
     const unsigned blocks = (unsigned)(rows_pad / LNS_ROWS);
     if (D == 768) {   // HuBERT: always with the fp32 rows (the post-LN residual stream)
@@ -730,12 +740,14 @@ static int default_attention_arith() {
     return kAttnX3Default ? 2 : 0;
 }
 
-int launch_relpos_attention(const float* qkv, const float* amask, const float* dist_emb, float* ctx, int B, int T,
-                            hipStream_t stream, int heads, int arith, int* status, __bf16* ctx_pieces, long long rows_pad, const __bf16* kv_pieces, int w8,
-                            const __bf16* dist_pieces, float dist_scale) {
+int launch_relpos_attention(const AttnArgs& a, hipStream_t stream) {
     static const int dflt = default_attention_arith();
-    if (arith < 0) arith = dflt;
-    if (arith > 0) return launch_relpos_attention_x3(qkv, amask, dist_emb, ctx, B, T, stream, heads, arith == 2 ? 1 : 0, status, ctx_pieces, rows_pad, kv_pieces, w8, dist_pieces, dist_scale);
+    const int arith = a.arith < 0 ? dflt : a.arith;
+    if (arith > 0) return launch_relpos_attention_x3(a, arith == 2 ? 1 : 0, stream);
+    const float *qkv = a.qkv, *amask = a.amask, *dist_emb = a.dist_emb;
+    float* const ctx = a.ctx;
+    const int B = a.B, T = a.T, heads = a.heads;
+    const __bf16 *ctx_pieces = a.ctx_pieces, *kv_pieces = a.kv_pieces;
     AT_REQUIRE(ctx_pieces == nullptr && kv_pieces == nullptr, "relpos_attention: piece input / output needs the split kernels");
     dim3 grid((T + ATT_QB - 1) / ATT_QB, heads, B);
     const size_t lds = ATT_LDS_FLOATS * sizeof(float);
@@ -832,8 +844,13 @@ __global__ __launch_bounds__(256) void dwconv_ln_swish_kernel(const float* __res
             range_publish(status, status ? status + 1 : nullptr, over);
 }
 
-int launch_dwconv_ln_swish(const float* g, const float* w, const float* gamma, const float* beta, float* out, int B, int T,
-                           hipStream_t stream, __bf16* pieces, long long rows_pad, int scheme, float scale, int* status) {
+int launch_dwconv_ln_swish(const float* g, const float* w, const float* gamma, const float* beta, float* out, int B, int T, hipStream_t stream,
+                           const SplitOut& split) {
+    __bf16* const pieces = split.pieces;
+    const long long rows_pad = split.rows_pad;
+    const int scheme = split.scheme;
+    const float scale = split.scale;
+    int* const status = split.status;
     constexpr int TT = 16;   // output rows per workgroup: 46 input rows per 16 outputs (8 rows: 38 per 8 — 1.4 ms more per semantic_m step, same box)
     dim3 grid((T + TT - 1) / TT, B);
     if (pieces && scheme == XB_SCHEME_F16X2)
