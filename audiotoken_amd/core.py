@@ -14,31 +14,20 @@ forced by the environment and stated here:
 from __future__ import annotations
 
 import os
-import time
 from pathlib import Path
 from typing import Callable, List, Optional, Union
 
 import numpy as np
 import torch
 
-from .configs import (AUDIO_EXTS, TAR_EXTS, ZIP_EXTS, AcousticDecoderConfig, AcousticEncoderConfig, EncoderConfig, HubertEncoderConfig, Tokenizers,
-                      Wav2VecBertConfig, num_codebooks_to_bandwidth)
-from .harness import batched, collate_fn, iter_chunk, sanitize_path, save_audio_tokens, save_rel_audio_tokens
+from . import encode_files as EF
+from . import runs
+from .configs import (AcousticDecoderConfig, AcousticEncoderConfig, EncoderConfig, HubertEncoderConfig, Tokenizers, Wav2VecBertConfig,
+                      num_codebooks_to_bandwidth)
+from .harness import sanitize_path
 from .logger import get_logger
 
 logger = get_logger(__name__, log_file=None, level="WARNING")
-
-
-def _in_flight(start, items, depth):
-    """``start(item)`` for up to ``depth`` items ahead of the consumer, results in order (``start`` returns immediately: it submits work elsewhere)."""
-    from collections import deque
-    pending = deque()
-    for it in items:
-        pending.append(start(it))
-        if len(pending) >= max(1, depth):
-            yield pending.popleft()
-    while pending:
-        yield pending.popleft()
 
 
 class AudioToken:
@@ -218,72 +207,9 @@ class AudioToken:
         return out
 
     def _chunk_stream(self, files, chunk_size: int, num_workers: int = 0, worker_processes: bool = False):
-        """File -> streamed ``chunk_size``-second chunks -> segments (reference datasets.py:107-139). Decoding and resampling run ``num_workers`` files
-        ahead of the consumer — in SPAWNED worker processes for plain audio files when ``worker_processes`` (the reference's DataLoader workers,
-        core.py:259-267; the parent has the GPU initialised, so never forked), else on a thread pool; archives are streamed member by member by a
-        background thread either way (members are not random-access). The segment order equals the sequential one."""
-        from .audio_io import AudioDecodeError, iterate_tar, iterate_zip, process_audio_chunks
-        from .prefetch import background, ordered_map
-        sr = self.model_config.model_sample_rate
-        pool = None
-        if worker_processes and num_workers > 0:
-            import multiprocessing as mp
-            from concurrent.futures import ProcessPoolExecutor
-            pool = ProcessPoolExecutor(max_workers=num_workers, mp_context=mp.get_context("spawn"))
-
-        def skipped(name, why):   # an undecodable file / archive member: recorded and skipped
-            logger.error(f"Skipping {name}: {why}")
-            self.skipped_files.append((name, why))
-
-        def load(file_path: str):
-            """One unit of host work: plain audio files are decoded completely; archives return a streaming source. A file that
-            cannot be decoded (AudioDecodeError: a codec this build does not ship, more than one channel, a damaged header) is skipped, recorded
-            in ``self.skipped_files`` and reported at the end of the run — it must not abort a run whose earlier files have already been
-            appended to. Any other exception propagates, as in the reference (datasets.py __iter__)."""
-            if file_path.endswith(AUDIO_EXTS):
-                if pool is not None:
-                    from ._workers import decode_chunks
-                    return pool.submit(decode_chunks, file_path, sr, chunk_size)
-                try:
-                    return list(process_audio_chunks(file_path, sr, chunk_size))
-                except AudioDecodeError as e:
-                    skipped(file_path, str(e))
-                    return []
-            if file_path.endswith(TAR_EXTS):
-                return background(lambda: iterate_tar(file_path, sr, chunk_size, skipped)) if num_workers > 0 else iterate_tar(file_path, sr, chunk_size, skipped)
-            if file_path.endswith(ZIP_EXTS):
-                return background(lambda: iterate_zip(file_path, sr, chunk_size, skipped)) if num_workers > 0 else iterate_zip(file_path, sr, chunk_size, skipped)
-            logger.error(f"File {file_path} not supported for processing. Only {AUDIO_EXTS + TAR_EXTS + ZIP_EXTS} supported")
-            self.skipped_files.append((file_path, "unsupported extension"))
-            return []
-
-        def resolve(file_path, source):
-            if pool is not None and hasattr(source, "result"):      # a worker process's answer: numpy chunks, or the reason the file was skipped
-                kind, payload = source.result()
-                if kind == "skip":
-                    skipped(file_path, payload)
-                    return []
-                return [(torch.from_numpy(c), file_path) for c in payload]
-            return source
-
-        names = [str(f) for f in files]
-        try:
-            # with processes `load` only SUBMITS (the thread pool of ordered_map is not needed: in-line submission keeps num_workers futures in flight)
-            sources = ordered_map(lambda f: (f, load(f)), names, num_workers if pool is None else 0) if pool is None else _in_flight(lambda f: (f, load(f)), names, num_workers)
-            for file_path, source in sources:
-                source = resolve(file_path, source)
-                try:
-                    for waveform, file_name in source:
-                        yield from iter_chunk(waveform, file_name, sample_rate=self.model_config.model_sample_rate, chunk_size=chunk_size,
-                                              model_token_rate=self.model_config.model_token_rate, pad_token=self.model_config.pad_token,
-                                              transform=self.transform_func)
-                finally:   # an exception in the consumer (or an abandoned run) must not leave an archive's producer thread and its handle behind
-                    close = getattr(source, "close", None)
-                    if close is not None:
-                        close()
-        finally:
-            if pool is not None:
-                pool.shutdown(wait=False, cancel_futures=True)
+        """The host data flow of ``encode_batch_files``: file -> ``chunk_size``-second chunks -> segments, in order (encode_files.ChunkStream)."""
+        skipped = runs.RunLog(self, "encode_batch_files").skipped
+        return EF.ChunkStream(self, skipped, chunk_size, num_workers, worker_processes).segments(files)
 
     def encode_batch_files(self, batch_size: int, outdir: os.PathLike, chunk_size: int = 30, num_workers: int = 12,
                            audio_files: Optional[List[os.PathLike]] = None, audio_dir: Optional[Union[os.PathLike, Path]] = None,
@@ -315,292 +241,17 @@ class AudioToken:
         assert not (audio_files and audio_dir), "Provide either audio_files or audio_dir, not both"
         outdir = sanitize_path(outdir)
         files = self._input_files(audio_files, audio_dir)
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dataloader_kwargs.get("shard_across_ranks", True):
-            files = self._shard_files(files)
-        if stream:
-            self._encode_files_streamed(files, int(batch_size), outdir, chunk_size, int(num_workers), audio_files, audio_dir, resample,
-                                        dataloader_kwargs.get("max_file_bytes", 4 << 30))
-        else:
-            self._encode_files(files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs)
+        files = runs.shard_if_distributed(self, files, dataloader_kwargs.get("shard_across_ranks", True))
+        EF.encode_files(self, files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, stream, resample, dataloader_kwargs)
 
     @staticmethod
     def _input_files(audio_files, audio_dir, exts=None) -> List[str]:
-        """The inputs of encode_batch_files / fit_quantizer / decode_batch_files: the given files, or every file with a known extension (``exts``; default: the
-        audio and archive extensions) under ``audio_dir``, sorted."""
-        if audio_files is not None:
-            files = [str(f) for f in audio_files]
-        else:
-            # every file under audio_dir with one of the extensions — the set the reference's `glob.iglob(f"{audio_dir}/**/*{ext}", recursive=True)` per
-            # extension finds (datasets.py:47-50; glob does not descend into or match dot-names) — in ONE walk instead of fourteen, sorted (the sharding
-            # below needs every rank to see the same order)
-            exts = tuple(exts) if exts is not None else AUDIO_EXTS + TAR_EXTS + ZIP_EXTS
-            files = []
-            seen = set()    # glob follows symlinked sub-directories (datasets laid out as symlink farms); so does this walk, once per real directory
-            try:            # the root counts as seen: a link cycle back to it must not list its own files a second time
-                st = os.stat(str(audio_dir))
-                seen.add((st.st_dev, st.st_ino))
-            except OSError:
-                pass
-            for d, dirs, names in os.walk(str(audio_dir), followlinks=True):
-                keep = []
-                for x in dirs:
-                    if x.startswith("."):
-                        continue
-                    try:
-                        st = os.stat(os.path.join(d, x))
-                    except OSError:
-                        continue
-                    if (st.st_dev, st.st_ino) not in seen:
-                        seen.add((st.st_dev, st.st_ino))
-                        keep.append(x)
-                dirs[:] = keep
-                files.extend(os.path.join(d, n) for n in names if n.endswith(exts) and not n.startswith("."))
-            files.sort()
-        return files
+        """The inputs of encode_batch_files / fit_quantizer / decode_batch_files (runs.input_files)."""
+        return runs.input_files(audio_files, audio_dir, exts)
 
     def _shard_files(self, files: List[str]) -> List[str]:
-        """This rank's share of the file list under torch.distributed (collective: every rank calls it with the same list)."""
-        import torch.distributed as dist
-        # duration-aware: whole files by greedy LPT on their sizes (distributed.shard_by_size). Rank 0 stats the list ONCE and broadcasts the sizes (N_files
-        # stats instead of N_files x world on a shared filesystem; and every rank provably shards the same numbers)
-        import hashlib
-        from .distributed import collective_device, shard_by_size
-        digest = hashlib.sha256("\0".join(files).encode("utf-8", "surrogateescape")).hexdigest()
-        sizes = [([os.path.getsize(f) if os.path.exists(f) else 0 for f in files], digest)] if dist.get_rank() == 0 else [None]
-        # the pickled list travels on THIS rank's device under RCCL (not torch's current device: a caller that never called set_device would put every rank on cuda:0)
-        dist.broadcast_object_list(sizes, src=0, device=collective_device(torch.device(self.device), dist))
-        sizes, digest0 = sizes[0]
-        # every rank learns whether ALL ranks hold rank 0's list: a rank that differs must stop the others too, not let them encode a shard of a list it does not share
-        from .distributed import gather_scalars
-        same = len(sizes) == len(files) and digest0 == digest
-        votes = gather_scalars([1.0 if same else 0.0], torch.device(self.device), dist)
-        bad = [r for r, v in enumerate(votes) if v[0] != 1.0]
-        assert not bad, f"ranks {bad} see a different file list than rank 0: encode_batch_files needs the same audio_files / audio_dir on every rank"
-        files = [files[i] for i in shard_by_size(sizes, dist.get_rank(), dist.get_world_size())]
-        return files
-
-    def _encode_files(self, files, batch_size, outdir, chunk_size, num_workers, audio_files, audio_dir, dataloader_kwargs) -> None:
-        start_time = time.time()
-        on_gpu = torch.device(self.device).type == "cuda"
-        copy_stream = torch.cuda.Stream(device=self.device) if on_gpu else None
-
-        def upload(batch):
-            """Collate a batch and start its host->device copy (pinned staging, side stream) so it overlaps the encode of
-            the batch before it; returns (ids, masks, file_pointers, ready_event)."""
-            input_ids, attention_masks, file_pointers = collate_fn(batch)
-            if not on_gpu:
-                return input_ids.to(self.device), attention_masks.to(self.device), file_pointers, None
-            with torch.cuda.stream(copy_stream):
-                ids = input_ids.pin_memory().to(self.device, non_blocking=True)
-                masks = attention_masks.pin_memory().to(self.device, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(copy_stream)
-            return ids, masks, file_pointers, ev
-
-        # Device feeder (feeder.py): decoding stays on the host, sample conversion / per-chunk resampling / segmentation / padding run in one HIP kernel per
-        # batch — for semantic_s including its per-chunk zero-mean / unit-variance transform (feeder.py, transform="zmuv"); a custom transform_func and
-        # `device_feeder=False` keep the host data flow of the reference.
-        from .hubert import hubert_processor as _zmuv
-        dev_transform = "zmuv" if self.transform_func is _zmuv else None     # semantic_s: the per-chunk normalisation runs in the feeder's kernels
-        use_feeder = on_gpu and (self.transform_func is None or dev_transform) and dataloader_kwargs.get("device_feeder", True)
-        self.feeder_timings = None
-        if use_feeder:
-            from .feeder import DeviceFeeder
-
-            def skipped(name, why):
-                logger.error(f"Skipping {name}: {why}")
-                self.skipped_files.append((name, why))
-            feeder = DeviceFeeder(self.device, self.model_config.model_sample_rate, chunk_size, self.model_config.model_token_rate,
-                                  self.model_config.pad_token, num_workers, skipped, transform=dev_transform)
-            self.feeder_timings = feeder.timings
-            staged_iter = feeder.batches(files, batch_size)
-            stage_next = lambda: next(staged_iter, None)
-        else:
-            batches = batched(self._chunk_stream(files, chunk_size, num_workers, bool(dataloader_kwargs.get("worker_processes", False))), batch_size)
-
-            def stage_next():
-                b = next(batches, None)
-                return upload(b) if b is not None else None
-        # host seconds per stage of the loop (bench.py's files leg): `stage` = producing the next batch (decode wait + upload + descriptors, or the host
-        # chunk stream + collate + upload), `encode_call` = enqueueing the encode, `device_wait` = blocked on the device (the status read of verified / the
-        # first .cpu()), `save` = the per-row trim + append to the .npy files (of the batch BEFORE, while the device encodes the current one)
-        rt = self.run_timings = {"stage_s": 0.0, "encode_call_s": 0.0, "device_wait_s": 0.0, "save_s": 0.0, "batches": 0, "rows": 0}
-        def save(tokens, pointers):
-            for tokens_batch, file_pointer in zip(tokens, pointers):
-                if audio_files is not None:
-                    save_audio_tokens(tokens_batch, file_pointer, str(outdir))
-                else:
-                    save_rel_audio_tokens(tokens_batch, file_pointer, str(outdir), str(audio_dir))
-
-        t0 = time.perf_counter()
-        staged = stage_next()
-        rt["stage_s"] += time.perf_counter() - t0
-        pending = None    # (tokens on the host, file pointers) of the batch before: written while the device encodes the next one, in batch order
-        try:
-            while staged is not None:
-                input_ids, attention_masks, file_pointers, ev = staged
-                t0 = time.perf_counter()
-                if ev is not None:
-                    torch.cuda.current_stream(self.device).wait_event(ev)
-                    input_ids.record_stream(torch.cuda.current_stream(self.device))
-                    attention_masks.record_stream(torch.cuda.current_stream(self.device))
-                encoded_audio = self.encoder(input_ids, attention_masks)      # asynchronous on the device
-                t1 = time.perf_counter()
-                if pending is not None:
-                    p, pending = pending, None      # ownership first: an interrupt inside the save must not make the `finally` below append the rows again
-                    save(*p)
-                t2 = time.perf_counter()
-                staged = stage_next()                                         # the next batch is decoded / uploaded / cut while this one encodes
-                t3 = time.perf_counter()
-                if hasattr(self.encoder, "verified"):   # the copy below synchronises anyway: check the call's device status first
-                    encoded_audio = self.encoder.verified(encoded_audio, input_ids, attention_masks)
-                pending = (encoded_audio.cpu(), file_pointers)   # ONE device-to-host copy per batch (a per-row .cpu() inside the save would synchronise B times)
-                t4 = time.perf_counter()
-                rt["encode_call_s"] += t1 - t0; rt["save_s"] += t2 - t1; rt["stage_s"] += t3 - t2; rt["device_wait_s"] += t4 - t3
-                rt["batches"] += 1; rt["rows"] += len(file_pointers)
-        finally:
-            # also when the encode / staging of batch k raised: the verified tokens of batch k - 1 are on the host and belong in their files (earlier
-            # batches are already there) — the save is deferred by one batch, it must not be lost by it
-            if pending is not None:
-                t0 = time.perf_counter()
-                p, pending = pending, None
-                save(*p)
-                rt["save_s"] += time.perf_counter() - t0
-            try:
-                self._end_of_run()
-            except Exception as e:   # bookkeeping must not mask the exception that ended the run
-                logger.error(f"encode_batch_files: end-of-run bookkeeping failed: {type(e).__name__}: {e}")
-        rt["total_s"] = time.time() - start_time
-        logger.debug(f"Encoding batch files took: {time.time() - start_time:.2f}s")
-        if self.skipped_files:
-            logger.error(f"encode_batch_files: {len(self.skipped_files)} input(s) were skipped and have NO token file (AudioToken.skipped_files): "
-                         + "; ".join(f"{p} ({why})" for p, why in self.skipped_files[:8]) + (" ..." if len(self.skipped_files) > 8 else ""))
-
-    def _encode_files_streamed(self, files, batch_size: int, outdir, chunk_size, num_workers: int, audio_files, audio_dir, resample: str = "chunk",
-                               max_file_bytes: int = 4 << 30) -> None:
-        """``encode_batch_files(stream=True)``: ticks over a stream pool (writer.plan_encode_stream_ticks). A tick: every live file's next chunk is pushed,
-        the files whose chunks are exhausted are flushed (their slots go to the next files, in order), the tick's new frames come to the host in ONE copy
-        and are appended to the token files. ``resample="file"``: a file's units are the ticks of its resident PCM (resample_stream.ResidentFiles) and a
-        tick's chunks come out of one resample launch."""
-        from .audio_io import AudioDecodeError, process_audio_chunks
-        from .configs import AudioConfig
-        from .prefetch import ordered_map
-        from .writer import plan_encode_stream_ticks
-        start_time = time.time()
-        sr, rate = self.model_config.model_sample_rate, self.model_config.model_token_rate
-        self.feeder_timings = None
-        rt = self.run_timings = {"stage_s": 0.0, "encode_call_s": 0.0, "device_wait_s": 0.0, "save_s": 0.0, "batches": 0, "rows": 0}
-
-        def skipped(name, why):
-            logger.error(f"Skipping {name}: {why}")
-            self.skipped_files.append((name, why))
-
-        def load(path: str):
-            """One file's chunks, decoded ``num_workers`` files ahead: (path, [samples [n] per chunk] or None, reason)."""
-            if not path.endswith(AUDIO_EXTS):
-                return path, None, ("stream=True takes plain audio files: archives are not streamed" if path.endswith(TAR_EXTS + ZIP_EXTS)
-                                    else "unsupported extension")
-            try:
-                return path, [chunk[0] for chunk, _ in process_audio_chunks(path, sr, chunk_size)], None
-            except AudioDecodeError as e:
-                return path, None, str(e)
-
-        opened: list = []     # position in the tick plan -> [path, chunks]
-
-        resident = None
-        if resample == "file":
-            from .resample_stream import ResidentFiles
-            resident = ResidentFiles(self.device, sr, chunk_size, num_workers, skipped, max_file_bytes=max_file_bytes, min_samples=321)
-
-        def chunk_counts():
-            if resident is not None:
-                for f in resident.open_all(files):    # [name, the file on the device]: its PCM is released with this entry, after its flush
-                    opened.append([f.name, f])
-                    yield range(f.ticks)
-                return
-            for path, chunks, why in ordered_map(load, [str(f) for f in files], num_workers):
-                if chunks is None:
-                    skipped(path, why)
-                elif sum(int(c.shape[-1]) for c in chunks) < 321:   # the library's rule for a clip (a stream whose first push is its last is a one-shot encode)
-                    skipped(path, "fewer than 321 samples")
-                else:
-                    opened.append([path, chunks])
-                    yield [int(c.shape[-1]) for c in chunks]
-
-        def save(path: str, codes: torch.Tensor):
-            pointer = AudioConfig(file_name=path, length_seconds=codes.shape[-1] / rate, model_token_rate=rate)
-            if audio_files is not None:
-                save_audio_tokens(codes, pointer, str(outdir))
-            else:
-                save_rel_audio_tokens(codes, pointer, str(outdir), str(audio_dir))
-
-        pool = self.encoder.new_stream_pool(batch_size)
-        sids: dict = {}
-        try:
-            ticks = plan_encode_stream_ticks(chunk_counts(), batch_size)
-            while True:
-                t0 = time.perf_counter()
-                tick = next(ticks, None)        # opens (waits for) the files that take the free slots
-                if tick is None:
-                    break
-                feed = {}
-                for r in tick:
-                    if r.file not in sids:
-                        sids[r.file] = pool.open()
-                    if resident is None:
-                        chunks = opened[r.file][1]
-                        feed[sids[r.file]], chunks[r.t0] = chunks[r.t0], None
-                if resident is not None:
-                    for r, x in zip(tick, resident.chunks([(opened[r.file][1], r.t0) for r in tick])):
-                        feed[sids[r.file]] = x
-                t1 = time.perf_counter()
-                out = pool.push(feed)           # every group's status word is read in there: the tokens are verified when it returns
-                last = [r.file for r in tick if r.last]
-                fin = pool.flush([sids[i] for i in last]) if last else {}
-                t2 = time.perf_counter()
-                parts = []
-                for r in tick:
-                    sid = sids[r.file]
-                    parts.append(torch.cat([out[sid], fin[sid]], dim=-1) if sid in fin else out[sid])
-                host = torch.cat(parts, dim=-1).cpu()   # ONE device-to-host copy per tick
-                t3 = time.perf_counter()
-                pos = 0
-                for r, p in zip(tick, parts):
-                    t = p.shape[-1]
-                    if t:
-                        save(opened[r.file][0], host[:, pos:pos + t])
-                    pos += t
-                for i in last:
-                    del sids[i]
-                    opened[i] = None
-                t4 = time.perf_counter()
-                rt["stage_s"] += t1 - t0; rt["encode_call_s"] += t2 - t1; rt["device_wait_s"] += t3 - t2; rt["save_s"] += t4 - t3
-                rt["batches"] += 1; rt["rows"] += len(tick)
-        finally:
-            try:
-                self._end_of_run()
-                self.run_summary["library_pushes"] = pool.library_pushes
-                if resident is not None:
-                    self.run_summary["resample_launches"] = resident.resampler.launches
-                    resident.finish()
-            except Exception as e:   # bookkeeping must not mask the exception that ended the run
-                logger.error(f"encode_batch_files: end-of-run bookkeeping failed: {type(e).__name__}: {e}")
-        rt["total_s"] = time.time() - start_time
-        if self.skipped_files:
-            logger.error(f"encode_batch_files: {len(self.skipped_files)} input(s) were skipped and have NO token file (AudioToken.skipped_files): "
-                         + "; ".join(f"{p} ({why})" for p, why in self.skipped_files[:8]) + (" ..." if len(self.skipped_files) > 8 else ""))
-
-    def _end_of_run(self):
-        """End of an encode_batch_files run: layers the range fallback moved to bf16x3 because of THIS run's inputs go back to f16x2 (a loud or clipped file
-        must not slow down, or change the rounding of, every later run of the process); what happened is kept in ``run_summary``."""
-        enc = self.encoder
-        self.run_summary = {"fallback_batches": getattr(enc, "fallback_batches", 0), "pinned_layers": sorted(set(getattr(enc, "pinned_layers", []) or [])),
-                            "nonfinite_batches": getattr(enc, "nonfinite_batches", 0), "skipped_files": len(self.skipped_files)}
-        if self.run_summary["pinned_layers"]:
-            logger.error(f"encode_batch_files: layers {self.run_summary['pinned_layers']} ran on bf16x3 for part of this run (fp16 range overflow); restored to f16x2")
-        if hasattr(enc, "unpin_layers"):
-            enc.unpin_layers()
+        """This rank's share of the file list under torch.distributed (collective: every rank calls it with the same list; runs.shard_files)."""
+        return runs.shard_files(self, files)
 
     # code-book sizes the tokenizers' finalize() accepts (csrc/w2vbert.hip, csrc/hubert.hip): (clusters, width, LayerNorm kernel of the quantiser step)
     _FIT_SHAPES = {Tokenizers.semantic_m: (2048, 1024, 1), Tokenizers.semantic_s: (1000, 768, 0)}
@@ -616,8 +267,7 @@ class AudioToken:
         LayerNorm kernel, in file / segment / frame order. ``keep_fraction`` keeps a frame by a counter-based draw keyed on (file, segment, frame);
         ``max_frames`` caps the sample. Local to this process: no collectives, also under torch.distributed. Returns the fitted ``KMeans``."""
         from . import _cabi
-        from .kmeans import KMeans, plusplus_uniforms, save_kmeans, save_vq  # noqa: F401
-        from . import prng
+        from .kmeans import KMeans, save_kmeans, save_vq
         if self.tokenizer_name not in self._FIT_SHAPES:
             raise ValueError(f"fit_quantizer: {self.tokenizer_name} has no semantic code book to fit (semantic_m or semantic_s)")
         k, d, split_ln = self._FIT_SHAPES[self.tokenizer_name]
@@ -651,61 +301,16 @@ class AudioToken:
         enc.eval()
         files = self._input_files(audio_files, audio_dir)
         self.skipped_files = []
-
-        def skipped(name, why):
-            logger.error(f"Skipping {name}: {why}")
-            self.skipped_files.append((name, why))
-        from .feeder import DeviceFeeder
-        from .hubert import hubert_processor
-        transform = "zmuv" if self.tokenizer_name == Tokenizers.semantic_s else None
-        assert self.tokenizer_name != Tokenizers.semantic_s or self.transform_func in (None, hubert_processor)
-        feeder = DeviceFeeder(self.device, self.model_config.model_sample_rate, chunk_size, self.model_config.model_token_rate,
-                              self.model_config.pad_token, num_workers, skipped, transform=transform)
-        frames = torch.empty((max_frames, d), dtype=torch.float32, device=dev)
-        filled, truncated, batches, seen = 0, False, 0, 0
+        log = runs.RunLog(self, "fit_quantizer")
         fb0 = getattr(enc, "fallback_batches", 0)
-        stream = torch.cuda.current_stream(dev)
-        for input_ids, masks, pointers, ev in feeder.batches(files, batch_size):
-            if ev is not None:
-                stream.wait_event(ev)
-                input_ids.record_stream(stream)
-                masks.record_stream(stream)
-            hidden = enc(input_ids, masks)
-            hidden = enc.verified(hidden, input_ids, masks)      # an fp16 range overflow: the batch is re-encoded before any frame is taken
-            batches += 1
-            B, T, _ = hidden.shape
-            rows = hidden.reshape(B * T, d)
-            y = torch.empty_like(rows)
-            ws = torch.empty(((B * T + 7) // 8 * 8) * d * 4 if split_ln else 1, dtype=torch.uint8, device=dev)
-            _cabi.check(lib.at_kmeans_layernorm(rows.data_ptr(), y.data_ptr(), B * T, d, split_ln, ws.data_ptr(), ws.numel(),
-                                                _cabi.current_stream_handle(dev)), "at_kmeans_layernorm")
-            keep = []
-            for b, p in enumerate(pointers):
-                n_valid = min(T, int(p.length_tokens))
-                seen += n_valid
-                idx = np.arange(n_valid, dtype=np.int64)
-                if keep_fraction < 1.0:
-                    u = prng.uniform01(f"fit_quantizer|{p.file_name}|{int(getattr(p, 'start_idx', 0))}", n_valid, seed)
-                    idx = idx[u < np.float32(keep_fraction)]
-                keep.append(b * T + idx)
-            sel = np.concatenate(keep) if keep else np.zeros(0, np.int64)
-            if filled + len(sel) > max_frames:
-                sel = sel[:max_frames - filled]
-                truncated = True
-            if len(sel):
-                frames[filled:filled + len(sel)] = y[torch.from_numpy(sel).to(dev)]
-                filled += len(sel)
-            if truncated:
-                break
-        if truncated:
+        X, sample = EF.collect_frames(self, log, enc, files, chunk_size, batch_size, num_workers, max_frames, d, split_ln, keep_fraction, seed)
+        if sample["truncated"]:
             logger.warning(f"fit_quantizer: the sample reached max_frames = {max_frames}; later frames were not used")
-        if filled < k:
-            raise ValueError(f"fit_quantizer: {filled} frames collected, fewer than the {k} codes to fit")
-        X = frames[:filled]
+        if len(X) < k:
+            raise ValueError(f"fit_quantizer: {len(X)} frames collected, fewer than the {k} codes to fit")
         km = KMeans(k, init=init, n_init=n_init, max_iter=max_iter, tol=tol, seed=seed, device=self.device)
         km.fit(X)
-        km.fit_summary_ = {"frames": filled, "frames_seen": seen, "batches": batches, "truncated": truncated,
-                           "fallback_batches": getattr(enc, "fallback_batches", 0) - fb0, "skipped_files": len(self.skipped_files)}
+        km.fit_summary_ = {**sample, "fallback_batches": getattr(enc, "fallback_batches", 0) - fb0, "skipped_files": len(self.skipped_files)}
         if self.tokenizer_name == Tokenizers.semantic_m:
             save_vq(path, km.cluster_centers_)
         else:
@@ -815,22 +420,20 @@ class AudioToken:
         self.skipped_files = []
         outdir = sanitize_path(outdir)
         files = self._input_files(token_files, token_dir, exts=(".npy",))
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and kwargs.get("shard_across_ranks", True):
-            files = self._shard_files(files)
+        files = runs.shard_if_distributed(self, files, kwargs.get("shard_across_ranks", True))
+        log = runs.RunLog(self, "decode_batch_files", "audio")
         inputs, taken = [], {}
         for f in files:
             out = Wr.output_path(f, outdir, None if token_files else str(token_dir), audio_format)
             if out in taken:
-                logger.error(f"Skipping {f}: its output {out} is already that of {taken[out]}")
-                self.skipped_files.append((f, f"duplicate output name: {out} is already written from {taken[out]}"))
+                log.skipped(f, f"duplicate output name: {out} is already written from {taken[out]}")
                 continue
             taken[out] = f
             inputs.append((f, out))
         on_gpu = torch.device(self.device).type == "cuda"
         Wr.decode_files(self, inputs, int(batch_size), chunk_size, int(num_workers), bool(rescale), bool(kwargs.get("device_writer", on_gpu)),
                         int(kwargs.get("max_held_bytes", Wr.DEFAULT_MAX_HELD_BYTES)), self.model_config.model_sample_rate, self.model_config.model_token_rate,
-                        audio_format, bool(stream))
+                        audio_format, bool(stream), log=log)
 
     def _decode_single(self, tokens: torch.Tensor) -> torch.Tensor:
         """core.py:355-359."""

@@ -1,5 +1,6 @@
 """Output side of ``decode_batch_files``: a tree of ``.npy`` token files -> a tree of 16-bit PCM WAV files, or of FLAC files
-(``audio_format="flac"``: the same samples, compressed on the device by csrc/flac_encode.hip, framed on the host).
+(``audio_format="flac"``: the same samples, compressed on the device by csrc/flac_encode.hip, framed on the host). Here: reading and validating token
+files, the batch and tick planners, the WAV / FLAC file writers and the device / host pack backends; the run that drives them is decode_files.py.
 
 The mirror image of feeder.py. The split is the same one:
 
@@ -18,18 +19,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-import time
 from dataclasses import dataclass, field
 from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .audio_io import PCM_LIMIT, pcm16_from_float, rescale_factor
-from .logger import get_logger
-from .prefetch import ordered_map
-
-logger = get_logger(__name__)
+from .audio_io import PCM_LIMIT, pcm16_from_float
 
 HOP = 320                     # samples per frame (24 kHz / 75 Hz)
 MIN_FRAMES = 7                # a one-shot decode needs 7 frames: shorter rows are padded up to it and trimmed
@@ -586,253 +582,8 @@ class HostFlacWriter(HostWriter):
         return _FlacPacked(recs, data, counts, self.sample_rate)
 
 
-# ---- the run ----------------------------------------------------------------------------------------------------------------------------------------------------
-@dataclass
-class _File:
-    path: str
-    out: str
-    tokens: Optional[np.ndarray] = None
-    rows_left: int = 0                  # segments not yet decoded
-    peak: np.float32 = np.float32(0.0)  # rescale=True: max over the rows decoded so far
-    held_bytes: int = 0
-    dropped: bool = False               # skipped after its first row was planned (max_held_bytes, a write error)
-    writer: Optional[object] = None     # WavWriter / FlacWriter
-    written: bool = False
-
-
-def decode_files(tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_size, num_workers: int, rescale: bool, device_writer: bool,
-                 max_held_bytes: int, sample_rate: int, token_rate: int, audio_format: str = "wav", stream: bool = False) -> None:
-    """The loop of ``AudioToken.decode_batch_files``: ``inputs`` = (token file, output path) in order. ``tok`` supplies ``decoder`` (``forward`` /
-    ``verified``), ``device``, ``skipped_files``; ``run_summary`` / ``run_timings`` are left on it.
-
-    ``stream=True``: every file is ONE clip. Up to ``batch_size`` files are live, one slot of a decode stream pool each
-    (``decoder.new_stream_pool``); per tick (``plan_stream_ticks``) every live file pushes its next ``chunk_size * 75`` frames and the pool batches the rows of
-    equal phase, K and length. The audio of a tick goes through the same writers as a batch's; a file below 7 frames is padded with ``PAD_CODE`` and
-    trimmed, as the segments of the chunked route are."""
-    start_time = time.time()
-    dec = tok.decoder
-    device = torch.device(tok.device)
-    num_codebooks = int(getattr(getattr(dec, "_h", None), "n_codebooks", tok.num_codebooks))
-    assert audio_format in AUDIO_FORMATS
-    if audio_format == "flac":
-        backend = DeviceFlacWriter(device, sample_rate) if device_writer else HostFlacWriter(device, sample_rate)
-    else:
-        backend = DeviceWriter(device) if device_writer else HostWriter(device)
-    fb0 = getattr(dec, "fallback_batches", 0)
-    summary = tok.run_summary = {"files": 0, "segments": 0, "batches": 0, "fallback_batches": 0, "clipped_samples": 0, "nonfinite_samples": 0,
-                                 "skipped_files": 0, "audio_bytes": 0}
-    # host seconds per stage, the keys of the encode loop: `stage` = the next batch's token files (read-ahead wait, validation, padding, upload),
-    # `encode_call` = enqueueing the decode, `device_wait` = blocked on the device (the status read of `verified`, the peaks), `save` = writing the PCM of the
-    # batches before (while the device decodes the current one)
-    rt = tok.run_timings = {"stage_s": 0.0, "encode_call_s": 0.0, "device_wait_s": 0.0, "save_s": 0.0, "batches": 0, "rows": 0}
-
-    def skipped(name, why):
-        logger.error(f"Skipping {name}: {why}")
-        tok.skipped_files.append((name, why))
-
-    files: dict = {}
-
-    def load(item):
-        i, (path, out) = item
-        try:
-            return i, path, out, read_token_file(path, num_codebooks, audio_format), None
-        except TokenFileError as e:
-            return i, path, out, None, str(e)
-
-    def valid_files():
-        for i, path, out, tokens, why in ordered_map(load, list(enumerate(inputs)), num_workers):
-            if tokens is None:
-                skipped(path, why)
-                continue
-            K, T = tokens.shape
-            step = chunk_frames_of(chunk_size, token_rate)
-            files[i] = _File(path, out, tokens, rows_left=1 if step is None else (T + step - 1) // step)
-            yield i, K, T
-
-    def drop(f: _File, why: str):
-        if not f.dropped:
-            f.dropped = True
-            if f.writer is not None:
-                f.writer.abort()
-                f.writer = None
-            skipped(f.path, why)
-
-    plans = plan_batches(valid_files() if not stream else (), batch_size, chunk_frames_of(chunk_size, token_rate))   # (the streamed run has ticks instead)
-    held: List[list] = []       # [plan, float rows (device tensor / host array)] decoded but not packed: rescale=True waits for the last row of a file
-    pending: List[tuple] = []   # (plan rows packed, _Packed): packed, on their way to the host, not yet written
-
-    def write_pending():
-        while pending:
-            rows, packed = pending.pop(0)
-            try:
-                counts = packed.result()[-1]
-                for j, (r, d, n) in enumerate(rows):
-                    f = files[r.file]
-                    if f.dropped:
-                        continue
-                    try:
-                        if f.writer is None:
-                            f.writer = open_writer(f.out, sample_rate, audio_format)
-                        packed.write_row(f.writer, j, d, n)
-                        summary["clipped_samples"] += int(counts[j, 0])
-                        summary["nonfinite_samples"] += int(counts[j, 1])
-                        if r.last:
-                            w, f.writer = f.writer, None
-                            w.close()
-                            f.written = True
-                            summary["files"] += 1
-                            summary["audio_bytes"] += (44 if audio_format == "wav" else 0) + w.data_bytes
-                    except (OSError, WavTooLarge, FlacTooLarge) as e:
-                        drop(f, f"cannot write {f.out}: {type(e).__name__}: {e}")
-            finally:
-                packed.release()
-
-    def release_held():
-        """Pack every held batch whose files are all complete (clamp mode: every batch, at once), in order."""
-        while held:
-            plan, rows_f = held[0]
-            # (batches are in file order, so only the LAST row's file can be incomplete; a tick of a streamed run has a row of every live file)
-            if rescale and any(files[r.file].rows_left > 0 and not files[r.file].dropped for r in (plan.rows if stream else plan.rows[-1:])):
-                break
-            held.pop(0)
-            keep, pack_rows, pos = [], [], 0
-            for b, r in enumerate(plan.rows):
-                f = files[r.file]
-                if f.dropped:
-                    continue
-                keep.append((r, pos, plan.n[b]))
-                pack_rows.append((plan.src_off[b], pos, plan.n[b], float(rescale_factor(f.peak)) if rescale else 1.0))
-                pos += plan.n[b]
-            if keep:
-                pending.append((keep, backend.pack(rows_f, pack_rows)))
-            for r in plan.rows:
-                if r.last:      # (no later batch holds a row of it)
-                    files[r.file].tokens = None
-
-    def run_ticks():
-        """The streamed run. A tick: upload and push the live files' next frames (the pool reads every group's status word: the audio is verified when
-        ``push`` returns), write what the ticks before packed, then hold / pack this tick's audio as a batch's."""
-        pool = dec.new_stream_pool(batch_size)
-        order: List[int] = []      # position in the tick plan -> file id
-
-        def shapes():
-            for i, K, T in valid_files():
-                order.append(i)
-                yield K, T
-
-        sids: dict = {}
-        for tick in plan_stream_ticks(shapes(), batch_size, chunk_frames_of(chunk_size, token_rate)):
-            t0 = time.perf_counter()
-            rows, feed, trim = [], {}, {}
-            for r in tick:
-                i = order[r.file]
-                f = files[i]
-                f.rows_left -= 1
-                if f.dropped:
-                    if i in sids:
-                        pool.close(sids.pop(i))
-                    continue
-                if i not in sids:
-                    sids[i] = pool.open()
-                x = f.tokens[:, r.t0:r.t0 + r.valid]
-                if r.last and r.t0 + r.valid < MIN_FRAMES:     # the whole file is below a first push's 7 frames: "no code" frames behind it, cut off again below
-                    trim[i] = HOP * (r.t0 + r.valid)
-                    x = np.concatenate([x, np.full((x.shape[0], MIN_FRAMES - (r.t0 + r.valid)), PAD_CODE, dtype=np.int64)], axis=1)
-                feed[sids[i]] = torch.from_numpy(np.ascontiguousarray(x))
-                rows.append(SegmentRow(i, r.t0, r.valid, r.last))
-            t1 = time.perf_counter()
-            out = pool.push(feed) if feed else {}
-            outs = [out[sids[r.file]][:trim.get(r.file)] for r in rows]
-            done = [sids.pop(r.file) for r in rows if r.last]
-            if done:
-                pool.flush(done)                                # started streams hold nothing: this frees their slots
-            t2 = time.perf_counter()
-            write_pending()
-            t3 = time.perf_counter()
-            emitted = [(r, o) for r, o in zip(rows, outs) if o.numel() > 0]    # (a file's first ticks emit nothing while it holds fewer than 7 frames)
-            if emitted:
-                plan = BatchPlan(0, [r for r, _ in emitted])
-                plan.n = [int(o.numel()) for _, o in emitted]
-                plan.src_off = plan.dst_off = [sum(plan.n[:b]) for b in range(len(plan.n))]
-                plan.total = sum(plan.n)
-                rows_f = backend.hold(torch.cat([o for _, o in emitted]))
-                if rescale:
-                    pk = backend.peaks(rows_f, [(plan.src_off[b], 0, plan.n[b], 1.0) for b in range(len(plan.rows))])
-                    for b, r in enumerate(plan.rows):
-                        f = files[r.file]
-                        f.peak = max(f.peak, np.float32(pk[b]))
-                        f.held_bytes += 4 * plan.n[b]
-                        if f.held_bytes > max_held_bytes:
-                            drop(f, f"rescale=True holds the file's float rows on the device until its last row: more than max_held_bytes = {max_held_bytes}")
-                held.append([plan, rows_f])
-                del rows_f
-            del out, outs, emitted
-            release_held()
-            t4 = time.perf_counter()
-            rt["stage_s"] += t1 - t0; rt["encode_call_s"] += t2 - t1; rt["save_s"] += t3 - t2; rt["device_wait_s"] += t4 - t3
-            rt["batches"] += 1; rt["rows"] += len(rows)
-            summary["batches"] += 1; summary["segments"] += len(rows)
-        summary["library_pushes"] = pool.library_pushes
-
-    ok = False
-    try:
-        t0 = time.perf_counter()
-        plan = next(plans, None)
-        toks = padded_tokens(plan, lambda i: files[i].tokens).to(device) if plan is not None else None
-        rt["stage_s"] += time.perf_counter() - t0
-        while plan is not None:
-            t0 = time.perf_counter()
-            wav = dec.forward(toks)                           # asynchronous on the device
-            t1 = time.perf_counter()
-            write_pending()                                   # the batches before: their copies ran behind the decode before this one
-            t2 = time.perf_counter()
-            nxt = next(plans, None)                           # the next batch's tokens are read / padded / uploaded while this one decodes
-            nxt_toks = padded_tokens(nxt, lambda i: files[i].tokens).to(device) if nxt is not None else None
-            t3 = time.perf_counter()
-            if hasattr(dec, "verified"):
-                wav = dec.verified(wav, toks)                 # the correctness ladder: no audio is accepted before the call's status was read
-            rows_f = backend.hold(wav)
-            if rescale:
-                pk = backend.peaks(rows_f, [(plan.src_off[b], 0, plan.n[b], 1.0) for b in range(len(plan.rows))])
-            for b, r in enumerate(plan.rows):
-                f = files[r.file]
-                f.rows_left -= 1
-                if rescale and not f.dropped:
-                    f.peak = max(f.peak, np.float32(pk[b]))
-                    f.held_bytes += 4 * HOP * plan.t_max
-                    if f.held_bytes > max_held_bytes:
-                        drop(f, f"rescale=True holds the file's float rows on the device until its last row: more than max_held_bytes = {max_held_bytes}")
-            held.append([plan, rows_f])
-            del wav, rows_f
-            release_held()
-            t4 = time.perf_counter()
-            rt["encode_call_s"] += t1 - t0; rt["save_s"] += t2 - t1; rt["stage_s"] += t3 - t2; rt["device_wait_s"] += t4 - t3
-            rt["batches"] += 1; rt["rows"] += len(plan.rows)
-            summary["batches"] += 1; summary["segments"] += len(plan.rows)
-            plan, toks = nxt, nxt_toks
-        if stream:
-            run_ticks()
-        t0 = time.perf_counter()
-        write_pending()
-        rt["save_s"] += time.perf_counter() - t0
-        ok = True
-    finally:
-        # also when a decode raised: what was verified and packed before it belongs in its files; then every file still open is incomplete and is removed
-        try:
-            if not ok:
-                write_pending()
-        except Exception as e:   # noqa: BLE001 — must not mask the exception that ended the run
-            logger.error(f"decode_batch_files: writing the batches before the failure failed too: {type(e).__name__}: {e}")
-        for _, packed in pending:
-            packed.release()
-        for f in files.values():
-            if f.writer is not None:
-                f.writer.abort()
-                f.writer = None
-        summary["fallback_batches"] = getattr(dec, "fallback_batches", 0) - fb0
-        summary["skipped_files"] = len(tok.skipped_files)
-        rt["total_s"] = time.time() - start_time
-        rt["bytes_downloaded"] = backend.bytes_downloaded
-    if tok.skipped_files:
-        logger.error(f"decode_batch_files: {len(tok.skipped_files)} input(s) were skipped and have NO audio file (AudioToken.skipped_files): "
-                     + "; ".join(f"{p} ({why})" for p, why in tok.skipped_files[:8]) + (" ..." if len(tok.skipped_files) > 8 else ""))
+# ---- the run: decode_files.py ------------------------------------------------------------------------------------------------------------------------------------
+def decode_files(tok, inputs, *args, **kwargs) -> None:
+    """``decode_files.decode_files``, under the name it had when it lived here (that module imports this one)."""
+    from .decode_files import decode_files as run
+    run(tok, inputs, *args, **kwargs)
