@@ -202,6 +202,17 @@ SIGNATURES = {
     "at_op_rvq_encode_split": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "at_op_rvq_encode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_gpt_create": (C.c_void_p, [C.c_int]),
+    "at_gpt_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "at_gpt_finalize": (C.c_int, [C.c_void_p]),
+    "at_gpt_destroy": (None, [C.c_void_p]),
+    "at_gpt_num_layers": (C.c_int, [C.c_void_p]),
+    "at_gpt_vocab": (C.c_int, [C.c_void_p]),
+    "at_gpt_block_size": (C.c_int, [C.c_void_p]),
+    "at_gpt_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "at_gpt_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p,
+                                  C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_op_topk_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
 }
 
 

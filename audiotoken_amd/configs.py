@@ -78,6 +78,31 @@ class Wav2VecBertConfig(EncoderConfig):
 
 
 @dataclass
+class HubertDecoderConfig:
+    """The semantic_s -> acoustic token space of the reference's semantic decoder (its stage 1, a GPT over one shared vocabulary): text ids, then the
+    semantic ids, then the acoustic ids with their control tokens. Constants only: nothing is fetched from a hub."""
+    TEXT_VOCAB_SIZE: int = 50257
+    SEMANTIC_VOCAB_SIZE: int = 1000
+    ACOUSTIC_VOCAB_SIZE: int = 2048
+    SEMANTIC_OFFSET: int = 50257
+    ACOUSTIC_OFFSET: int = 51257
+    INFER_TOKEN: int = 53311     # "now produce acoustic ids": appended to the source
+    STOP_TOKEN: int = 53314      # end of the acoustic sequence
+    VOCAB_SIZE: int = 53376
+    max_source_tokens: int = 256
+    num_codebooks: int = 2       # the coarse code books stage 1 produces
+    codebook_size: int = 1024
+    weights: Optional[str] = os.environ.get("AUDIOTOKEN_HUBERT_DECODER_WEIGHTS")
+
+
+@dataclass
+class Wav2VecBertDecoderConfig(HubertDecoderConfig):
+    """The same token space for semantic_m sources; the reference keeps a shorter source there."""
+    max_source_tokens: int = 250
+    weights: Optional[str] = os.environ.get("AUDIOTOKEN_W2VBERT_DECODER_WEIGHTS")
+
+
+@dataclass
 class AudioConfig:
     """Per-chunk metadata (reference audiotoken/configs.py:190-218)."""
     file_name: str

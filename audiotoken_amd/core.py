@@ -317,8 +317,34 @@ class AudioToken:
             save_kmeans(path, km)
         return km
 
+    def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0, uniforms=None,
+                    constrain: bool = False, return_logits: bool = False):
+        """Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoder (its GPT, ``decoder.py:210-239``) on the
+        KV-cached HIP decoder (semantic_decoder.py). Semantic tokenizers only. ``tokens``: a tensor / array / path of semantic ids (any
+        shape, flattened), or a list of up to 64 of them, generated as one batch. Returns an ``AcousticGeneration``: ``codes`` (a list of int64
+        ``[2, T_b]`` that ``AudioToken(Tokenizers.acoustic, num_codebooks=2).decode`` takes; None where the ids do not deserialise), ``ids``,
+        ``finish`` ("stop" | "max_new_tokens" | "block_size") and, with ``return_logits``, the per-step logits.
+        The draws are ``uniforms`` (float32 ``[B, max_new_tokens]``) or, from ``seed``, ``np.random.Generator(np.random.Philox(seed)).random(...)``: not
+        ``torch.multinomial``'s stream, but the same distribution. ``constrain=True`` lets step s produce only ids of code book ``s % 2`` (and STOP on even
+        s), so that every result is a valid ``[2, T]``; the default samples the reference's unconstrained distribution. Weights: the constructor's
+        ``decoder_weights=`` (a checkpoint path or a ``{name: array}`` dict), else the seeded synthetic model."""
+        if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
+            raise ValueError(f"to_acoustic maps semantic ids to acoustic code books; {self.tokenizer_name} has no semantic ids")
+        if getattr(self, "semantic_decoder", None) is None:
+            from .configs import HubertDecoderConfig, Wav2VecBertDecoderConfig
+            from .semantic_decoder import SemanticToAcoustic
+            cfg = HubertDecoderConfig() if self.tokenizer_name == Tokenizers.semantic_s else Wav2VecBertDecoderConfig()
+            w = self.kwargs.get("decoder_weights")
+            if w is None and cfg.weights is None:
+                logger.warning("to_acoustic: no decoder_weights given; using the seeded synthetic GPT")
+            self.semantic_decoder = SemanticToAcoustic(cfg, device=self.device, weights=w)
+        return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
+                                                 constrain=constrain, return_logits=return_logits)
+
     def load_decoder(self, **kwargs):
-        """core.py:291-315 — only the acoustic decoder exists here (the semantic decoders are out of scope)."""
+        """core.py:291-315. Built: the acoustic decoder. Of the semantic decoders, stage 1 (semantic ids -> the two coarse code books, a GPT) is built under
+        its own name, ``to_acoustic``; the fine stage (bark, code books 3 to 8) is absent, so the semantic ``decode`` and this loader still raise
+        ``NotImplementedError`` for the semantic tokenizers."""
         if self.decoder is None:
             if self.tokenizer_name == Tokenizers.acoustic:
                 from .decoder import AcousticDecoder
@@ -334,7 +360,8 @@ class AudioToken:
                                                  torch.device(self.device), dist, "acoustic decoder")
                 self.decoder = AcousticDecoder(config=cfg, device=self.device, weights=wkw, **kwargs)
             elif self.tokenizer_name in (Tokenizers.semantic_s, Tokenizers.semantic_m):
-                raise NotImplementedError("semantic decoders (autoregressive GPT + bark fine model) are out of scope of the MI355X hot path")
+                raise NotImplementedError("the semantic decode needs the bark fine model, which is not built; stage 1 (semantic ids -> two coarse code "
+                                          "books) is AudioToken.to_acoustic")
             else:
                 raise ValueError(f"Tokenizer {self.tokenizer_name} not supported")
             self.decoder.eval()

@@ -129,6 +129,24 @@ std::vector<Entry> hubert(int n_layers, bool kmeans) {
     if (kmeans) v.push_back({"kmeans.cluster_centers_", {1000, H}});
     return v;
 }
+
+std::vector<Entry> gpt(int n_layers) {
+    std::vector<Entry> v;
+    const int H = 768, F = 3072;
+    v.push_back({"transformer.wte.weight", {53376, H}});
+    v.push_back({"transformer.wpe.weight", {1024, H}});
+    for (int i = 0; i < n_layers; ++i) {
+        const std::string p = "transformer.h." + std::to_string(i);
+        v.push_back({p + ".ln_1.weight", {H}});
+        v.push_back({p + ".attn.c_attn.weight", {3 * H, H}});
+        v.push_back({p + ".attn.c_proj.weight", {H, H}});
+        v.push_back({p + ".ln_2.weight", {H}});
+        v.push_back({p + ".mlp.c_fc.weight", {F, H}});
+        v.push_back({p + ".mlp.c_proj.weight", {H, F}});
+    }
+    v.push_back({"transformer.ln_f.weight", {H}});
+    return v;
+}
 }  // namespace
 
 extern "C" int at_required_tensors(const char* model, int n, int with_extras, char* buf, size_t cap) {
@@ -139,6 +157,7 @@ extern "C" int at_required_tensors(const char* model, int n, int with_extras, ch
     if (m == "encodec") v = encodec(n, with_extras != 0);
     else if (m == "w2vbert") v = w2vbert(n, with_extras != 0);
     else if (m == "hubert") v = hubert(n, with_extras != 0);
+    else if (m == "gpt") v = gpt(n);
     else { set_error("at_required_tensors: unknown model " + m); return -1; }
     std::string out;
     for (const Entry& e : v) {

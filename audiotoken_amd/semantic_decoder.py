@@ -1,0 +1,175 @@
+"""Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoders (``gpt2_model.py``, ``decoder.py:210-239``) on the
+KV-cached HIP GPT (csrc/gpt.hip). The fine stage (bark, code books 3 to 8) is not here, so the semantic ``decode`` stays absent; the
+``[2, T]`` this stage yields is what the acoustic decoder at ``num_codebooks=2`` turns into audio.
+
+Stated deviations from the reference: the draws come from a caller-visible uniform stream, not ``torch.multinomial``; a row whose length
+reaches the model's block finishes with ``"block_size"`` instead of having its context cropped; bias-free checkpoints only."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Dict, List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _cabi
+from ._handle import LibHandle
+from .configs import HubertDecoderConfig
+
+FINISH = {1: "stop", 2: "max_new_tokens", 3: "block_size"}
+
+
+@dataclass
+class AcousticGeneration:
+    """What ``to_acoustic`` returns, one entry per row of the batch."""
+    ids: List[torch.Tensor]                 # int64 [n_b]: the generated ids minus the acoustic offset (the stop token is not among them)
+    codes: List[Optional[torch.Tensor]]     # int64 [2, n_b // 2], or None where ``coarse_codes`` refused the ids
+    finish: List[str]                       # "stop" | "max_new_tokens" | "block_size"
+    logits: Optional[List[torch.Tensor]] = None   # return_logits: float32 [n_b (+ 1 when the row stopped), V], the logits each id was drawn from
+
+
+def coarse_codes(ids, codebook_size: int = 1024, num_codebooks: int = 2) -> torch.Tensor:
+    """Offset-free acoustic ids, interleaved as the reference serialises them, -> ``[2, T]``: even positions are code book 0, odd positions minus 1024
+    are code book 1. A trailing unpaired id is dropped. An id outside its code book's range raises ``ValueError`` naming the position."""
+    assert num_codebooks == 2, "stage 1 produces the two coarse code books"
+    ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+    T = ids.numel() // 2
+    pairs = ids[:2 * T].reshape(T, 2) - torch.tensor([0, codebook_size])
+    bad = ((pairs < 0) | (pairs >= codebook_size)).reshape(-1).nonzero()
+    if bad.numel():
+        pos = int(bad[0])
+        raise ValueError(f"coarse_codes: id {int(ids[pos])} at position {pos} is outside code book {pos % 2}'s range "
+                         f"[{(pos % 2) * codebook_size}, {(pos % 2 + 1) * codebook_size})")
+    return pairs.t().contiguous()
+
+
+def prepare_source(tokens, config: HubertDecoderConfig) -> np.ndarray:
+    """The prompt of one source, as the reference's ``_prepare_source`` builds it: ids + the semantic offset, flattened, truncated to
+    ``max_source_tokens``, the INFER token appended."""
+    if isinstance(tokens, (str, os.PathLike, Path)):
+        p = str(tokens)
+        tokens = np.load(p) if p.endswith(".npy") else torch.load(p, map_location="cpu")
+    t = torch.as_tensor(np.asarray(tokens.cpu() if isinstance(tokens, torch.Tensor) else tokens)).to(torch.int64).reshape(-1)
+    if t.numel() == 0:
+        raise ValueError("to_acoustic: an empty source")
+    if int(t.min()) < 0 or int(t.max()) >= config.SEMANTIC_VOCAB_SIZE:
+        raise ValueError(f"to_acoustic: semantic ids must lie in [0, {config.SEMANTIC_VOCAB_SIZE})")
+    t = (t + config.SEMANTIC_OFFSET)[:config.max_source_tokens]
+    return np.concatenate([t.numpy(), [config.INFER_TOKEN]]).astype(np.int32)
+
+
+def seeded_uniforms(seed: int, batch: int, max_new_tokens: int) -> np.ndarray:
+    return np.random.Generator(np.random.Philox(seed)).random((batch, max_new_tokens), dtype=np.float32)
+
+
+class SemanticToAcoustic(LibHandle):
+    """Owner of one ``at_gpt`` handle. ``weights``: a checkpoint path, a ``{name: array}`` dict, or None for the seeded synthetic model."""
+
+    FAMILY = "gpt"
+
+    def __init__(self, config: Optional[HubertDecoderConfig] = None, device="cuda:0", weights: Union[None, str, os.PathLike, Dict[str, np.ndarray]] = None):
+        self.config = config or HubertDecoderConfig()
+        if weights is None:
+            weights = self.config.weights
+
+        def host_tensors():
+            from . import weights as W
+            if weights is None:
+                return W.synth_gpt_weights(vocab=self.config.VOCAB_SIZE)
+            if isinstance(weights, dict):
+                return W.gpt_tensors_from_state_dict(weights, "weights dict")
+            return W.read_gpt_checkpoint(weights)
+
+        self._create(device, None, host_tensors)
+
+    def _finish_init(self) -> None:
+        self.n_layers = self._fn("num_layers")(self.handle)
+        self.vocab = self._fn("vocab")(self.handle)
+        self.block_size = self._fn("block_size")(self.handle)
+        self._init_call_state()
+
+    def eval(self):
+        return self
+
+    def generate(self, prompts: Sequence[np.ndarray], max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100,
+                 stop_token: int = -1, uniforms: Optional[np.ndarray] = None, seed: int = 0, allow=None, return_logits: bool = False):
+        """Raw generation over the model's own vocabulary: ``prompts`` a list of int id arrays (1 to 64 rows of their own lengths). Returns
+        ``(ids, finish, logits)``: per row the int64 ids on the CPU, the finish reason's name and (``return_logits``) the float32 logits
+        ``[n + stopped, V]``. ``allow``: None or int ``[2][4]``, the id ranges even / odd steps may produce (include/audiotoken_hip.h)."""
+        B = len(prompts)
+        max_new = int(max_new_tokens)
+        lens = [int(len(p)) for p in prompts]
+        if uniforms is None:
+            uniforms = seeded_uniforms(seed, B, max_new)
+        uniforms = np.ascontiguousarray(uniforms, dtype=np.float32)
+        if uniforms.shape != (B, max_new):
+            raise ValueError(f"uniforms must be float32 [{B}, {max_new}] (one draw per row and step), got {uniforms.shape}")
+        stride = max(lens) if lens else 1
+        host = np.zeros((max(B, 1), max(stride, 1)), dtype=np.int32)
+        for b, p in enumerate(prompts):
+            host[b, :lens[b]] = np.asarray(p, dtype=np.int32)
+        max_len = max(1, min(self.block_size, stride + max_new))
+        dev = self.device
+        with torch.cuda.device(dev):
+            d_prompts = torch.from_numpy(host).to(dev)
+            d_u = torch.from_numpy(uniforms).to(dev)
+            d_ids = torch.full((max(B, 1), max(max_new, 1)), -1, dtype=torch.int32, device=dev)
+            d_len = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
+            d_fin = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
+            d_logits = torch.empty((B, max_new, self.vocab), dtype=torch.float32, device=dev) if return_logits and B >= 1 and max_new >= 1 else None
+            nbytes = int(self._fn("state_bytes")(self.handle, B, max_len))
+            state = self._workspace(max(nbytes, 256))
+            self._status.zero_()
+            c_lens = (C.c_int32 * max(B, 1))(*lens)
+            c_allow = None if allow is None else (C.c_int32 * 8)(*[int(v) for v in np.asarray(allow).reshape(8)])
+            _cabi.check(self._fn("generate")(self.handle, d_prompts.data_ptr(), stride, c_lens, B, max_new, float(temperature), int(top_k), int(stop_token),
+                                             d_u.data_ptr(), c_allow, d_ids.data_ptr(), d_len.data_ptr(), d_fin.data_ptr(), _cabi.ptr(d_logits),
+                                             state.data_ptr(), state.numel(), max_len, _cabi.current_stream_handle(dev), self._status.data_ptr()),
+                        "at_gpt_generate")
+            n = d_len.cpu().tolist()    # synchronises
+            fin = d_fin.cpu().tolist()
+            ids_all = d_ids.cpu().to(torch.int64)
+        if self.last_status() & 1:
+            raise ValueError("at_gpt_generate: a prompt id lies outside the model's vocabulary")
+        self.last_raw_ids = ids_all   # the whole [B, max_new_tokens] buffer, -1 where nothing was written (tests)
+        ids = [ids_all[b, :n[b]].clone() for b in range(B)]
+        finish = [FINISH[f] for f in fin]
+        logits = None
+        if d_logits is not None:
+            logits = [d_logits[b, :min(max_new, n[b] + (1 if fin[b] == 1 else 0))].cpu() for b in range(B)]
+        return ids, finish, logits
+
+    def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0,
+                    uniforms: Optional[np.ndarray] = None, constrain: bool = False, return_logits: bool = False) -> AcousticGeneration:
+        cfg = self.config
+        batch = tokens if isinstance(tokens, (list, tuple)) else [tokens]
+        prompts = [prepare_source(t, cfg) for t in batch]
+        allow = None
+        if constrain:   # step s: the code book of its parity, and STOP where a whole frame has been written
+            a, n = cfg.ACOUSTIC_OFFSET, cfg.codebook_size
+            allow = [[a, a + n, cfg.STOP_TOKEN, cfg.STOP_TOKEN + 1], [a + n, a + 2 * n, 0, 0]]
+        ids, finish, logits = self.generate(prompts, max_new_tokens, temperature, top_k, cfg.STOP_TOKEN, uniforms, seed, allow, return_logits)
+        ids = [i - cfg.ACOUSTIC_OFFSET for i in ids]
+        codes: List[Optional[torch.Tensor]] = []
+        for i in ids:
+            try:
+                codes.append(coarse_codes(i, cfg.codebook_size, cfg.num_codebooks))
+            except ValueError:
+                codes.append(None)
+        return AcousticGeneration(ids=ids, codes=codes, finish=finish, logits=logits)
+
+
+def topk_sample(logits: torch.Tensor, temperature: float, top_k: int, uniforms: torch.Tensor, allow=None) -> torch.Tensor:
+    """``at_op_topk_sample`` on device tensors: logits float32 ``[B, V]``, uniforms float32 ``[B]`` -> int32 ``[B]`` (the sampling rule alone)."""
+    lib = _cabi.load()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+    assert uniforms.is_cuda and uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.numel() == logits.shape[0]
+    out = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    c_allow = None if allow is None else (C.c_int32 * 4)(*[int(v) for v in allow])
+    with torch.cuda.device(logits.device):
+        _cabi.check(lib.at_op_topk_sample(logits.data_ptr(), logits.shape[0], logits.shape[1], float(temperature), int(top_k), uniforms.data_ptr(), c_allow,
+                                          out.data_ptr(), _cabi.current_stream_handle(logits.device)), "at_op_topk_sample")
+    return out

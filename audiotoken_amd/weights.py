@@ -369,6 +369,58 @@ def synth_hubert_weights(n_layers: int = HUB_LAYERS_USED, seed: int = 0, with_km
 # ======================================================================================================
 # HF checkpoint directories (save_pretrained layout) -> numpy state dict
 # ======================================================================================================
+GPT_FAMILIES = ("uniform", "peaky")
+
+
+def synth_gpt_weights(n_layer: int = 12, vocab: int = 53376, block: int = 1024, seed: int = 0, family: str = "uniform") -> Dict[str, np.ndarray]:
+    """Seeded synthetic weights of the semantic-to-acoustic GPT (csrc/gpt.hip) under the checkpoint's names. ``"uniform"`` is the nanoGPT initialisation:
+    every matrix N(0, 0.02), the two ``c_proj`` at 0.02 / sqrt(2 n_layer); ``"peaky"`` is the same with ``wte`` at std 0.16, so that the logits spread
+    over tens of units and top-k and the softmax see a real dynamic range. The LayerNorm gains are drawn from [0.8, 1.2] instead of the
+    initialisation's ones, so that a kernel that dropped the gain would not pass."""
+    if family not in GPT_FAMILIES:
+        raise ValueError(f"weight family {family!r}: one of {GPT_FAMILIES}")
+    E, F = 768, 3072
+    proj_std = 0.02 / float(np.sqrt(2.0 * n_layer))
+    jobs = [("transformer.wte.weight", (vocab, E), 0.16 if family == "peaky" else 0.02), ("transformer.wpe.weight", (block, E), 0.02)]
+    for i in range(n_layer):
+        p = f"transformer.h.{i}"
+        jobs += [(f"{p}.attn.c_attn.weight", (3 * E, E), 0.02), (f"{p}.attn.c_proj.weight", (E, E), proj_std),
+                 (f"{p}.mlp.c_fc.weight", (F, E), 0.02), (f"{p}.mlp.c_proj.weight", (E, F), proj_std)]
+    w = _run_jobs([(name, (lambda name=name, shape=shape, std=std: prng.irwin_hall("gpt." + name, shape, std, seed))) for name, shape, std in jobs])
+    for name in [f"transformer.h.{i}.ln_{j}.weight" for i in range(n_layer) for j in (1, 2)] + ["transformer.ln_f.weight"]:
+        w[name] = prng.uniform("gpt." + name, (E,), 0.8, 1.2, seed)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in w.items()}
+
+
+def read_gpt_checkpoint(path) -> Dict[str, np.ndarray]:
+    """The reference's stage-1 checkpoint as the tensors ``at_gpt_finalize`` takes: ``torch.load(path)["model"]``, an optional ``_orig_mod.`` prefix on
+    every key, ``lm_head.weight`` tied to ``transformer.wte.weight``. Refused with ``ValueError``: biases, another ``n_embd``, an untied head."""
+    import torch
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ckpt, dict) or not isinstance(ckpt.get("model"), dict):
+        raise ValueError(f"{path}: not a GPT checkpoint (a dict with a 'model' state dict is expected)")
+    return gpt_tensors_from_state_dict(ckpt["model"], what=str(path))
+
+
+def gpt_tensors_from_state_dict(sd, what: str = "state dict") -> Dict[str, np.ndarray]:
+    pre = "_orig_mod."
+    sd = {(k[len(pre):] if k.startswith(pre) else k): v for k, v in sd.items()}
+    sd = {k: (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, dtype=np.float32)) for k, v in sd.items()
+          if not k.endswith(".attn.bias")}   # nanoGPT's causal-mask buffer is not a parameter
+    biases = sorted(k for k in sd if k.endswith(".bias"))
+    if biases:
+        raise ValueError(f"{what}: the checkpoint has biases ({biases[0]}, ...); the HIP decoder implements the bias-free model only")
+    wte = sd.get("transformer.wte.weight")
+    if wte is None or wte.ndim != 2:
+        raise ValueError(f"{what}: transformer.wte.weight is missing")
+    if wte.shape[1] != 768:
+        raise ValueError(f"{what}: n_embd = {wte.shape[1]}; the HIP decoder implements n_embd = 768 (12 heads of 64) only")
+    head = sd.pop("lm_head.weight", None)
+    if head is not None and (head.shape != wte.shape or not np.array_equal(head, wte)):
+        raise ValueError(f"{what}: lm_head.weight is not tied to transformer.wte.weight; the HIP decoder implements the tied head only")
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
 def read_hf_state_dict(model_dir: str, strip_prefixes=()) -> Dict[str, np.ndarray]:
     """A HF ``save_pretrained`` directory -> {name: float32 array}. Understands ``model.safetensors``, the sharded form
     (``model.safetensors.index.json`` + ``model-0000i-of-0000n.safetensors``) and the legacy ``pytorch_model.bin`` (+ its sharded index).

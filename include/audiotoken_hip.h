@@ -527,7 +527,8 @@ int at_op_gemm(const at_gemm_desc* d, at_stream_t stream);
  * codes int16 written at codes[(row / T)*n_q*T + q*T + row % T]. */
 /* The named host tensors (float32, weight-norm already folded) a model's finalize() needs, one per line as "name d0 d1 ...":
  * model "encodec" (n = number of codebooks, with_extras = decoder too), "w2vbert" (n = conformer layers, with_extras = VQ codebook),
- * "hubert" (n = transformer layers, with_extras = k-means centres). Returns the number of entries, or -(bytes needed) when buf is NULL or
+ * "hubert" (n = transformer layers, with_extras = k-means centres), "gpt" (n = layers; the embedding shapes listed are the reference's V = 53376 and
+ * block = 1024, finalize takes both from the tensors; with_extras is ignored). Returns the number of entries, or -(bytes needed) when buf is NULL or
  * too small. A checkpoint loader can validate its output against this list without a device. */
 int at_required_tensors(const char* model, int n, int with_extras, char* buf, size_t cap);
 
@@ -625,6 +626,48 @@ int at_kmeans_layernorm(const float* x, float* y, int64_t rows, int D, int split
  * new cluster; the first n_empty entries are valid): for tests. */
 int at_kmeans_row_d2(const at_kmeans_t* h, double* out, at_stream_t stream);
 int at_kmeans_relocations(const at_kmeans_t* h, int32_t* out, at_stream_t stream);
+
+/* ---- semantic-to-acoustic generation: a KV-cached GPT decoder (csrc/gpt.hip) -------------------------------------------------
+ * The model of the reference's semantic decoders' first stage: token embedding wte [V][768] tied to the head, learned positions wpe [block][768],
+ * n_layer pre-LN blocks (LayerNorm with a gain only, eps 1e-5; every linear without bias; 12 heads of 64; causal attention scaled by 1/8; MLP
+ * 768 -> 3072 -> 768 with the erf GELU), a final LayerNorm, logits = ln_f(x) . wte^T. Tensors carry the checkpoint's names ("transformer.wte.weight",
+ * "transformer.h.<i>.attn.c_attn.weight", ...; at_required_tensors("gpt", n_layer, ...)). finalize takes n_layer (1 to 48), V (a multiple of 64, at
+ * most 65536) and block (a multiple of 64, at most 1024) from the shapes and refuses anything else, a ".bias" tensor included. */
+typedef struct at_gpt at_gpt_t;
+at_gpt_t* at_gpt_create(int device_id);
+int at_gpt_set_tensor(at_gpt_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int at_gpt_finalize(at_gpt_t* h);
+void at_gpt_destroy(at_gpt_t* h);
+int at_gpt_num_layers(const at_gpt_t* h);
+int at_gpt_vocab(const at_gpt_t* h);
+int at_gpt_block_size(const at_gpt_t* h);
+/* Bytes of the caller-owned device state of one at_gpt_generate call with B rows (1 to 64) whose sequences reach at most max_len tokens
+ * (prompt + new, at most the block size): the K / V cache, the activations of the prefill and the rows' bookkeeping. 0 = error. */
+size_t at_gpt_state_bytes(const at_gpt_t* h, int B, int max_len);
+#define AT_GPT_FINISH_STOP 1
+#define AT_GPT_FINISH_MAX_NEW 2
+#define AT_GPT_FINISH_BLOCK 3
+/* Generate up to max_new tokens for B rows in one stream-ordered call that allocates nothing. prompts_dev: device int32 [B][prompt_stride], row b
+ * holding prompt_len[b] ids (prompt_len is a HOST array; 1 <= prompt_len[b] <= prompt_stride). uniforms_dev: device float32 [B][max_new], the draw of
+ * row b at step s. Per step and row: logits of the last token, then the sampling rule of at_op_topk_sample (below) with `allow` = NULL or a HOST array
+ * int32 [2][4]: step s may only produce ids in [a[s%2][0], a[s%2][1]) or [a[s%2][2], a[s%2][3]). A row finishes when it samples stop_token (not
+ * written; negative = none): finish AT_GPT_FINISH_STOP; after max_new tokens: _MAX_NEW; when prompt + new reaches the model's block size: _BLOCK
+ * (the reference crops the context instead). A finished row writes nothing more. out_ids_dev device int32 [B][max_new] (entries past
+ * out_len_dev[b] are left as they were), out_len_dev / finish_dev device int32 [B]; logits_out_dev NULL or device float32 [B][max_new][V]: the logits each
+ * written token was sampled from (and those of a sampled stop token). state_dev: at_gpt_state_bytes(h, B, max_len) bytes with
+ * max_len >= min(block, longest prompt + max_new). The steps are enqueued without waiting for the device; every 16 steps the host reads the rows' finish
+ * flags and stops when all rows are done, so the call returns with work still in flight on `stream`. status_dev NULL or a device word: bit 0 = a prompt
+ * id outside [0, V) was clamped. Every argument is checked before the device is touched. Not re-entrant per handle. */
+int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, const int32_t* prompt_len, int B, int max_new, float temperature, int top_k,
+                    int stop_token, const float* uniforms_dev, const int32_t* allow, int32_t* out_ids_dev, int32_t* out_len_dev, int32_t* finish_dev,
+                    float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev);
+/* The sampling step alone, one workgroup per row, no float atomics (the same call twice gives the same ids). logits_dev device float32 [B][V], V <= 65536;
+ * uniforms_dev device float32 [B]; allow NULL or a HOST array int32 [4] = two half-open id ranges; out_dev device int32 [B]. The rule:
+ * 1. zt_i = z_i / temperature (one IEEE fp32 division). 2. ids outside the allow ranges become -inf. 3. v = the min(top_k, V)-th largest zt; every id
+ * with zt_i >= v is kept (ties at the threshold stay). 4. m = max kept zt, p_i = exp(zt_i - m), S = sum p_i. 5. the token is the lowest kept id whose
+ * running sum in ascending id order exceeds u * S; if rounding leaves none, the highest kept id. */
+int at_op_topk_sample(const float* logits_dev, int B, int V, float temperature, int top_k, const float* uniforms_dev, const int32_t* allow, int32_t* out_dev,
+                      at_stream_t stream);
 
 #ifdef __cplusplus
 }
