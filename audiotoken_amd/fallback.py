@@ -28,7 +28,7 @@ def _count_nonfinite(owner, what: str, where: str) -> None:
 
 
 def encodec_ladder(owner, first, rerun: Callable, batch: int, range_options: Sequence[str], what: str, nonfinite_bit: bool = True):
-    """EnCodec family (``AcousticEncoder.verified``, ``AcousticDecoder.verified``, ``AcousticStream`` per push). ``first`` is what the call whose
+    """EnCodec family (``AcousticEncoder.verified``, ``AcousticDecoder.verified``, the lockstep streams and the pools of streaming.py per push). ``first`` is what the call whose
     status is being read returned; it comes back as it is when the status is 0. ``batch`` = clips in the call, ``range_options`` = the f16x2
     switches turned off for the repeat, ``what`` = noun of the log lines, ``nonfinite_bit`` = whether the call has a quantiser (bit 2)."""
     status = owner.last_status()

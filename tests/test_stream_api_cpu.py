@@ -91,3 +91,18 @@ def test_push_after_flush_raises_until_reset():
     st.reset()
     assert st.frames_emitted == 0
     assert st.push(torch.zeros(1, 3200)).shape[-1] == 10
+
+
+@pytest.mark.parametrize("first", [0, 10 * HOP], ids=["first_push", "after_whole_frames"])
+def test_what_is_held_is_a_copy_of_the_callers_samples(first):
+    """A caller may reuse the tensor it pushed: the end a stream holds back is its own copy, on the first push and after a push that left nothing held."""
+    stub = _Stub(1, 4)
+    st = AcousticStream(None, 1, push_fn=stub, n_q=4)
+    if first:
+        st.push(torch.zeros(1, first))
+    buf = torch.arange(8 * HOP + 100, dtype=torch.float32)[None].clone()
+    want = buf[:, -100:].clone()
+    st.push(buf)
+    buf.fill_(-1.0)                 # the caller's buffer goes on to other use
+    st.flush()
+    assert stub.calls[-1] == (100, True) and torch.equal(stub.seen[-1], want)

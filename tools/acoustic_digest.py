@@ -73,9 +73,9 @@ def encode_side() -> None:
     ids, emb = enc(wav, return_embeddings=True)
     line("encode B=81 N=633 subbatch=2", enc, ids=ids, emb=emb)
     enc.set_option("subbatch", saved)
-    # a stream of 2240 + 3200 + (final) 1000 samples, straight through the library's push. This reaches into AcousticStream (streaming.py): _device_push
-    # is one library push, _state is its pair of state buffers, swapped after every successful push, so _state[0] is what the push just wrote and
-    # _state[1] what it read. decode_side() relies on the same members of AcousticDecodeStream. If streaming.py changes that order, change it here too.
+    # a stream of 2240 + 3200 + (final) 1000 samples, straight through the library's push, past the residual buffering. The two seams are those of
+    # streaming._Stream, which both lockstep streams are: _device_push(x, final) is one transaction (the bare push, the ladder, the swap) and _state
+    # its pair of state buffers, so after a push _state[0] is what it wrote and _state[1] what it read. decode_side() uses the same two.
     st = enc.new_stream(batch=3)
     st._state[1].zero_()
     wav = torch.from_numpy(W.synth_waveform(3, 6440, 24000, seed=7999)).cuda()

@@ -80,14 +80,13 @@ def report(what, ms, audio_s):
 
 
 def copies(pool, model, B, reps=200):
-    """ms of one gather + one scatter at B rows, slots reversed (the copies are what the product calls: pool._gather / pool._scatter)."""
+    """ms of one gather + one scatter at B rows, slots reversed (the copies are what the product calls: pool.gather_scatter is a transaction without its push)."""
     slots = list(range(B))[::-1]
-    pool._reset_state(pool._staging[1], B)      # a state the handle knows, for the scatter
-    for _ in range(10):
-        pool._gather(slots)
-        pool._scatter(slots)
+    pool.gather_scatter(slots, fresh=True)      # a state the handle knows, for the scatter
+    for _ in range(9):
+        pool.gather_scatter(slots)
     torch.cuda.synchronize()
-    return once(lambda: [(pool._gather(slots), pool._scatter(slots)) for _ in range(reps)]) / reps
+    return once(lambda: [pool.gather_scatter(slots) for _ in range(reps)]) / reps
 
 
 def encode_side():
