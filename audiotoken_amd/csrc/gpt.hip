@@ -444,7 +444,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
                 if (lane >= o) incl += up;
             }
             if (walk == 1 && kept) {
-                top = i;
+                if (v > -INFINITY) top = i;   // the fallback never returns an id of weight zero (a threshold of -inf keeps every id)
                 if (!found && carry + incl > target) { found = true; atomicMin(&best_id, i); }
             }
             carry += __shfl(incl, 63);

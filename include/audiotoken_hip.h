@@ -665,7 +665,7 @@ int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, 
  * uniforms_dev device float32 [B]; allow NULL or a HOST array int32 [4] = two half-open id ranges; out_dev device int32 [B]. The rule:
  * 1. zt_i = z_i / temperature (one IEEE fp32 division). 2. ids outside the allow ranges become -inf. 3. v = the min(top_k, V)-th largest zt; every id
  * with zt_i >= v is kept (ties at the threshold stay). 4. m = max kept zt, p_i = exp(zt_i - m), S = sum p_i. 5. the token is the lowest kept id whose
- * running sum in ascending id order exceeds u * S; if rounding leaves none, the highest kept id. */
+ * running sum in ascending id order exceeds u * S; if rounding leaves none, the highest kept id whose zt is not -inf. */
 int at_op_topk_sample(const float* logits_dev, int B, int V, float temperature, int top_k, const float* uniforms_dev, const int32_t* allow, int32_t* out_dev,
                       at_stream_t stream);
 

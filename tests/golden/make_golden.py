@@ -1,7 +1,7 @@
 """Generate the committed golden vectors (run in the BUILD container only: needs HF `transformers`
 and, for the semantic fixtures, read access to /root/reference).
 
-    python tests/golden/make_golden.py [encodec] [fbank] [attention] [conformer] [harness]
+    python tests/golden/make_golden.py [encodec] [fbank] [attention] [conformer] [harness] [gpt]
 
 Outputs small .npz files next to this script. Inputs are regenerated from the in-repo counter-based PRNG
 (audiotoken_amd/prng.py), so fixtures hold only seeds/shapes and the expected outputs.
@@ -220,6 +220,137 @@ def make_hubert():
                         normalized=norm.astype(np.float32), hs0=hs[0].numpy(), hs1=hs[1].numpy(), hs_last=hs[n_layers].numpy(),
                         tokens=toks.numpy())
     print("hubert", hs[0].shape, toks.shape)
+
+
+GPT_IDS_SEED, GPT_LENGTHS = 1, (1, 64, 65, 257, 513, 1024)
+GPT_V, GPT_STEPS, GPT_TEMP, GPT_TOP_K, GPT_PROMPT = 2048, 24, 0.8, 100, 5
+# Philox seeds of the draws, per family: ("free" and "stop", "tie"). Chosen by hand (gpt_find_seed below): with about 100 ids kept, a draw lies within 1e-3 of one
+# of the CDF's boundaries at one step in five of the uniform family, so most seeds fail the distance assertion at one of a run's 24 steps.
+GPT_DRAW_SEEDS = {"uniform": (75, 433), "peaky": (0, 0)}   # the first seeds that pass
+
+
+def _gpt_model(G, w):
+    model = G.get_model(n_layer=2, vocab_size=GPT_V, block_size=1024).eval()
+    sd = {k: torch.from_numpy(v.copy()) for k, v in w.items()}
+    sd["lm_head.weight"] = sd["transformer.wte.weight"]
+    model.load_state_dict(sd)
+    return model
+
+
+def _gpt_last_logits(model, ids):
+    with torch.no_grad():
+        return model(torch.from_numpy(np.asarray(ids, dtype=np.int64))[None])[0][0, -1].numpy().copy()
+
+
+def _gpt_generate(model, prompt, u, stop_token):
+    """The reference's generate loop with torch.multinomial replaced by the ordered inverse-CDF draw: (returned sequence, the probs of every step)."""
+    seen = []
+
+    def draw(probs, num_samples):   # the lowest id whose running sum in ascending id order exceeds u * S
+        cdf = np.cumsum(probs[0].double().numpy())
+        over = np.nonzero(cdf > np.float64(u[len(seen)]) * cdf[-1])[0]
+        seen.append(probs[0].numpy().copy())
+        return torch.tensor([[int(over[0])]])
+
+    real = torch.multinomial
+    torch.multinomial = draw
+    try:
+        got = model.generate(torch.from_numpy(prompt.astype(np.int64))[None], GPT_STEPS, temperature=GPT_TEMP, top_k=GPT_TOP_K, stop_token=stop_token)
+    finally:
+        torch.multinomial = real
+    return got[0].numpy().copy(), np.stack(seen)
+
+
+def _gpt_checked_run(model, prompt, seed, stop_token, what):
+    """One generation whose every step lies at least 1e-3 from a CDF boundary (the twin's measure on the reference's logits), or AssertionError naming the seed."""
+    from audiotoken_amd.semantic_decoder import seeded_uniforms
+    from tests import gpt_ref as R
+    u = seeded_uniforms(seed, 1, GPT_STEPS)[0]
+    ids, probs = _gpt_generate(model, prompt, u, stop_token)
+    closest = float("inf")
+    for s in range(probs.shape[0]):
+        tok, dist, kept = R.sample(_gpt_last_logits(model, ids[:GPT_PROMPT + s]), GPT_TEMP, GPT_TOP_K, u[s])
+        assert kept == int((probs[s] > 0).sum()), "a kept probability underflowed: the kept set cannot be read from probs"
+        assert dist >= 1e-3, f"draw seed {seed}: {what} step {s} lies {dist:.2e} from a CDF boundary; choose another seed"
+        closest = min(closest, dist)
+    return ids, probs, closest
+
+
+def _gpt_models(G, family, prompt):
+    """(weights' model, the tie run's model, [copied-from id, overwritten id])."""
+    w = W.synth_gpt_weights(n_layer=2, vocab=GPT_V, block=1024, seed=0, family=family)
+    model = _gpt_model(G, w)
+    order = np.argsort(-_gpt_last_logits(model, prompt), kind="stable")
+    tie = [int(order[GPT_TOP_K - 1]), int(order[GPT_TOP_K])]
+    assert not set(tie) & set(prompt.tolist())
+    w_tie = dict(w)
+    w_tie["transformer.wte.weight"] = w["transformer.wte.weight"].copy()
+    w_tie["transformer.wte.weight"][tie[1]] = w["transformer.wte.weight"][tie[0]]
+    return model, _gpt_model(G, w_tie), tie
+
+
+def gpt_find_seed(family, run, limit=4000):
+    """python -c "import make_golden as m; print(m.gpt_find_seed('uniform', 'free'))": the first Philox seed whose run passes the distance assertion."""
+    from _ref_gpt_loader import load_reference_gpt
+    G = load_reference_gpt()["gpt2_model"]
+    prompt = np.random.default_rng(GPT_IDS_SEED).integers(0, GPT_V, size=1024)[:GPT_PROMPT]
+    model, model_tie, _ = _gpt_models(G, family, prompt)
+    for seed in range(limit):
+        try:
+            _, _, closest = _gpt_checked_run(model_tie if run == "tie" else model, prompt, seed, None, run)
+            return seed, closest
+        except AssertionError:
+            continue
+
+
+def make_gpt():
+    """The reference's GPT (gpt2_model.py: get_model(n_layer=2, vocab_size=2048, block_size=1024), bias-free) loaded with the synthetic weights of both
+    families, and the three array helpers of its decoder.py. Logits: the reference's fp32 last-position logits of one seeded id sequence cut at
+    GPT_LENGTHS. Generation (5 prompt ids, 24 steps, temperature 0.8, top_k 100): the reference's own ``generate`` loop (temperature, top-k masking with
+    its ties, softmax, stop handling) with only ``torch.multinomial`` replaced by this project's ordered inverse-CDF draw from ``seeded_uniforms``; the
+    replacement records the ``probs`` it is handed, and those of the first 4 steps are saved (the kept set is their support: the recipe asserts that no kept
+    probability underflowed). Three runs per family: "free" (no stop token), "stop" (the
+    stop token is the 8th id of "free"), and "tie": in the weights of this run alone, the ``wte`` row of the id ranked 101st at the first step is
+    overwritten with the row of the id ranked 100th, so that the two share a logit at every step and tie at the top-k threshold of the first one
+    (``tie_<family>`` = [copied-from id, overwritten id])."""
+    from _ref_gpt_loader import load_reference_gpt
+    mods = load_reference_gpt()
+    G, D = mods["gpt2_model"], mods["decoder"]
+    seq = np.random.default_rng(GPT_IDS_SEED).integers(0, GPT_V, size=1024)
+    prompt = seq[:GPT_PROMPT]
+    out = dict(ids_seed=GPT_IDS_SEED, lengths=np.array(GPT_LENGTHS), weight_seed=0, n_layer=2, vocab=GPT_V, block=1024,
+               temperature=GPT_TEMP, top_k=GPT_TOP_K, prompt_len=GPT_PROMPT, steps=GPT_STEPS)
+    closest = float("inf")
+    for family in ("uniform", "peaky"):
+        model, model_tie, tie = _gpt_models(G, family, prompt)
+        out[f"logits_{family}"] = np.stack([_gpt_last_logits(model, seq[:T]) for T in GPT_LENGTHS])
+        out[f"tie_{family}"] = np.array(tie)
+        seed_free, seed_tie = GPT_DRAW_SEEDS[family]
+        free, _, _ = _gpt_checked_run(model, prompt, seed_free, None, f"{family}/free")
+        for run, m, seed, stop in (("free", model, seed_free, None), ("stop", model, seed_free, int(free[GPT_PROMPT + 7])), ("tie", model_tie, seed_tie, None)):
+            ids, probs, c = _gpt_checked_run(m, prompt, seed, stop, f"{family}/{run}")
+            closest = min(closest, c)
+            out[f"seq_{family}_{run}"] = ids
+            out[f"probs_{family}_{run}"] = probs[:4]
+            out[f"stop_{family}_{run}"] = -1 if stop is None else stop
+            out[f"draw_seed_{family}_{run}"] = seed
+        assert int((out[f"probs_{family}_tie"][0] > 0).sum()) == GPT_TOP_K + 1, "the tie must be at the first step's threshold"
+    out["closest_boundary"] = closest
+    # decoder.py's helpers on a handful of inputs (the constants of the w2v-BERT decoder: offset 50257, 250 source ids, INFER 53311, STOP 53314)
+    src2d = torch.arange(12).reshape(3, 4) * 83 % 1000
+    src_long = torch.from_numpy(np.random.default_rng(3).integers(0, 1000, size=(1, 600)))
+    out["src_2d"], out["src_long"] = src2d.numpy(), src_long.numpy()
+    out["prepared_2d"] = D._prepare_source(src2d, 50257, 250).numpy()
+    out["prepared_long"] = D._prepare_source(src_long, 50257, 250).numpy()
+    body = 51257 + np.array([5, 1031, 1023, 2047, 0, 1024, 77, 1500])
+    out["y_stop"] = np.concatenate([[50300, 50400, 53311], body[:6], [53314], body[6:]])
+    out["y_free"] = np.concatenate([[50300, 53311], body])
+    out["new_stop"] = D._extract_new_tokens(out["y_stop"], 53311, 53314)
+    out["new_free"] = D._extract_new_tokens(out["y_free"], 53311, 53314)
+    out["codes_stop"] = D._deserialize_acoustic_tokens(out["new_stop"] - 51257)
+    out["codes_free"] = D._deserialize_acoustic_tokens(out["new_free"] - 51257)
+    np.savez_compressed(os.path.join(HERE, "gpt_a.npz"), **out)
+    print("gpt", {k: np.asarray(v).shape for k, v in out.items()}, f"closest boundary {closest:.3e}")
 
 
 if __name__ == "__main__":

@@ -51,9 +51,8 @@ def forward(w, ids, dtype=torch.float64, positions=None):
     return x @ W("transformer.wte.weight").t()
 
 
-def sample(logits_f32, temperature, top_k, u, allow=None):
-    """The sampling rule on one float32 logit vector: (token, dist, kept). Step 1 (the division) in fp32, the rest in float64. ``allow``: None or
-    (lo0, hi0, lo1, hi1), two half-open id ranges. ``dist`` is the distance from ``u`` to the nearest boundary between two kept ids in the kept set's normalised CDF."""
+def kept_values(logits_f32, temperature, top_k, allow=None):
+    """Steps 1 to 3 of the sampling rule: (kept ids ascending, their tempered float32 values). The division in fp32."""
     z = np.asarray(logits_f32, dtype=np.float32)
     V = z.shape[0]
     zt = (z / np.float32(temperature)).astype(np.float32)
@@ -64,13 +63,27 @@ def sample(logits_f32, temperature, top_k, u, allow=None):
     k = min(int(top_k), V)
     v = np.partition(zt, V - k)[V - k]          # the k-th largest
     kept = np.nonzero(zt >= v)[0]               # ascending ids; ties at the threshold stay
-    z64 = zt[kept].astype(np.float64)
+    return kept, zt[kept]
+
+
+def kept_weights(logits_f32, temperature, top_k, allow=None):
+    """Steps 1 to 4: (kept ids ascending, their float64 weights normalised to sum 1): what a softmax over the masked logits gives the kept ids."""
+    kept, zk = kept_values(logits_f32, temperature, top_k, allow)
+    p = np.exp(zk.astype(np.float64) - np.float64(zk.max()))
+    return kept, p / p.sum()
+
+
+def sample(logits_f32, temperature, top_k, u, allow=None):
+    """The sampling rule on one float32 logit vector: (token, dist, kept). Step 1 (the division) in fp32, the rest in float64. ``allow``: None or
+    (lo0, hi0, lo1, hi1), two half-open id ranges. ``dist`` is the distance from ``u`` to the nearest boundary between two kept ids in the kept set's normalised CDF."""
+    kept, zk = kept_values(logits_f32, temperature, top_k, allow)
+    z64 = zk.astype(np.float64)
     p = np.exp(z64 - z64.max())
     cdf = np.cumsum(p)
     S = cdf[-1]
     target = np.float64(np.float32(u)) * S
     over = np.nonzero(cdf > target)[0]
-    token = int(kept[over[0]]) if over.size else int(kept[-1])
-    # the boundaries between two kept ids; the CDF's end (1) decides nothing: past it the rule takes the highest kept id, the id just below it too
+    token = int(kept[over[0]]) if over.size else int(kept[z64 > -np.inf][-1])   # the fallback: the highest kept id that is not -inf
+    # the boundaries between two kept ids; the CDF's end (1) decides nothing: past it the rule takes the highest kept id that is not -inf, the id just below it too
     dist = float(np.abs(cdf[:-1] / S - np.float64(np.float32(u))).min()) if kept.size > 1 else float("inf")
     return token, dist, int(kept.size)
