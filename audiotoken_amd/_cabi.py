@@ -213,6 +213,18 @@ SIGNATURES = {
     "at_gpt_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                   C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "at_op_topk_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "at_fine_create": (C.c_void_p, [C.c_int]),
+    "at_fine_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "at_fine_finalize": (C.c_int, [C.c_void_p]),
+    "at_fine_destroy": (None, [C.c_void_p]),
+    "at_fine_num_layers": (C.c_int, [C.c_void_p]),
+    "at_fine_hidden": (C.c_int, [C.c_void_p]),
+    "at_fine_block_size": (C.c_int, [C.c_void_p]),
+    "at_fine_has_bias": (C.c_int, [C.c_void_p]),
+    "at_fine_num_windows": (C.c_int, [C.c_void_p, C.c_int]),
+    "at_fine_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "at_fine_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -103,6 +103,20 @@ class Wav2VecBertDecoderConfig(HubertDecoderConfig):
 
 
 @dataclass
+class FineDecoderConfig:
+    """The fine stage of the semantic way back (bark's non-causal fine transformer): two coarse code books in, all eight out. Constants only."""
+    n_coarse: int = 2            # code books given
+    n_fine: int = 8              # code books of the result: EnCodec at bandwidth 6
+    codebook_size: int = 1024    # ids of a code book; the value 1024 itself fills a cell that holds nothing yet
+    temperature: float = 0.5     # bark's default in generate_fine
+    synthetic_layers: int = 12   # the seeded synthetic model used when no weights are given
+    synthetic_hidden: int = 1024
+    synthetic_block: int = 1024
+    max_rows: int = 64           # rows of one call
+    weights: Optional[str] = os.environ.get("AUDIOTOKEN_FINE_DECODER_WEIGHTS")
+
+
+@dataclass
 class AudioConfig:
     """Per-chunk metadata (reference audiotoken/configs.py:190-218)."""
     file_name: str

@@ -341,10 +341,48 @@ class AudioToken:
         return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
                                                  constrain=constrain, return_logits=return_logits)
 
+    def to_fine(self, codes, temperature: Optional[float] = 0.5, seed: int = 0, uniforms=None, return_logits: bool = False):
+        """The two coarse EnCodec code books -> all eight: stage 2 of the reference's semantic decoder (bark's ``generate_fine``) on the HIP fine
+        transformer (fine_decoder.py). Acoustic codes in, acoustic codes out, so every tokenizer has it. ``codes``: integer ``[2, T]``, or a
+        list of up to 64 of them of their own lengths, run as one batch. Returns a ``FineGeneration``: ``codes`` (a list of int64 ``[8, T_b]`` that
+        ``AudioToken(Tokenizers.acoustic, num_codebooks=8).decode`` takes) and, with ``return_logits``, the logits and ids of every window and pass.
+        ``temperature=None`` takes the argmax; any number samples (1.0 too, where HF takes the argmax) with the draws ``uniforms`` (float32
+        ``[B, n_max, 6, W]``) or, from ``seed``, ``np.random.Generator(np.random.Philox(seed)).random(...)`` of that shape. Weights: the constructor's
+        ``fine_weights=`` (a checkpoint path or a ``{name: array}`` dict), else ``$AUDIOTOKEN_FINE_DECODER_WEIGHTS``, else the seeded synthetic model."""
+        from .fine_decoder import _as_rows
+        rows = _as_rows(codes)   # a malformed input is refused before any model is built
+        if getattr(self, "fine_decoder", None) is None:
+            from .configs import FineDecoderConfig
+            from .fine_decoder import CoarseToFine
+            cfg = FineDecoderConfig()
+            w = self.kwargs.get("fine_weights")
+            if w is None and cfg.weights is None:
+                logger.warning("to_fine: no fine_weights given; using the seeded synthetic fine model")
+            self.fine_decoder = CoarseToFine(cfg, device=self.device, weights=w)
+        return self.fine_decoder.generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
+
+    def to_audio(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, fine_temperature: Optional[float] = 0.5,
+                 seed: int = 0, uniforms=None, fine_uniforms=None):
+        """Semantic ids -> audio, this project's form of the reference's semantic ``decode`` (``decoder.py:210-243``): ``to_acoustic(constrain=True)``, then
+        ``to_fine``, then the acoustic decoder at 8 code books (bandwidth 6). Semantic tokenizers only. ``tokens`` as ``to_acoustic`` takes them. Returns
+        ``(audio, coarse, fine)``: a list of one float32 ``(1, 320 * T_b)`` CPU tensor per source, the ``AcousticGeneration`` and the ``FineGeneration``.
+        ``uniforms`` / ``fine_uniforms`` / ``seed`` are the two stages' draws. A source whose stage 1 produced no whole frame raises ``ValueError``."""
+        if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
+            raise ValueError(f"to_audio maps semantic ids to audio; {self.tokenizer_name} has no semantic ids (its own decode is the way back)")
+        coarse = self.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms, constrain=True)
+        for b, c in enumerate(coarse.codes):
+            if c is None or c.shape[1] < 1:
+                raise ValueError(f"to_audio: source {b} produced no whole frame of coarse codes (finish: {coarse.finish[b]})")
+        fine = self.to_fine(coarse.codes, temperature=fine_temperature, seed=seed, uniforms=fine_uniforms)
+        if getattr(self, "fine_audio", None) is None:
+            self.fine_audio = AudioToken(Tokenizers.acoustic, device=self.device, num_codebooks=8, weights=self.kwargs.get("acoustic_weights"))
+        audio = [self.fine_audio.decode(c.unsqueeze(0)) for c in fine.codes]
+        return audio, coarse, fine
+
     def load_decoder(self, **kwargs):
-        """core.py:291-315. Built: the acoustic decoder. Of the semantic decoders, stage 1 (semantic ids -> the two coarse code books, a GPT) is built under
-        its own name, ``to_acoustic``; the fine stage (bark, code books 3 to 8) is absent, so the semantic ``decode`` and this loader still raise
-        ``NotImplementedError`` for the semantic tokenizers."""
+        """core.py:291-315. Built: the acoustic decoder. The semantic way back is built under its own names: ``to_acoustic`` (stage 1, semantic ids -> the
+        two coarse code books, a GPT), ``to_fine`` (stage 2, code books 3 to 8) and ``to_audio`` (both, then the acoustic decoder). The semantic ``decode``
+        and this loader keep raising ``NotImplementedError`` for the semantic tokenizers."""
         if self.decoder is None:
             if self.tokenizer_name == Tokenizers.acoustic:
                 from .decoder import AcousticDecoder

@@ -147,6 +147,28 @@ std::vector<Entry> gpt(int n_layers) {
     v.push_back({"transformer.ln_f.weight", {H}});
     return v;
 }
+
+// the fine stage at the checkpoint's sizes (E = 1024, W = 1024); finalize takes E and W from the shapes
+std::vector<Entry> fine(int n_layers, bool bias) {
+    std::vector<Entry> v;
+    const int H = 1024, F = 4096;
+    for (int i = 0; i < 8; ++i) v.push_back({"transformer.wtes." + std::to_string(i) + ".weight", {1056, H}});
+    v.push_back({"transformer.wpe.weight", {1024, H}});
+    auto lin = [&](const std::string& b, int o, int i) { v.push_back({b + ".weight", {o, i}}); if (bias) v.push_back({b + ".bias", {o}}); };
+    auto ln = [&](const std::string& b) { v.push_back({b + ".weight", {H}}); v.push_back({b + ".bias", {H}}); };
+    for (int i = 0; i < n_layers; ++i) {
+        const std::string p = "transformer.h." + std::to_string(i);
+        ln(p + ".ln_1");
+        lin(p + ".attn.c_attn", 3 * H, H);
+        lin(p + ".attn.c_proj", H, H);
+        ln(p + ".ln_2");
+        lin(p + ".mlp.c_fc", F, H);
+        lin(p + ".mlp.c_proj", H, F);
+    }
+    ln("transformer.ln_f");
+    for (int j = 0; j < 7; ++j) v.push_back({"lm_heads." + std::to_string(j) + ".weight", {1056, H}});
+    return v;
+}
 }  // namespace
 
 extern "C" int at_required_tensors(const char* model, int n, int with_extras, char* buf, size_t cap) {
@@ -158,6 +180,7 @@ extern "C" int at_required_tensors(const char* model, int n, int with_extras, ch
     else if (m == "w2vbert") v = w2vbert(n, with_extras != 0);
     else if (m == "hubert") v = hubert(n, with_extras != 0);
     else if (m == "gpt") v = gpt(n);
+    else if (m == "fine") v = fine(n, with_extras != 0);
     else { set_error("at_required_tensors: unknown model " + m); return -1; }
     std::string out;
     for (const Entry& e : v) {

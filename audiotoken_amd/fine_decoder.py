@@ -1,0 +1,135 @@
+"""The two coarse EnCodec code books -> all eight: stage 2 of the reference's semantic decoders (bark's ``generate_fine``, ``decoder.py:109-121`` and
+``241-243``) on the HIP fine transformer (csrc/fine.hip). The loop is ``BarkFineModel.generate`` without a history prompt: windows of
+``W`` frames hopping by ``W / 2``, six forwards per window (code books 2 to 7), each writing one id per predicted position.
+
+Stated deviations from the reference: the draws come from a caller-visible uniform stream, not ``torch.multinomial``; temperature 1.0
+samples (HF takes the argmax there; here only ``temperature=None`` does); no history prompt."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Union
+
+import numpy as np
+import torch
+
+from . import _cabi
+from ._handle import LibHandle
+from .configs import FineDecoderConfig
+
+N_PASSES = 6   # code books 2 to 7
+
+
+@dataclass
+class FineGeneration:
+    """What ``to_fine`` returns, one entry per row of the batch."""
+    codes: List[torch.Tensor]                          # int64 [8, T_b]: rows 0 and 1 are the input
+    logits: Optional[List[torch.Tensor]] = None        # return_logits: float32 [n_b, 6, W, 1024]; positions below a window's ``rel`` hold NaN
+    window_ids: Optional[List[torch.Tensor]] = None    # return_logits: int64 [n_b, 6, W], what each pass wrote (-1 below ``rel``), overwritten ones included
+
+
+def fine_windows(T: int, W: int):
+    """The windows of a row of ``T`` frames at block ``W``: a list of ``(start, fill)``; window ``k`` reads positions ``[start, start + W)`` of the
+    row's work array of ``max(T, W)`` cells and predicts from ``fill`` on (buffer positions ``>= fill - start``)."""
+    H, L = W // 2, max(T, W)
+    n = max(0, -(-(T - W) // H)) + 1
+    return [(min(k * H, L - W), min(k * H, L - H)) for k in range(n)]
+
+
+def seeded_uniforms(seed: int, batch: int, n_max: int, block: int) -> np.ndarray:
+    return np.random.Generator(np.random.Philox(seed)).random((batch, n_max, N_PASSES, block), dtype=np.float32)
+
+
+def _as_rows(codes) -> List[np.ndarray]:
+    batch = list(codes) if isinstance(codes, (list, tuple)) else [codes]
+    rows = []
+    for i, c in enumerate(batch):
+        a = np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c)
+        if a.ndim == 3 and a.shape[0] == 1:
+            a = a[0]
+        if a.ndim != 2 or a.shape[0] != 2 or a.shape[1] < 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"to_fine: row {i} must be integer coarse codes [2, T] with T >= 1, got {a.dtype} {tuple(a.shape)}")
+        rows.append(np.ascontiguousarray(a, dtype=np.int64))
+    return rows
+
+
+class CoarseToFine(LibHandle):
+    """Owner of one ``at_fine`` handle. ``weights``: a checkpoint path, a ``{name: array}`` dict, or None for the seeded synthetic model."""
+
+    FAMILY = "fine"
+
+    def __init__(self, config: Optional[FineDecoderConfig] = None, device="cuda:0", weights: Union[None, str, os.PathLike, Dict[str, np.ndarray]] = None):
+        self.config = config or FineDecoderConfig()
+        if weights is None:
+            weights = self.config.weights
+
+        def host_tensors():
+            from . import weights as W
+            if weights is None:
+                return W.synth_fine_weights(self.config.synthetic_layers, self.config.synthetic_hidden, self.config.synthetic_block)
+            if isinstance(weights, dict):
+                return W.fine_tensors_from_state_dict(weights, "weights dict")
+            return W.read_fine_checkpoint(weights)
+
+        self._create(device, None, host_tensors)
+
+    def _finish_init(self) -> None:
+        self.n_layers = self._fn("num_layers")(self.handle)
+        self.hidden = self._fn("hidden")(self.handle)
+        self.block_size = self._fn("block_size")(self.handle)
+        self.has_bias = bool(self._fn("has_bias")(self.handle))
+        self._init_call_state()
+
+    def eval(self):
+        return self
+
+    def generate(self, codes, temperature: Optional[float] = 0.5, seed: int = 0, uniforms: Optional[np.ndarray] = None,
+                 return_logits: bool = False) -> FineGeneration:
+        """``codes``: integer ``[2, T]`` or a list of 1 to 64 of them, each of its own length. ``temperature=None``: the argmax, the lowest id among
+        equals. ``uniforms``: float32 ``[B, n_max, 6, W]``, the draw of row b, window k, code book 2 + j and buffer position t (``n_max``: the windows
+        of the longest row); from ``seed`` otherwise (``seeded_uniforms``)."""
+        rows = _as_rows(codes)
+        B, W = len(rows), self.block_size
+        if not 1 <= B <= self.config.max_rows:
+            raise ValueError(f"to_fine: 1 to {self.config.max_rows} rows per call, got {B}")
+        lens = [int(r.shape[1]) for r in rows]
+        n = [len(fine_windows(T, W)) for T in lens]
+        n_max, max_T = max(n), max(lens)
+        greedy = temperature is None
+        if not greedy:
+            if uniforms is None:
+                uniforms = seeded_uniforms(seed, B, n_max, W)
+            uniforms = np.ascontiguousarray(uniforms, dtype=np.float32)
+            if uniforms.shape != (B, n_max, N_PASSES, W):
+                raise ValueError(f"uniforms must be float32 [{B}, {n_max}, {N_PASSES}, {W}] (row, window, code book, buffer position), got {uniforms.shape}")
+        host = np.zeros((B, 2, max_T), dtype=np.int32)
+        for b, r in enumerate(rows):
+            host[b, :, :lens[b]] = np.clip(r, -1, self.config.codebook_size)   # what lies outside stays outside after the narrowing
+        dev = self.device
+        with torch.cuda.device(dev):
+            d_codes = torch.from_numpy(host).to(dev)
+            d_u = None if greedy else torch.from_numpy(uniforms).to(dev)
+            d_out = torch.full((B, 8, max_T), -1, dtype=torch.int32, device=dev)
+            d_logits = d_ids = None
+            if return_logits:
+                d_logits = torch.full((B, n_max, N_PASSES, W, 1024), float("nan"), dtype=torch.float32, device=dev)
+                d_ids = torch.full((B, n_max, N_PASSES, W), -1, dtype=torch.int32, device=dev)
+            nbytes = int(self._fn("state_bytes")(self.handle, B, max_T))
+            if nbytes == 0:
+                raise _cabi.HipLibraryError(f"at_fine_state_bytes failed: {_cabi.last_error()}")
+            state = self._workspace(nbytes)
+            self._status.zero_()
+            c_lens = (C.c_int32 * B)(*lens)
+            _cabi.check(self._fn("generate")(self.handle, d_codes.data_ptr(), max_T, c_lens, B, 1.0 if greedy else float(temperature), 1 if greedy else 0,
+                                             _cabi.ptr(d_u), n_max, d_out.data_ptr(), _cabi.ptr(d_logits), _cabi.ptr(d_ids), state.data_ptr(), state.numel(),
+                                             max_T, _cabi.current_stream_handle(dev), self._status.data_ptr()), "at_fine_generate")
+            out = d_out.cpu().to(torch.int64)   # synchronises
+        if self.last_status() & 1:
+            raise ValueError("at_fine_generate: a coarse code lies outside [0, 1024)")
+        self.last_raw_codes = out   # the whole [B, 8, max_T] buffer, -1 where nothing was written (tests)
+        result = FineGeneration(codes=[out[b, :, :lens[b]].clone() for b in range(B)])
+        if return_logits:
+            result.logits = [d_logits[b, :n[b]].cpu() for b in range(B)]
+            result.window_ids = [d_ids[b, :n[b]].cpu().to(torch.int64) for b in range(B)]
+        return result

@@ -1,6 +1,6 @@
 """Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoders (``gpt2_model.py``, ``decoder.py:210-239``) on the
-KV-cached HIP GPT (csrc/gpt.hip). The fine stage (bark, code books 3 to 8) is not here, so the semantic ``decode`` stays absent; the
-``[2, T]`` this stage yields is what the acoustic decoder at ``num_codebooks=2`` turns into audio.
+KV-cached HIP GPT (csrc/gpt.hip). The fine stage (bark, code books 3 to 8) is fine_decoder.py; the ``[2, T]`` this stage yields is what
+it takes, or what the acoustic decoder at ``num_codebooks=2`` turns into audio. The semantic ``decode`` stays absent: ``AudioToken.to_audio`` is its form here.
 
 Stated deviations from the reference: the draws come from a caller-visible uniform stream, not ``torch.multinomial``; a row whose length
 reaches the model's block finishes with ``"block_size"`` instead of having its context cropped; bias-free checkpoints only."""

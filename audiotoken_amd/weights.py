@@ -421,6 +421,114 @@ def gpt_tensors_from_state_dict(sd, what: str = "state dict") -> Dict[str, np.nd
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}
 
 
+# ---- the fine stage (csrc/fine.hip) -----------------------------------------------------------------------------------------------
+FINE_TABLE_ROWS, FINE_CODE_BOOKS, FINE_HEADS = 1056, 8, 7
+_FINE_LINEARS = ("attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj")
+# HF's BarkFineModel names -> bark's model_fine.py names, the canonical ones
+_FINE_HF_NAMES = (("input_embeds_layers.", "transformer.wtes."), ("position_embeds_layer.", "transformer.wpe."), ("layernorm_final.", "transformer.ln_f."),
+                  ("layers.", "transformer.h."))
+_FINE_HF_PARTS = ((".layernorm_1.", ".ln_1."), (".layernorm_2.", ".ln_2."), (".attn.att_proj.", ".attn.c_attn."), (".attn.out_proj.", ".attn.c_proj."),
+                  (".mlp.in_proj.", ".mlp.c_fc."), (".mlp.out_proj.", ".mlp.c_proj."))
+
+
+def synth_fine_weights(n_layer: int = 12, hidden: int = 1024, block: int = 1024, seed: int = 0, family: str = "uniform", bias: bool = False) -> Dict[str, np.ndarray]:
+    """Seeded synthetic weights of the fine stage under bark's names. ``"uniform"``: every matrix N(0, 0.02), the two ``c_proj`` at 0.02 / sqrt(2 n_layer);
+    ``"peaky"``: the same with the heads at std 0.16, so that the logits spread over tens of units. LayerNorm gains are drawn from [0.8, 1.2] and
+    LayerNorm biases from [-0.1, 0.1] (nonzero), so that a kernel that dropped either would not pass; ``bias=True`` adds N(0, 0.02) biases to the four
+    linears of every block. The heads are not tied to the tables."""
+    if family not in GPT_FAMILIES:
+        raise ValueError(f"weight family {family!r}: one of {GPT_FAMILIES}")
+    if hidden not in (768, 1024):
+        raise ValueError(f"hidden = {hidden}: the fine stage is built for 768 or 1024")
+    E, F = hidden, 4 * hidden
+    proj_std = 0.02 / float(np.sqrt(2.0 * n_layer))
+    jobs = [(f"transformer.wtes.{i}.weight", (FINE_TABLE_ROWS, E), 0.02) for i in range(FINE_CODE_BOOKS)]
+    jobs += [("transformer.wpe.weight", (block, E), 0.02)]
+    jobs += [(f"lm_heads.{j}.weight", (FINE_TABLE_ROWS, E), 0.16 if family == "peaky" else 0.02) for j in range(FINE_HEADS)]
+    for i in range(n_layer):
+        p = f"transformer.h.{i}"
+        shapes = {"attn.c_attn": ((3 * E, E), 0.02), "attn.c_proj": ((E, E), proj_std), "mlp.c_fc": ((F, E), 0.02), "mlp.c_proj": ((E, F), proj_std)}
+        for lin in _FINE_LINEARS:
+            shape, std = shapes[lin]
+            jobs.append((f"{p}.{lin}.weight", shape, std))
+            if bias:
+                jobs.append((f"{p}.{lin}.bias", (shape[0],), 0.02))
+    w = _run_jobs([(name, (lambda name=name, shape=shape, std=std: prng.irwin_hall("fine." + name, shape, std, seed))) for name, shape, std in jobs])
+    for name in [f"transformer.h.{i}.ln_{j}" for i in range(n_layer) for j in (1, 2)] + ["transformer.ln_f"]:
+        w[name + ".weight"] = prng.uniform("fine." + name + ".weight", (E,), 0.8, 1.2, seed)
+        b = prng.uniform("fine." + name + ".bias", (E,), 0.02, 0.1, seed)
+        w[name + ".bias"] = b * np.where(prng.uniform01("fine." + name + ".sign", E, seed) < 0.5, np.float32(-1), np.float32(1))
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in w.items()}
+
+
+def read_fine_checkpoint(path) -> Dict[str, np.ndarray]:
+    """A fine-stage checkpoint as the tensors ``at_fine_finalize`` takes: ``torch.load(path)``, the state dict itself or nested under ``["model"]``,
+    under bark's names or HF's (``fine_tensors_from_state_dict``)."""
+    import torch
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(ckpt, dict) and isinstance(ckpt.get("model"), dict):
+        ckpt = ckpt["model"]
+    if not isinstance(ckpt, dict):
+        raise ValueError(f"{path}: not a fine-stage checkpoint (a state dict, or a dict with a 'model' state dict, is expected)")
+    return fine_tensors_from_state_dict(ckpt, what=str(path))
+
+
+def fine_tensors_from_state_dict(sd, what: str = "state dict") -> Dict[str, np.ndarray]:
+    """{bark name: float32 array} from a state dict under bark's names (``transformer.wtes.{i}.weight``, ...) or HF's (``input_embeds_layers.{i}.weight``,
+    ...), with an optional ``_orig_mod.`` prefix. Refused with ``ValueError``: a missing table, head or LayerNorm bias, a width other than 768 / 1024, a
+    block that is no multiple of 128 in [128, 1024], linear biases on some linears only."""
+    out: Dict[str, np.ndarray] = {}
+    for k, v in sd.items():
+        for pre in ("_orig_mod.", "fine_acoustics."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        if k.endswith(".attn.bias"):      # a mask buffer, not a parameter
+            continue
+        for hf, ours in _FINE_HF_NAMES:
+            if k.startswith(hf):
+                k = ours + k[len(hf):]
+                break
+        for hf, ours in _FINE_HF_PARTS:
+            k = k.replace(hf, ours)
+        out[k] = np.ascontiguousarray(v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, dtype=np.float32), dtype=np.float32)
+    wpe = out.get("transformer.wpe.weight")
+    if wpe is None or wpe.ndim != 2:
+        raise ValueError(f"{what}: transformer.wpe.weight is missing")
+    W, E = wpe.shape
+    if E not in (768, 1024):
+        raise ValueError(f"{what}: n_embd = {E}; the HIP fine stage implements 768 or 1024 (heads of 64)")
+    if W % 128 or not 128 <= W <= 1024:
+        raise ValueError(f"{what}: block size {W}; the HIP fine stage implements multiples of 128 from 128 to 1024")
+    n_layer = 0
+    while f"transformer.h.{n_layer}.ln_1.weight" in out:
+        n_layer += 1
+    if n_layer < 1:
+        raise ValueError(f"{what}: no transformer block (transformer.h.0.ln_1.weight is missing)")
+    need = {f"transformer.wtes.{i}.weight": (FINE_TABLE_ROWS, E) for i in range(FINE_CODE_BOOKS)}
+    need.update({f"lm_heads.{j}.weight": (FINE_TABLE_ROWS, E) for j in range(FINE_HEADS)})
+    need.update({"transformer.ln_f.weight": (E,), "transformer.ln_f.bias": (E,)})
+    lin_shapes = {"attn.c_attn": (3 * E, E), "attn.c_proj": (E, E), "mlp.c_fc": (4 * E, E), "mlp.c_proj": (E, 4 * E)}
+    biases = [f"transformer.h.{i}.{lin}.bias" for i in range(n_layer) for lin in _FINE_LINEARS]
+    have = [b for b in biases if b in out]
+    if have and len(have) != len(biases):
+        missing = next(b for b in biases if b not in out)
+        raise ValueError(f"{what}: mixed biases: {have[0]} is there and {missing} is not; the linears carry a bias in every block or in none")
+    for i in range(n_layer):
+        p = f"transformer.h.{i}"
+        for ln in ("ln_1", "ln_2"):
+            need[f"{p}.{ln}.weight"] = need[f"{p}.{ln}.bias"] = (E,)
+        for lin, shape in lin_shapes.items():
+            need[f"{p}.{lin}.weight"] = shape
+            if have:
+                need[f"{p}.{lin}.bias"] = (shape[0],)
+    for name, shape in need.items():
+        if name not in out:
+            raise ValueError(f"{what}: {name} is missing")
+        if tuple(out[name].shape) != shape:
+            raise ValueError(f"{what}: {name} has shape {tuple(out[name].shape)}, expected {shape}")
+    return {k: out[k] for k in need} | {"transformer.wpe.weight": wpe}
+
+
 def read_hf_state_dict(model_dir: str, strip_prefixes=()) -> Dict[str, np.ndarray]:
     """A HF ``save_pretrained`` directory -> {name: float32 array}. Understands ``model.safetensors``, the sharded form
     (``model.safetensors.index.json`` + ``model-0000i-of-0000n.safetensors``) and the legacy ``pytorch_model.bin`` (+ its sharded index).

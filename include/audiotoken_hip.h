@@ -669,6 +669,43 @@ int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, 
 int at_op_topk_sample(const float* logits_dev, int B, int V, float temperature, int top_k, const float* uniforms_dev, const int32_t* allow, int32_t* out_dev,
                       at_stream_t stream);
 
+/* ---- the fine stage: coarse code books -> all eight (csrc/fine.hip) -----------------------------------------------------------
+ * bark's non-causal fine transformer: 8 embedding tables wtes[i] [1056][E] and learned positions wpe [W][E]; n_layer pre-LN blocks (LayerNorm with gain
+ * and bias, eps 1e-5; E / 64 heads of 64; attention over the whole window without a mask, scaled by 1/8; MLP E -> 4E -> E with the erf GELU; the four
+ * linears of every block with a bias or all without); a final LayerNorm; 7 heads lm_heads[j] [1056][E], lm_heads[j] predicting code book j + 1. Tensors
+ * carry bark's names ("transformer.wtes.<i>.weight", "transformer.h.<l>.attn.c_attn.weight", "lm_heads.<j>.weight", ...; at_required_tensors("fine",
+ * n_layer, with_bias, ...) lists them at E = 1024, W = 1024). finalize takes E (768 or 1024), W (a multiple of 128, 128 to 1024) and n_layer (1 to 48)
+ * from the shapes and refuses anything else. */
+typedef struct at_fine at_fine_t;
+at_fine_t* at_fine_create(int device_id);
+int at_fine_set_tensor(at_fine_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int at_fine_finalize(at_fine_t* h);
+void at_fine_destroy(at_fine_t* h);
+int at_fine_num_layers(const at_fine_t* h);
+int at_fine_hidden(const at_fine_t* h);
+int at_fine_block_size(const at_fine_t* h);
+int at_fine_has_bias(const at_fine_t* h);
+/* Windows of a row of T frames (1 to 262144): max(0, ceil((T - W) / (W / 2))) + 1. 0 = error. */
+int at_fine_num_windows(const at_fine_t* h, int T);
+/* Bytes of the caller-owned device state of one at_fine_generate call with B rows (1 to 64) of at most max_T frames: the rows' work arrays
+ * [max(max_T, W)][8] and the activations of B windows. 0 = error. */
+size_t at_fine_state_bytes(const at_fine_t* h, int B, int max_T);
+/* Fill code books 2 to 7 of B rows in one stream-ordered call that allocates nothing and never waits for the device. coarse_dev: device int32
+ * [B][2][t_stride], row b holding lens[b] frames (lens is a HOST array; 1 <= lens[b] <= min(t_stride, max_T)). A row's work array is [L][8] with
+ * L = max(T, W), every cell 1024 but the coarse codes; window k of its n windows covers positions [start, start + W) with start = min(k W/2, L - W) and
+ * predicts buffer positions >= rel = min(k W/2, L - W/2) - start: for c = 2..7 the model runs on the window's current contents and one id per predicted
+ * position is written into channel c, padding positions included. Pass k of the call runs window k of every row that has one as one batch.
+ * greedy = 1: the id is the argmax of the logits [0, 1024), the lowest id among equals (temperature and uniforms_dev are not read). greedy = 0: with
+ * u = uniforms_dev[b][k][c - 2][t] (device float32 [B][n_max][6][W], n_max >= the windows of the longest row): zt_i = z_i / temperature (one IEEE fp32
+ * division), m = max zt, p_i = expf(zt_i - m), S = sum p_i; the id is the lowest whose running sum in ascending id order exceeds u * S; if rounding
+ * leaves none, the highest id with p_i > 0. out_dev: device int32 [B][8][t_stride]; entries at t >= lens[b] are left as they were. logits_out_dev NULL
+ * or device float32 [B][n_max][6][W][1024], window_ids_dev NULL or device int32 [B][n_max][6][W]: the logits every written id was drawn from and the id;
+ * entries of positions < rel and of windows a row does not have are left as they were. status_dev NULL or a device word: bit 0 = a coarse code outside
+ * [0, 1024) was clamped. Every argument is checked before the device is touched. Not re-entrant per handle. */
+int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
+                     const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
+                     int max_T, at_stream_t stream, int32_t* status_dev);
+
 #ifdef __cplusplus
 }
 #endif
