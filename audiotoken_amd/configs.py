@@ -92,6 +92,7 @@ class HubertDecoderConfig:
     max_source_tokens: int = 256
     num_codebooks: int = 2       # the coarse code books stage 1 produces
     codebook_size: int = 1024
+    ids_per_source_token: int = 3   # the long form's alignment: 75 frames/s x 2 code books / 50 semantic ids/s
     weights: Optional[str] = os.environ.get("AUDIOTOKEN_HUBERT_DECODER_WEIGHTS")
 
 

@@ -318,7 +318,7 @@ class AudioToken:
         return km
 
     def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0, uniforms=None,
-                    constrain: bool = False, return_logits: bool = False):
+                    constrain: bool = False, return_logits: bool = False, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None):
         """Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoder (its GPT, ``decoder.py:210-239``) on the
         KV-cached HIP decoder (semantic_decoder.py). Semantic tokenizers only. ``tokens``: a tensor / array / path of semantic ids (any
         shape, flattened), or a list of up to 64 of them, generated as one batch. Returns an ``AcousticGeneration``: ``codes`` (a list of int64
@@ -327,9 +327,14 @@ class AudioToken:
         The draws are ``uniforms`` (float32 ``[B, max_new_tokens]``) or, from ``seed``, ``np.random.Generator(np.random.Philox(seed)).random(...)``: not
         ``torch.multinomial``'s stream, but the same distribution. ``constrain=True`` lets step s produce only ids of code book ``s % 2`` (and STOP on even
         s), so that every result is a valid ``[2, T]``; the default samples the reference's unconstrained distribution. Weights: the constructor's
-        ``decoder_weights=`` (a checkpoint path or a ``{name: array}`` dict), else the seeded synthetic model."""
+        ``decoder_weights=`` (a checkpoint path or a ``{name: array}`` dict), else the seeded synthetic model.
+        Without ``long_form`` a source is cut to its first ``max_source_tokens`` ids (5 s), as the reference cuts it. ``long_form=True`` walks the whole
+        source (up to 65536 ids) in windows of ``window`` ids every ``hop`` ids, carrying the acoustic ids of the overlap: always
+        constrained, ``uniforms`` indexed by the position in the row's result, ``windows`` of the result the schedule that ran."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_acoustic maps semantic ids to acoustic code books; {self.tokenizer_name} has no semantic ids")
+        if not long_form and (window is not None or hop is not None):
+            raise ValueError("to_acoustic: window= and hop= belong to long_form=True")
         if getattr(self, "semantic_decoder", None) is None:
             from .configs import HubertDecoderConfig, Wav2VecBertDecoderConfig
             from .semantic_decoder import SemanticToAcoustic
@@ -338,6 +343,9 @@ class AudioToken:
             if w is None and cfg.weights is None:
                 logger.warning("to_acoustic: no decoder_weights given; using the seeded synthetic GPT")
             self.semantic_decoder = SemanticToAcoustic(cfg, device=self.device, weights=w)
+        if long_form:
+            return self.semantic_decoder.to_acoustic_long(tokens, window=window, hop=hop, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
+                                                          seed=seed, uniforms=uniforms, return_logits=return_logits)
         return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
                                                  constrain=constrain, return_logits=return_logits)
 
@@ -362,14 +370,17 @@ class AudioToken:
         return self.fine_decoder.generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
 
     def to_audio(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, fine_temperature: Optional[float] = 0.5,
-                 seed: int = 0, uniforms=None, fine_uniforms=None):
+                 seed: int = 0, uniforms=None, fine_uniforms=None, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None):
         """Semantic ids -> audio, this project's form of the reference's semantic ``decode`` (``decoder.py:210-243``): ``to_acoustic(constrain=True)``, then
         ``to_fine``, then the acoustic decoder at 8 code books (bandwidth 6). Semantic tokenizers only. ``tokens`` as ``to_acoustic`` takes them. Returns
         ``(audio, coarse, fine)``: a list of one float32 ``(1, 320 * T_b)`` CPU tensor per source, the ``AcousticGeneration`` and the ``FineGeneration``.
-        ``uniforms`` / ``fine_uniforms`` / ``seed`` are the two stages' draws. A source whose stage 1 produced no whole frame raises ``ValueError``."""
+        ``uniforms`` / ``fine_uniforms`` / ``seed`` are the two stages' draws. A source whose stage 1 produced no whole frame raises ``ValueError``.
+        ``long_form=True`` (with ``window`` / ``hop``) makes stage 1 the long form of ``to_acoustic``, so that the audio covers the whole source and not its
+        first 5 s; the two later stages take any length as they are."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_audio maps semantic ids to audio; {self.tokenizer_name} has no semantic ids (its own decode is the way back)")
-        coarse = self.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms, constrain=True)
+        coarse = self.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms, constrain=True,
+                                  long_form=long_form, window=window, hop=hop)
         for b, c in enumerate(coarse.codes):
             if c is None or c.shape[1] < 1:
                 raise ValueError(f"to_audio: source {b} produced no whole frame of coarse codes (finish: {coarse.finish[b]})")

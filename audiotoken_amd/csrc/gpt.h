@@ -15,6 +15,11 @@ constexpr int GPT_ROW_TILE = 16;       // activation rows one pass of a linear k
 constexpr int GPT_CHECK_EVERY = 16;    // steps between two looks of the host at the rows' finish flags
 // finish[] of at_gpt_generate
 enum { GPT_RUNNING = 0, GPT_FINISH_STOP = 1, GPT_FINISH_MAX_NEW = 2, GPT_FINISH_BLOCK = 3 };
+constexpr int GPT_PASS_DONE = 4;       // done[] of a row whose non-final window is complete (at_gpt_generate_long): never written to finish[]
+constexpr int GPT_MAX_SOURCE = 65536;  // source ids of one row of at_gpt_generate_long
+
+// The long form's schedule: windows of a source of N ids at window S and hop H; window k reads source ids [k H, k H + min(S, N - k H)).
+inline int gpt_long_windows(int N, int S, int H) { return N <= S ? 1 : (N - S + H - 1) / H + 1; }
 
 struct GptHostTensor {
     std::vector<int64_t> shape;

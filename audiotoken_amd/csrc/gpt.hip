@@ -8,6 +8,7 @@
 //                       A prefill of more than 64 tokens runs its four linears per layer on the fp32 matrix-core GEMM instead (gemm_f32.hip, launch_gemm).
 //   gpt_attn_kernel     causal attention of one query over its row's cache, one workgroup of 4 waves per (token, head)
 //   gpt_sample_kernel   temperature, allow ranges, exact top-k threshold (radix select), softmax weights and the inverse-CDF draw, one workgroup per row
+//   gpt_window_kernel   the long form: the prompts of one window of every row, from the source ids and the row's own output stream
 // Nothing here adds floats atomically: every sum has one order, so a call repeated gives the same tokens.
 #include <cmath>
 #include <cstring>
@@ -347,6 +348,12 @@ struct Allow {
     int on;
     int lo0, hi0, lo1, hi1;   // ids in [lo0, hi0) or [lo1, hi1) are allowed
 };
+// One row of one pass of the long form (at_gpt_generate_long): which row of the caller's arrays it is, where in that row's stream its step 0 lies (out_ids,
+// uniforms and logits_out are indexed by stream position), how many steps it has, what it may produce on even / odd steps and which id stops it (-1: none).
+struct SampleRow {
+    int out_row, base, budget, stop_token, final_window;
+    Allow allow[2];
+};
 struct SampleArgs {
     const float* logits;      // [B][V]
     int V, top_k;
@@ -357,8 +364,10 @@ struct SampleArgs {
     int* out;                 // the op alone: out[b] = token; generation: nullptr
     // generation
     int *len, *done, *cur, *out_ids, *out_len, *finish;
-    float* logits_out;        // nullable [B][max_new][V]
+    float* logits_out;        // nullable [B][out_stride][V]
     int max_new, stop_token, block;
+    int out_stride;           // ids of one row of out_ids (at_gpt_generate: max_new)
+    const SampleRow* rows;    // nullable [B]: the long form's per-row rules; nullptr: the call's own scalars
 };
 
 // floats as unsigned keys in the same order
@@ -384,8 +393,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     if (generating && a.done[b] != GPT_RUNNING) return;   // a finished row writes nothing more (uniform over the workgroup)
     const int V = a.V;
     const float* z = a.logits + (size_t)b * V;
+    // where the step's id, draw and logits live: row b at a.step, or the long form's row and stream position
+    const SampleRow* pr = a.rows ? a.rows + b : nullptr;
+    if (pr && a.step >= pr->budget) return;
+    const int orow = pr ? pr->out_row : b, pos = (pr ? pr->base : 0) + a.step;
+    const Allow allow = pr ? pr->allow[a.step & 1] : a.allow;
     if (generating && a.logits_out) {
-        float* dst = a.logits_out + ((size_t)b * a.max_new + a.step) * V;
+        float* dst = a.logits_out + ((size_t)orow * a.out_stride + pos) * V;
         for (int i = tid; i < V; i += SAMPLE_THREADS) dst[i] = z[i];
     }
     // ---- the k-th largest tempered value, exactly: radix select over the order keys, 8 bits a pass, and the maximum on the way
@@ -397,7 +411,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
         __syncthreads();
         const unsigned prefix = sel_prefix, need = sel_k, mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
         for (int i = tid; i < V; i += SAMPLE_THREADS) {
-            const float v = tempered(z, i, a.temperature, a.allow);
+            const float v = tempered(z, i, a.temperature, allow);
             if (pass == 0) mx = fmaxf(mx, v);
             const unsigned k = order_key(v);
             if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
@@ -426,7 +440,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     // weights are scanned (shuffle scan), the groups chain through a carry, the waves' totals are added in wave order. The first walk gives the waves' totals and S,
     // the second the running sums, its carry starting from the total of the waves before.
     const int per_wave = ((V + SAMPLE_THREADS / 64 - 1) / (SAMPLE_THREADS / 64) + 63) / 64 * 64, first = wave * per_wave;
-    const float u = a.uniforms[(size_t)b * a.u_stride + a.step];
+    const float u = a.uniforms[(size_t)orow * a.u_stride + pos];
     float before = 0.f, target = 0.f;
     bool found = false;
     int top = -1;
@@ -435,7 +449,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
         for (int g = 0; g < per_wave; g += 64) {
             const int i = first + g + lane;
             float v = -INFINITY;
-            if (i < V) v = tempered(z, i, a.temperature, a.allow);
+            if (i < V) v = tempered(z, i, a.temperature, allow);
             const bool kept = i < V && v >= thresh;
             float incl = kept ? expf(v - m) : 0.f;
 #pragma unroll
@@ -466,17 +480,21 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     const int tok = best_id < V ? best_id : max(high_id, 0);
     if (!generating) { a.out[b] = tok; return; }
     // ---- the row's bookkeeping: stop, max_new_tokens, block_size in that order
-    if (tok == a.stop_token) {
-        a.done[b] = a.finish[b] = GPT_FINISH_STOP;
+    if (tok == (pr ? pr->stop_token : a.stop_token)) {
+        a.done[b] = a.finish[orow] = GPT_FINISH_STOP;
         return;
     }
-    a.out_ids[(size_t)b * a.max_new + a.step] = tok;
-    a.out_len[b] = a.step + 1;
+    a.out_ids[(size_t)orow * a.out_stride + pos] = tok;
+    a.out_len[orow] = pos + 1;
     a.cur[b] = tok;
     const int total = a.len[b] + 1;
     a.len[b] = total;
-    if (a.step + 1 >= a.max_new) a.done[b] = a.finish[b] = GPT_FINISH_MAX_NEW;
-    else if (total >= a.block) a.done[b] = a.finish[b] = GPT_FINISH_BLOCK;
+    if (pr && !pr->final_window) {   // the window's count is exact; the row is done for this pass, not for the call
+        if (a.step + 1 >= pr->budget) a.done[b] = GPT_PASS_DONE;
+        return;
+    }
+    if (a.step + 1 >= a.max_new) a.done[b] = a.finish[orow] = GPT_FINISH_MAX_NEW;
+    else if (total >= a.block) a.done[b] = a.finish[orow] = GPT_FINISH_BLOCK;
 }
 
 int check_allow(const int32_t* r, int V, Allow* out) {
@@ -493,6 +511,84 @@ int check_sampling(float temperature, int top_k) {
     AT_REQUIRE(std::isfinite(temperature) && temperature > 0.0f, "temperature must be a positive finite number");
     AT_REQUIRE(top_k >= 1, "top_k must be at least 1");
     return 0;
+}
+
+// ---- the long form: one window of every row that has one --------------------------------------------------------------------
+struct LongPass {
+    int off[GPT_MAX_B + 1];          // pass row j's prompt tokens are the pass's tokens [off[j], off[j + 1])
+    int row[GPT_MAX_B];              // the caller's row that pass row j is
+    unsigned long long final_mask;   // bit j: this is the row's last window
+};
+struct LongRules {
+    int k, S, H, r, semantic_offset, semantic_vocab, infer_token, stop_token, max_new, block;
+    Allow mid[2], last[2];           // even / odd steps of a non-final and of a final window
+};
+
+// Start of pass k: the prompt rows (source ids + the offset, INFER, the carry out of the row's own stream), the prefill's token list, the rows' state and
+// their rules for the sampler. A source id outside [0, semantic_vocab) is clamped and reported in bit 0 of *status.
+__global__ void gpt_window_kernel(LongPass p, LongRules q, int Bk, int R, const int* src, int src_stride, const int* out_ids, int out_stride, int* prompts,
+                                  int prompt_stride, int* len, int* done, int* cur, int* last_row, int* tok_row, int* tok_pos, SampleRow* rows, int* out_len,
+                                  int* finish, int* status) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int carry = q.k > 0 ? q.r * (q.S - q.H) : 0;
+    if (i < R) {
+        int j = 0;
+        while (j + 1 < Bk && p.off[j + 1] <= i) ++j;
+        const int b = p.row[j], pos = i - p.off[j], n_src = p.off[j + 1] - p.off[j] - 1 - carry;
+        int id;
+        if (pos < n_src) {
+            id = src[(size_t)b * src_stride + q.k * q.H + pos];
+            if (id < 0 || id >= q.semantic_vocab) {
+                if (status) atomicOr(status, 1);
+                id = min(max(id, 0), q.semantic_vocab - 1);
+            }
+            id += q.semantic_offset;
+        } else if (pos == n_src) {
+            id = q.infer_token;
+        } else {
+            id = out_ids[(size_t)b * out_stride + q.r * q.k * q.H + (pos - n_src - 1)];
+        }
+        prompts[(size_t)j * prompt_stride + pos] = id;
+        tok_row[i] = j;
+        tok_pos[i] = pos;
+    }
+    if (i < Bk) {
+        const int P = p.off[i + 1] - p.off[i], b = p.row[i];
+        const bool last = (p.final_mask >> i) & 1ull;
+        len[i] = P;
+        done[i] = GPT_RUNNING;
+        cur[i] = 0;
+        last_row[i] = p.off[i + 1] - 1;
+        SampleRow s;
+        s.out_row = b;
+        s.base = q.r * q.k * q.H + carry;
+        s.budget = last ? min(q.max_new, q.block - P) : q.r * q.S - carry;
+        s.stop_token = last ? q.stop_token : -1;
+        s.final_window = last ? 1 : 0;
+        s.allow[0] = last ? q.last[0] : q.mid[0];
+        s.allow[1] = last ? q.last[1] : q.mid[1];
+        rows[i] = s;
+        if (q.k == 0) { out_len[b] = 0; finish[b] = GPT_RUNNING; }
+    }
+}
+
+struct LongState {
+    GptState g;
+    int* prompts;      // [B][cap]
+    SampleRow* rows;   // [GPT_MAX_B]
+    size_t bytes;
+};
+
+LongState carve_long_state(void* base, int B, int cap, int vocab, int n_layer) {
+    LongState s{};
+    s.g = carve_state(base, B, cap, vocab, n_layer);
+    char* p = static_cast<char*>(base);
+    size_t off = s.g.bytes;
+    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += round256(bytes); return r; };
+    s.prompts = (int*)take((size_t)B * cap * 4);
+    s.rows = (SampleRow*)take(GPT_MAX_B * sizeof(SampleRow));
+    s.bytes = off;
+    return s;
 }
 
 // ---- one pass of the model over R tokens: the prefill of every prompt (prompts != nullptr) or one step of every row (R = B) -----------------------------
@@ -716,7 +812,7 @@ int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, 
     SampleArgs sa{};
     sa.logits = s.logits; sa.V = h->vocab; sa.top_k = top_k; sa.temperature = temperature; sa.uniforms = uniforms_dev; sa.u_stride = max_new;
     sa.len = s.len; sa.done = s.done; sa.cur = s.cur; sa.out_ids = out_ids_dev; sa.out_len = out_len_dev; sa.finish = finish_dev;
-    sa.logits_out = logits_out_dev; sa.max_new = max_new; sa.stop_token = stop_token; sa.block = h->block;
+    sa.logits_out = logits_out_dev; sa.max_new = max_new; sa.stop_token = stop_token; sa.block = h->block; sa.out_stride = max_new;
     for (int step = 0; step < max_new; ++step) {
         if (step > 0)
             if (int rc = run_pass(h, s, nullptr, 0, B, B, max_len, status_dev, stream)) return rc;
@@ -730,6 +826,126 @@ int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, 
             bool all = true;
             for (int b = 0; b < B; ++b) all = all && h->flags_host[b] != GPT_RUNNING;
             if (all) break;
+        }
+    }
+    return 0;
+}
+
+int at_gpt_long_num_windows(int N, int S, int H) {
+    if (!(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0 && H <= S && N >= 1 && N <= GPT_MAX_SOURCE)) {
+        set_error("at_gpt_long_num_windows: S and H must be even with 2 <= H <= S, N 1 to 65536");
+        return 0;
+    }
+    return gpt_long_windows(N, S, H);
+}
+
+size_t at_gpt_long_state_bytes(const at_gpt_t* h, int B, int max_len) {
+    if (!(h && h->finalized)) { set_error("at_gpt_long_state_bytes: the model is not finalized"); return 0; }
+    if (!(B >= 1 && B <= GPT_MAX_B)) { set_error("at_gpt_long_state_bytes: B must be 1 to 64"); return 0; }
+    if (!(max_len >= 1 && max_len <= h->block)) { set_error("at_gpt_long_state_bytes: max_len must be 1 to the model's block size"); return 0; }
+    return carve_long_state(nullptr, B, max_len, h->vocab, h->n_layer).bytes;
+}
+
+int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, int S, int H, int r, int semantic_offset,
+                         int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                         const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
+                         float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream_, int32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized, "the model is not finalized");
+    AT_REQUIRE(B >= 1 && B <= GPT_MAX_B, "B must be 1 to 64");
+    AT_REQUIRE(src_dev && src_len && uniforms_dev && out_ids_dev && out_len_dev && finish_dev, "null pointer");
+    AT_REQUIRE(state_dev != nullptr, "null state");
+    const int V = h->vocab, block = h->block;
+    AT_REQUIRE(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0, "the window S and the hop H must be even, at least 2");
+    AT_REQUIRE(H <= S, "the hop H must not exceed the window S");
+    AT_REQUIRE(r >= 1 && r <= GPT_MAX_BLOCK, "r (acoustic ids per source id) must be 1 to 1024");
+    AT_REQUIRE((int64_t)S + 1 + (int64_t)r * S <= block, "a window does not fit: S + 1 + r S must not exceed the model's block size");
+    AT_REQUIRE(src_stride >= 1, "src_stride must be at least 1");
+    AT_REQUIRE(max_new >= 1 && max_new <= GPT_MAX_BLOCK, "max_new must be 1 to 1024");
+    if (int rc = check_sampling(temperature, top_k)) return rc;
+    AT_REQUIRE(semantic_offset >= 0 && semantic_vocab >= 1 && (int64_t)semantic_offset + semantic_vocab <= V, "the semantic ids must lie inside the vocabulary");
+    AT_REQUIRE(infer_token >= 0 && infer_token < V, "infer_token is not in the vocabulary");
+    AT_REQUIRE(acoustic_offset >= 0 && codebook_size >= 1 && (int64_t)acoustic_offset + 2 * (int64_t)codebook_size <= V,
+               "the two code books must lie inside the vocabulary");
+    AT_REQUIRE(stop_token < V, "stop_token is not in the vocabulary (negative: none)");
+    // ---- the schedule: rows in descending order of their window counts, so that the rows of pass k are the first Bk of them
+    int n_win[GPT_MAX_B], order[GPT_MAX_B];
+    int n_max = 0, need_len = 0;
+    int64_t need_stride = 0;
+    const int carry = r * (S - H);
+    for (int b = 0; b < B; ++b) {
+        if (src_len[b] < 1 || src_len[b] > src_stride || src_len[b] > GPT_MAX_SOURCE) {
+            set_error("at_gpt_generate_long: src_len of row " + std::to_string(b) + " must be 1 to min(src_stride, 65536)");
+            return -1;
+        }
+        const int n = gpt_long_windows(src_len[b], S, H);
+        n_win[b] = n;
+        n_max = n > n_max ? n : n_max;
+        const int P = src_len[b] - (n - 1) * H + 1 + (n > 1 ? carry : 0);   // the final window's prompt
+        const int budget = max_new < block - P ? max_new : block - P;
+        const int64_t end = (n > 1 ? (int64_t)r * (n - 1) * H + carry : 0) + budget;
+        need_stride = end > need_stride ? end : need_stride;
+        need_len = P + budget > need_len ? P + budget : need_len;
+        if (n > 1 && S + 1 + r * S > need_len) need_len = S + 1 + r * S;
+        int at = b;
+        while (at > 0 && n_win[order[at - 1]] < n) { order[at] = order[at - 1]; --at; }
+        order[at] = b;
+    }
+    AT_REQUIRE(out_stride >= need_stride && u_stride >= need_stride, "out_stride and u_stride must hold the longest row's stream");
+    AT_REQUIRE(max_len >= need_len && max_len <= block, "max_len must hold the longest window with its new ids and not exceed the block size");
+    LongRules q{};
+    q.S = S; q.H = H; q.r = r; q.semantic_offset = semantic_offset; q.semantic_vocab = semantic_vocab; q.infer_token = infer_token;
+    q.stop_token = stop_token < 0 ? -1 : stop_token; q.max_new = max_new; q.block = block;
+    q.mid[0] = Allow{1, acoustic_offset, acoustic_offset + codebook_size, 0, 0};
+    q.mid[1] = Allow{1, acoustic_offset + codebook_size, acoustic_offset + 2 * codebook_size, 0, 0};
+    q.last[0] = q.mid[0];
+    q.last[1] = q.mid[1];
+    if (stop_token >= 0) { q.last[0].lo1 = stop_token; q.last[0].hi1 = stop_token + 1; }
+    const LongState ls = carve_long_state(state_dev, B, max_len, V, h->n_layer);
+    const GptState& s = ls.g;
+    AT_REQUIRE(state_bytes >= ls.bytes, "state too small: at_gpt_long_state_bytes(h, B, max_len)");
+    // ---- nothing above touched the device
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    hipStream_t stream = (hipStream_t)stream_;
+    SampleArgs sa{};
+    sa.logits = s.logits; sa.V = V; sa.top_k = top_k; sa.temperature = temperature; sa.uniforms = uniforms_dev; sa.u_stride = u_stride;
+    sa.len = s.len; sa.done = s.done; sa.cur = s.cur; sa.out_ids = out_ids_dev; sa.out_len = out_len_dev; sa.finish = finish_dev;
+    sa.logits_out = logits_out_dev; sa.max_new = max_new; sa.stop_token = -1; sa.block = block; sa.out_stride = out_stride; sa.rows = ls.rows;
+    for (int k = 0; k < n_max; ++k) {
+        LongPass p{};
+        int Bk = 0, steps = 0, mid_steps = 0;
+        while (Bk < B && n_win[order[Bk]] > k) {
+            const int b = order[Bk];
+            const bool last = k == n_win[b] - 1;
+            const int n_src = last ? src_len[b] - k * H : S, P = n_src + 1 + (k > 0 ? carry : 0);
+            const int budget = last ? (max_new < block - P ? max_new : block - P) : r * S - (k > 0 ? carry : 0);
+            p.off[Bk + 1] = p.off[Bk] + P;
+            p.row[Bk] = b;
+            if (last) p.final_mask |= 1ull << Bk;
+            else mid_steps = budget > mid_steps ? budget : mid_steps;
+            steps = budget > steps ? budget : steps;
+            ++Bk;
+        }
+        const int R = p.off[Bk];
+        q.k = k;
+        hipLaunchKernelGGL(gpt_window_kernel, dim3(((R > Bk ? R : Bk) + 255) / 256), dim3(256), 0, stream, p, q, Bk, R, src_dev, src_stride, out_ids_dev, out_stride,
+                           ls.prompts, max_len, s.len, s.done, s.cur, s.last_row, s.tok_row, s.tok_pos, ls.rows, out_len_dev, finish_dev, status_dev);
+        AT_CHECK_HIP(hipGetLastError());
+        if (int rc = run_pass(h, s, ls.prompts, max_len, Bk, R, max_len, status_dev, stream)) return rc;
+        for (int step = 0; step < steps; ++step) {
+            if (step > 0)
+                if (int rc = run_pass(h, s, nullptr, 0, Bk, Bk, max_len, status_dev, stream)) return rc;
+            sa.step = step;
+            hipLaunchKernelGGL(gpt_sample_kernel, dim3(Bk), dim3(SAMPLE_THREADS), 0, stream, sa);
+            AT_CHECK_HIP(hipGetLastError());
+            // the host's only look at the device; a non-final window never ends early, so there is nothing to see before the last of them is complete
+            if ((step + 1) % GPT_CHECK_EVERY == 0 && step + 1 < steps && step + 1 >= mid_steps) {
+                AT_CHECK_HIP(hipMemcpyAsync(h->flags_host, s.done, Bk * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                AT_CHECK_HIP(hipStreamSynchronize(stream));
+                bool all = true;
+                for (int j = 0; j < Bk; ++j) all = all && h->flags_host[j] != GPT_RUNNING;
+                if (all) break;
+            }
         }
     }
     return 0;

@@ -1,6 +1,8 @@
 """Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoders (``gpt2_model.py``, ``decoder.py:210-239``) on the
 KV-cached HIP GPT (csrc/gpt.hip). The fine stage (bark, code books 3 to 8) is fine_decoder.py; the ``[2, T]`` this stage yields is what
 it takes, or what the acoustic decoder at ``num_codebooks=2`` turns into audio. The semantic ``decode`` stays absent: ``AudioToken.to_audio`` is its form here.
+``to_acoustic`` keeps the first ``max_source_tokens`` ids of a source, as the reference does; ``to_acoustic_long`` walks a whole source in windows that carry the
+acoustic ids of their overlap (``acoustic_windows``).
 
 Stated deviations from the reference: the draws come from a caller-visible uniform stream, not ``torch.multinomial``; a row whose length
 reaches the model's block finishes with ``"block_size"`` instead of having its context cropped; bias-free checkpoints only."""
@@ -29,6 +31,7 @@ class AcousticGeneration:
     codes: List[Optional[torch.Tensor]]     # int64 [2, n_b // 2], or None where ``coarse_codes`` refused the ids
     finish: List[str]                       # "stop" | "max_new_tokens" | "block_size"
     logits: Optional[List[torch.Tensor]] = None   # return_logits: float32 [n_b (+ 1 when the row stopped), V], the logits each id was drawn from
+    windows: Optional[List[List[tuple]]] = None   # the long form: per row (source_start, source_len, carry, new_ids) of every window
 
 
 def coarse_codes(ids, codebook_size: int = 1024, num_codebooks: int = 2) -> torch.Tensor:
@@ -46,9 +49,8 @@ def coarse_codes(ids, codebook_size: int = 1024, num_codebooks: int = 2) -> torc
     return pairs.t().contiguous()
 
 
-def prepare_source(tokens, config: HubertDecoderConfig) -> np.ndarray:
-    """The prompt of one source, as the reference's ``_prepare_source`` builds it: ids + the semantic offset, flattened, truncated to
-    ``max_source_tokens``, the INFER token appended."""
+def source_ids(tokens, config: HubertDecoderConfig) -> torch.Tensor:
+    """One source as flat int64 semantic ids: a tensor / array / path, any shape. Empty sources and ids outside the semantic vocabulary raise."""
     if isinstance(tokens, (str, os.PathLike, Path)):
         p = str(tokens)
         tokens = np.load(p) if p.endswith(".npy") else torch.load(p, map_location="cpu")
@@ -57,8 +59,50 @@ def prepare_source(tokens, config: HubertDecoderConfig) -> np.ndarray:
         raise ValueError("to_acoustic: an empty source")
     if int(t.min()) < 0 or int(t.max()) >= config.SEMANTIC_VOCAB_SIZE:
         raise ValueError(f"to_acoustic: semantic ids must lie in [0, {config.SEMANTIC_VOCAB_SIZE})")
-    t = (t + config.SEMANTIC_OFFSET)[:config.max_source_tokens]
+    return t
+
+
+def prepare_source(tokens, config: HubertDecoderConfig) -> np.ndarray:
+    """The prompt of one source, as the reference's ``_prepare_source`` builds it: ids + the semantic offset, flattened, truncated to
+    ``max_source_tokens``, the INFER token appended."""
+    t = (source_ids(tokens, config) + config.SEMANTIC_OFFSET)[:config.max_source_tokens]
     return np.concatenate([t.numpy(), [config.INFER_TOKEN]]).astype(np.int32)
+
+
+MAX_SOURCE_IDS = 65536   # of one row of the long form (csrc/gpt.h: GPT_MAX_SOURCE)
+
+
+def check_windows(S: int, H: int, r: int, block: int) -> None:
+    """The long form's conditions on window ``S``, hop ``H`` and ``r`` acoustic ids per source id at a model of ``block`` positions."""
+    if S < 2 or H < 2 or S % 2 or H % 2:
+        raise ValueError(f"long form: the window ({S}) and the hop ({H}) must be even, at least 2")
+    if H > S:
+        raise ValueError(f"long form: the hop ({H}) must not exceed the window ({S})")
+    if r < 1 or S + 1 + r * S > block:
+        raise ValueError(f"long form: a window of {S} source ids needs {S} + 1 + {r} * {S} positions, the model has {block}")
+
+
+def default_window(config: HubertDecoderConfig, block: int):
+    """``(S, H)``: the largest even window that fits the source limit and the block with its ``r S`` new ids, and the largest even hop up to half of it."""
+    r = config.ids_per_source_token
+    S = min(config.max_source_tokens, (block - 1) // (r + 1)) // 2 * 2
+    return S, (S // 2) // 2 * 2
+
+
+def acoustic_windows(N: int, S: int, H: int, r: int = 3, block: int = 1024):
+    """The long form's schedule for a source of ``N`` ids (csrc/gpt.h has the same arithmetic): a list of
+    ``(source_start, source_len, carry, new_ids)``, one per window. Window k reads source ids ``[k H, k H + source_len)``, is prompted with the ``carry``
+    stream ids ``[r k H, r k H + carry)`` the window before produced, and produces exactly ``new_ids`` ids from stream position ``r k H + carry`` on;
+    ``new_ids`` of the last window is None: it runs until STOP or its budget."""
+    check_windows(S, H, r, block)
+    if N < 1 or N > MAX_SOURCE_IDS:
+        raise ValueError(f"long form: a source has 1 to {MAX_SOURCE_IDS} ids, got {N}")
+    n = 1 if N <= S else -(-(N - S) // H) + 1
+    out = []
+    for k in range(n):
+        carry = r * (S - H) if k else 0
+        out.append((k * H, min(S, N - k * H), carry, None if k == n - 1 else r * S - carry))
+    return out
 
 
 def seeded_uniforms(seed: int, batch: int, max_new_tokens: int) -> np.ndarray:
@@ -152,6 +196,10 @@ class SemanticToAcoustic(LibHandle):
             a, n = cfg.ACOUSTIC_OFFSET, cfg.codebook_size
             allow = [[a, a + n, cfg.STOP_TOKEN, cfg.STOP_TOKEN + 1], [a + n, a + 2 * n, 0, 0]]
         ids, finish, logits = self.generate(prompts, max_new_tokens, temperature, top_k, cfg.STOP_TOKEN, uniforms, seed, allow, return_logits)
+        return self._generation(ids, finish, logits)
+
+    def _generation(self, ids, finish, logits, windows=None) -> AcousticGeneration:
+        cfg = self.config
         ids = [i - cfg.ACOUSTIC_OFFSET for i in ids]
         codes: List[Optional[torch.Tensor]] = []
         for i in ids:
@@ -159,7 +207,77 @@ class SemanticToAcoustic(LibHandle):
                 codes.append(coarse_codes(i, cfg.codebook_size, cfg.num_codebooks))
             except ValueError:
                 codes.append(None)
-        return AcousticGeneration(ids=ids, codes=codes, finish=finish, logits=logits)
+        return AcousticGeneration(ids=ids, codes=codes, finish=finish, logits=logits, windows=windows)
+
+    def to_acoustic_long(self, tokens, window: Optional[int] = None, hop: Optional[int] = None, max_new_tokens: int = 1024, temperature: float = 0.8,
+                         top_k: int = 100, seed: int = 0, uniforms: Optional[np.ndarray] = None, return_logits: bool = False) -> AcousticGeneration:
+        """``to_acoustic(constrain=True)`` for sources of any length up to 65536 ids: the source is walked in windows of ``window`` ids every
+        ``hop`` ids (defaults: ``default_window``), each window prompted with the acoustic ids the window before produced for their overlap, all windows of up
+        to 64 sources enqueued by one library call. Every window but a source's last produces exactly ``ids_per_source_token`` ids per source id and cannot
+        stop; the last ends as ``to_acoustic`` does, within ``max_new_tokens``. ``uniforms``: float32 ``[B, L]``, the draw of a row's stream position (one per
+        id of the result), ``L`` at least the longest row's capacity; from ``seed``: ``seeded_uniforms(seed, B, max(max_new_tokens, capacity))``. A source of
+        at most ``window`` ids gives what ``to_acoustic(constrain=True)`` gives. ``windows`` of the result is the schedule with the counts produced."""
+        cfg = self.config
+        r, block = int(cfg.ids_per_source_token), self.block_size
+        S = default_window(cfg, block)[0] if window is None else int(window)
+        H = (S // 2) // 2 * 2 if hop is None else int(hop)
+        batch = tokens if isinstance(tokens, (list, tuple)) else [tokens]
+        B = len(batch)
+        if not 1 <= B <= 64:
+            raise ValueError(f"to_acoustic: 1 to 64 sources per call, got {B}")
+        max_new = int(max_new_tokens)
+        if not 1 <= max_new <= 1024:
+            raise ValueError(f"to_acoustic: max_new_tokens must be 1 to 1024, got {max_new}")
+        srcs = [source_ids(t, cfg) for t in batch]
+        plans = [acoustic_windows(int(s.numel()), S, H, r, block) for s in srcs]   # refuses a bad window / hop / length before anything is launched
+        lens = [int(s.numel()) for s in srcs]
+        base, cap, longest = [], 0, 0
+        for plan in plans:
+            k = len(plan) - 1
+            start, n_src, carry, _ = plan[-1]
+            P = n_src + 1 + carry
+            budget = min(max_new, block - P)
+            base.append(r * start + carry)
+            cap = max(cap, base[-1] + budget)
+            longest = max(longest, P + budget, S + 1 + r * S if k else 0)
+        if uniforms is None:
+            uniforms = seeded_uniforms(seed, B, max(max_new, cap))
+        uniforms = np.ascontiguousarray(uniforms, dtype=np.float32)
+        if uniforms.ndim != 2 or uniforms.shape[0] != B or uniforms.shape[1] < cap:
+            raise ValueError(f"uniforms must be float32 [{B}, L] with L >= {cap} (one draw per row and stream position), got {uniforms.shape}")
+        stride = max(lens)
+        host = np.zeros((B, stride), dtype=np.int32)
+        for b, s in enumerate(srcs):
+            host[b, :lens[b]] = s.numpy()
+        dev = self.device
+        with torch.cuda.device(dev):
+            d_src = torch.from_numpy(host).to(dev)
+            d_u = torch.from_numpy(uniforms).to(dev)
+            d_ids = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
+            d_len = torch.zeros(B, dtype=torch.int32, device=dev)
+            d_fin = torch.zeros(B, dtype=torch.int32, device=dev)
+            d_logits = torch.empty((B, cap, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
+            nbytes = int(self._fn("long_state_bytes")(self.handle, B, longest))
+            state = self._workspace(max(nbytes, 256))
+            self._status.zero_()
+            c_lens = (C.c_int32 * B)(*lens)
+            _cabi.check(self._fn("generate_long")(self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE,
+                                                  cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET, cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature),
+                                                  int(top_k), d_u.data_ptr(), uniforms.shape[1], d_ids.data_ptr(), cap, d_len.data_ptr(), d_fin.data_ptr(),
+                                                  _cabi.ptr(d_logits), state.data_ptr(), state.numel(), longest, _cabi.current_stream_handle(dev),
+                                                  self._status.data_ptr()), "at_gpt_generate_long")
+            n = d_len.cpu().tolist()    # synchronises
+            fin = d_fin.cpu().tolist()
+            ids_all = d_ids.cpu().to(torch.int64)
+        if self.last_status() & 1:
+            raise ValueError("at_gpt_generate_long: a source id lies outside the semantic vocabulary")
+        self.last_raw_ids = ids_all   # the whole [B, capacity] buffer, -1 where nothing was written (tests)
+        ids = [ids_all[b, :n[b]].clone() for b in range(B)]
+        logits = None
+        if d_logits is not None:
+            logits = [d_logits[b, :min(cap, n[b] + (1 if fin[b] == 1 else 0))].cpu() for b in range(B)]
+        windows = [plan[:-1] + [plan[-1][:3] + (n[b] - base[b],)] for b, plan in enumerate(plans)]
+        return self._generation(ids, [FINISH[f] for f in fin], logits, windows)
 
 
 def topk_sample(logits: torch.Tensor, temperature: float, top_k: int, uniforms: torch.Tensor, allow=None) -> torch.Tensor:

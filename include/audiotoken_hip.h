@@ -661,6 +661,25 @@ size_t at_gpt_state_bytes(const at_gpt_t* h, int B, int max_len);
 int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, const int32_t* prompt_len, int B, int max_new, float temperature, int top_k,
                     int stop_token, const float* uniforms_dev, const int32_t* allow, int32_t* out_ids_dev, int32_t* out_len_dev, int32_t* finish_dev,
                     float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev);
+/* The long form: sources longer than one prompt, generated window by window with the row's own output carried over, every window of
+ * every row enqueued by one call and nothing copied to the host in between. Windows of a source of N ids (1 to 65536) at window S and hop H (both even,
+ * 2 <= H <= S, S + 1 + r S <= block): n = 1 if N <= S, else ceil((N - S) / H) + 1 (at_gpt_long_num_windows; 0 = error). Window k reads source ids
+ * [k H, k H + min(S, N - k H)); its prompt is those ids + semantic_offset, infer_token, then the row's stream positions [r k H, r k H + carry) with carry = 0
+ * for k = 0 and r (S - H) after. A non-final window produces exactly r S - carry ids, step s from [acoustic_offset + (s % 2) codebook_size, ... +
+ * codebook_size), and cannot stop. The final window also allows stop_token (negative = none) on even steps, has min(max_new, block - prompt) steps and
+ * sets finish_dev[b] as at_gpt_generate does. Pass k of the call runs window k of every row that has one as one batch: one launch that writes the prompts,
+ * the prefill, then the steps. The id, the draw and the logits of a step live at the row's STREAM position: out_ids_dev int32 [B][out_stride],
+ * uniforms_dev float32 [B][u_stride], logits_out_dev NULL or float32 [B][out_stride][V]; both strides >= the final window's first position + its
+ * steps, for every row. src_dev: device int32 [B][src_stride] raw semantic ids, src_len a HOST array. out_len_dev[b] = ids of the row's stream.
+ * state_dev: at_gpt_long_state_bytes(h, B, max_len) bytes, max_len >= the longest window's prompt + steps (S + 1 + r S covers every non-final one) and
+ * <= block. status_dev bit 0 = a source id outside [0, semantic_vocab) was clamped. For N <= S the result is at_gpt_generate's on the same prompt with
+ * the same rules. Every argument and the whole schedule are checked before the device is touched. Not re-entrant per handle. */
+int at_gpt_long_num_windows(int N, int S, int H);
+size_t at_gpt_long_state_bytes(const at_gpt_t* h, int B, int max_len);
+int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, int S, int H, int r, int semantic_offset,
+                         int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                         const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
+                         float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev);
 /* The sampling step alone, one workgroup per row, no float atomics (the same call twice gives the same ids). logits_dev device float32 [B][V], V <= 65536;
  * uniforms_dev device float32 [B]; allow NULL or a HOST array int32 [4] = two half-open id ranges; out_dev device int32 [B]. The rule:
  * 1. zt_i = z_i / temperature (one IEEE fp32 division). 2. ids outside the allow ranges become -inf. 3. v = the min(top_k, V)-th largest zt; every id
