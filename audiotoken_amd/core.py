@@ -318,7 +318,8 @@ class AudioToken:
         return km
 
     def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0, uniforms=None,
-                    constrain: bool = False, return_logits: bool = False, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None):
+                    constrain: bool = False, return_logits: bool = False, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None,
+                    slots: Optional[int] = None, tick_tokens: Optional[int] = None):
         """Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoder (its GPT, ``decoder.py:210-239``) on the
         KV-cached HIP decoder (semantic_decoder.py). Semantic tokenizers only. ``tokens``: a tensor / array / path of semantic ids (any
         shape, flattened), or a list of up to 64 of them, generated as one batch. Returns an ``AcousticGeneration``: ``codes`` (a list of int64
@@ -330,11 +331,15 @@ class AudioToken:
         ``decoder_weights=`` (a checkpoint path or a ``{name: array}`` dict), else the seeded synthetic model.
         Without ``long_form`` a source is cut to its first ``max_source_tokens`` ids (5 s), as the reference cuts it. ``long_form=True`` walks the whole
         source (up to 65536 ids) in windows of ``window`` ids every ``hop`` ids, carrying the acoustic ids of the overlap: always
-        constrained, ``uniforms`` indexed by the position in the row's result, ``windows`` of the result the schedule that ran."""
+        constrained, ``uniforms`` indexed by the position in the row's result, ``windows`` of the result the schedule that ran. With ``slots=`` (1 to 64) the
+        long form takes 1 to 4096 sources and runs them through that many cache rows, each source starting when a row is free and finishing on its own
+        (DESIGN.md §20); ``tick_tokens`` bounds the tokens of one model pass. A source's result does not depend on its neighbours."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_acoustic maps semantic ids to acoustic code books; {self.tokenizer_name} has no semantic ids")
         if not long_form and (window is not None or hop is not None):
             raise ValueError("to_acoustic: window= and hop= belong to long_form=True")
+        if not long_form and (slots is not None or tick_tokens is not None):
+            raise ValueError("to_acoustic: slots= and tick_tokens= belong to long_form=True")
         if getattr(self, "semantic_decoder", None) is None:
             from .configs import HubertDecoderConfig, Wav2VecBertDecoderConfig
             from .semantic_decoder import SemanticToAcoustic
@@ -345,7 +350,7 @@ class AudioToken:
             self.semantic_decoder = SemanticToAcoustic(cfg, device=self.device, weights=w)
         if long_form:
             return self.semantic_decoder.to_acoustic_long(tokens, window=window, hop=hop, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
-                                                          seed=seed, uniforms=uniforms, return_logits=return_logits)
+                                                          seed=seed, uniforms=uniforms, return_logits=return_logits, slots=slots, tick_tokens=tick_tokens)
         return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
                                                  constrain=constrain, return_logits=return_logits)
 
@@ -359,6 +364,9 @@ class AudioToken:
         ``fine_weights=`` (a checkpoint path or a ``{name: array}`` dict), else ``$AUDIOTOKEN_FINE_DECODER_WEIGHTS``, else the seeded synthetic model."""
         from .fine_decoder import _as_rows
         rows = _as_rows(codes)   # a malformed input is refused before any model is built
+        return self._fine().generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
+
+    def _fine(self):
         if getattr(self, "fine_decoder", None) is None:
             from .configs import FineDecoderConfig
             from .fine_decoder import CoarseToFine
@@ -367,28 +375,53 @@ class AudioToken:
             if w is None and cfg.weights is None:
                 logger.warning("to_fine: no fine_weights given; using the seeded synthetic fine model")
             self.fine_decoder = CoarseToFine(cfg, device=self.device, weights=w)
-        return self.fine_decoder.generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
+        return self.fine_decoder
 
     def to_audio(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, fine_temperature: Optional[float] = 0.5,
-                 seed: int = 0, uniforms=None, fine_uniforms=None, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None):
+                 seed: int = 0, uniforms=None, fine_uniforms=None, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None,
+                 slots: Optional[int] = None, tick_tokens: Optional[int] = None):
         """Semantic ids -> audio, this project's form of the reference's semantic ``decode`` (``decoder.py:210-243``): ``to_acoustic(constrain=True)``, then
         ``to_fine``, then the acoustic decoder at 8 code books (bandwidth 6). Semantic tokenizers only. ``tokens`` as ``to_acoustic`` takes them. Returns
         ``(audio, coarse, fine)``: a list of one float32 ``(1, 320 * T_b)`` CPU tensor per source, the ``AcousticGeneration`` and the ``FineGeneration``.
         ``uniforms`` / ``fine_uniforms`` / ``seed`` are the two stages' draws. A source whose stage 1 produced no whole frame raises ``ValueError``.
         ``long_form=True`` (with ``window`` / ``hop``) makes stage 1 the long form of ``to_acoustic``, so that the audio covers the whole source and not its
-        first 5 s; the two later stages take any length as they are."""
+        first 5 s; the two later stages take any length as they are. With ``slots=`` stage 1 is the generation queue and takes up to 4096 sources; ``to_fine``
+        then runs in groups of at most 64 in source order (``fine_uniforms``: ``[B, n_max, 6, W]`` over all sources, each group taking its rows and the windows
+        its longest member needs), and the returned ``FineGeneration`` holds every source's codes."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_audio maps semantic ids to audio; {self.tokenizer_name} has no semantic ids (its own decode is the way back)")
         coarse = self.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms, constrain=True,
-                                  long_form=long_form, window=window, hop=hop)
+                                  long_form=long_form, window=window, hop=hop, slots=slots, tick_tokens=tick_tokens)
         for b, c in enumerate(coarse.codes):
             if c is None or c.shape[1] < 1:
                 raise ValueError(f"to_audio: source {b} produced no whole frame of coarse codes (finish: {coarse.finish[b]})")
-        fine = self.to_fine(coarse.codes, temperature=fine_temperature, seed=seed, uniforms=fine_uniforms)
+        if len(coarse.codes) <= 64:
+            fine = self.to_fine(coarse.codes, temperature=fine_temperature, seed=seed, uniforms=fine_uniforms)
+        else:
+            fine = self._to_fine_in_groups(coarse.codes, fine_temperature, seed, fine_uniforms)
         if getattr(self, "fine_audio", None) is None:
             self.fine_audio = AudioToken(Tokenizers.acoustic, device=self.device, num_codebooks=8, weights=self.kwargs.get("acoustic_weights"))
         audio = [self.fine_audio.decode(c.unsqueeze(0)) for c in fine.codes]
         return audio, coarse, fine
+
+    def _to_fine_in_groups(self, codes, temperature, seed, uniforms, group: int = 64):
+        """``to_fine`` over more than 64 rows: groups of at most ``group`` in order, one ``FineGeneration`` over all of them. A group's draws are its rows of
+        ``uniforms`` cut to the windows its longest member has; from ``seed`` each group draws its own stream, seeded ``seed + its index``."""
+        from .fine_decoder import fine_windows
+        W = self._fine().block_size
+        out = None
+        for g, at in enumerate(range(0, len(codes), group)):
+            rows = codes[at:at + group]
+            u = None
+            if uniforms is not None:
+                n_max = max(len(fine_windows(int(c.shape[1]), W)) for c in rows)
+                u = np.ascontiguousarray(np.asarray(uniforms)[at:at + group, :n_max])
+            part = self.to_fine(rows, temperature=temperature, seed=seed + g, uniforms=u)
+            if out is None:
+                out = part
+            else:
+                out.codes.extend(part.codes)
+        return out
 
     def load_decoder(self, **kwargs):
         """core.py:291-315. Built: the acoustic decoder. The semantic way back is built under its own names: ``to_acoustic`` (stage 1, semantic ids -> the

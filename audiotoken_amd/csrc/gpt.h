@@ -21,6 +21,123 @@ constexpr int GPT_MAX_SOURCE = 65536;  // source ids of one row of at_gpt_genera
 // The long form's schedule: windows of a source of N ids at window S and hop H; window k reads source ids [k H, k H + min(S, N - k H)).
 inline int gpt_long_windows(int N, int S, int H) { return N <= S ? 1 : (N - S + H - 1) / H + 1; }
 
+// ---- the generation queue's scheduler: pure host code, shared by at_gpt_generate_queue and tools/gpt_queue_args.hip ------------------------
+// Sources run 19's windows through `slots` cache rows. A tick is one model pass over one token list: one step token of every slot that is mid-window, then
+// the whole prompt of every window admitted this tick. Everything about the schedule is known from the lengths except when a final window ends; that
+// comes from the rows' flags, looked at every GPT_CHECK_EVERY ticks while some slot is in a final window.
+constexpr int GPT_MAX_QUEUE = 4096;                                   // sources of one at_gpt_generate_queue call
+constexpr int GPT_MAX_TICK_TOKENS = GPT_MAX_B * (GPT_MAX_BLOCK + 1);  // more than every slot prefilling at once cannot be used
+constexpr int GPT_GEMM_ABOVE = GPT_MAX_B;                             // a pass of more tokens takes the fp32 GEMM route (run_layers)
+
+struct GptQueueStart {
+    int slot, src, k, final_window, n_ids, P;   // window k of source src begins in slot: n_ids source ids, P prompt tokens
+};
+struct GptQueueTick {
+    int n_step = 0, n_start = 0, prefill_tokens = 0;
+    int step_slot[GPT_MAX_B];
+    GptQueueStart start[GPT_MAX_B];
+    bool poll = false;   // the caller must hand the rows' flags to seen() before the next tick
+    int tokens() const { return n_step + prefill_tokens; }
+    int route() const { return tokens() > GPT_GEMM_ABOVE ? 1 : 0; }
+};
+
+class GptQueueSchedule {
+  public:
+    // src_len must outlive the schedule; every argument has been validated by the caller (tick_tokens >= slots + the longest prompt)
+    GptQueueSchedule(const int32_t* src_len, int n_src, int S, int H, int r, int max_new, int block, int slots, int tick_tokens)
+        : len_(src_len), n_src_(n_src), S_(S), H_(H), r_(r), max_new_(max_new), block_(block), slots_(slots), tick_tokens_(tick_tokens),
+          placement_((size_t)n_src * 3, -1) {
+        for (int j = 0; j < GPT_MAX_B; ++j) slot_[j] = Slot{};
+    }
+    // window k of a source of N ids: its source ids, prompt tokens and steps (a final window's: at most)
+    void window(int N, int k, int* n_ids, int* P, int* budget, bool* final_window) const {
+        const int n = gpt_long_windows(N, S_, H_), carry = k > 0 ? r_ * (S_ - H_) : 0;
+        *final_window = k == n - 1;
+        *n_ids = *final_window ? N - k * H_ : S_;
+        *P = *n_ids + 1 + carry;
+        *budget = *final_window ? (max_new_ < block_ - *P ? max_new_ : block_ - *P) : r_ * S_ - carry;
+    }
+    // The next tick, or false when every source has been retired. Waiting sources take empty slots in source order; every running slot steps; windows are
+    // admitted in slot order while the list stays within tick_tokens (the first always fits, so no tick is empty and no slot starves).
+    bool next(GptQueueTick* t) {
+        *t = GptQueueTick{};
+        tick_ = n_ticks_;
+        bool any = false;
+        for (int j = 0; j < slots_; ++j) {
+            Slot& s = slot_[j];
+            if (s.src < 0 && next_src_ < n_src_) {
+                s = Slot{};
+                s.src = next_src_++;
+                placement_[3 * (size_t)s.src] = j;
+            }
+            any = any || s.src >= 0;
+        }
+        if (!any) return false;
+        for (int j = 0; j < slots_; ++j)
+            if (slot_[j].src >= 0 && slot_[j].running) t->step_slot[t->n_step++] = j;
+        for (int j = 0; j < slots_; ++j) {
+            Slot& s = slot_[j];
+            if (s.src < 0 || s.running) continue;
+            int n_ids, P, budget;
+            bool fin;
+            window(len_[s.src], s.k, &n_ids, &P, &budget, &fin);
+            if (t->tokens() + P > tick_tokens_) break;   // it waits, and so does every slot after it
+            t->start[t->n_start++] = GptQueueStart{j, s.src, s.k, fin ? 1 : 0, n_ids, P};
+            t->prefill_tokens += P;
+            s.running = true;
+            s.final_window = fin;
+            s.budget = budget;
+            s.t = 0;
+            if (s.k == 0) placement_[3 * (size_t)s.src + 1] = tick_;
+        }
+        // the state after this tick's sampler launch, as far as the host knows it
+        bool in_final = false;
+        auto sampled = [&](int j) {
+            Slot& s = slot_[j];
+            if (++s.t < s.budget) { in_final = in_final || s.final_window; return; }
+            if (s.final_window) { retire(j); return; }   // out of budget: finished whatever it drew
+            ++s.k;
+            s.running = false;
+        };
+        for (int i = 0; i < t->n_step; ++i) sampled(t->step_slot[i]);
+        for (int i = 0; i < t->n_start; ++i) sampled(t->start[i].slot);
+        ++n_ticks_;
+        t->poll = in_final && n_ticks_ % GPT_CHECK_EVERY == 0;
+        return true;
+    }
+    // after a tick with poll set: done[j] of every slot as the device has it now
+    void seen(const int32_t* done) {
+        for (int j = 0; j < slots_; ++j)
+            if (slot_[j].src >= 0 && slot_[j].running && slot_[j].final_window && done[j] != GPT_RUNNING) retire(j);
+    }
+    // the dry run's stand-in for the device: the flag of a slot whose final window ends after final_steps[src] sampler launches
+    void seen_by_steps(const int32_t* final_steps) {
+        int32_t done[GPT_MAX_B];
+        for (int j = 0; j < slots_; ++j) {
+            const Slot& s = slot_[j];
+            done[j] = s.src >= 0 && s.running && s.final_window && s.t >= final_steps[s.src] ? GPT_FINISH_STOP : GPT_RUNNING;
+        }
+        seen(done);
+    }
+    int ticks() const { return n_ticks_; }
+    const std::vector<int32_t>& placement() const { return placement_; }   // [n_src][3]: slot, first tick, last tick seen
+
+  private:
+    struct Slot {
+        int src = -1, k = 0, t = 0, budget = 0;
+        bool running = false, final_window = false;
+    };
+    void retire(int j) {
+        placement_[3 * (size_t)slot_[j].src + 2] = tick_;
+        slot_[j] = Slot{};
+    }
+    const int32_t* len_;
+    int n_src_, S_, H_, r_, max_new_, block_, slots_, tick_tokens_;
+    int next_src_ = 0, n_ticks_ = 0, tick_ = 0;   // tick_: the index of the tick next() made last
+    Slot slot_[GPT_MAX_B];
+    std::vector<int32_t> placement_;
+};
+
 struct GptHostTensor {
     std::vector<int64_t> shape;
     std::vector<float> data;

@@ -9,6 +9,8 @@
 //   gpt_attn_kernel     causal attention of one query over its row's cache, one workgroup of 4 waves per (token, head)
 //   gpt_sample_kernel   temperature, allow ranges, exact top-k threshold (radix select), softmax weights and the inverse-CDF draw, one workgroup per row
 //   gpt_window_kernel   the long form: the prompts of one window of every row, from the source ids and the row's own output stream
+//   gpt_tick_kernel     the queue: one tick's token list, step tokens of the rows that are mid-window and the prompts of the windows that begin,
+//                       with gpt_embed_list_kernel, the embedding that reads it
 // Nothing here adds floats atomically: every sum has one order, so a call repeated gives the same tokens.
 #include <cmath>
 #include <cstring>
@@ -132,6 +134,22 @@ __global__ __launch_bounds__(E / 4) void gpt_embed_kernel(const int* prompts, in
         id = cur[b];
         if (t == 0) { tok_row[i] = b; tok_pos[i] = p; last_row[b] = b; }
     }
+    if (id < 0 || id >= V) {
+        if (t == 0 && status) atomicOr(status, 1);
+        id = min(max(id, 0), V - 1);
+    }
+    const float4 a = reinterpret_cast<const float4*>(wte + (size_t)id * E)[t];
+    const float4 c = reinterpret_cast<const float4*>(wpe + (size_t)p * E)[t];
+    reinterpret_cast<float4*>(x + (size_t)i * E)[t] = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
+}
+
+// The queue's form: token i of a list that gpt_tick_kernel resolved, prompt tokens and step tokens alike: x[i] = wte[tok_id[i]] + wpe[tok_pos[i]].
+// The list's ids are the model's own (sampled, or clamped when the prompt was written); the clamp here only keeps a corrupted list inside the tables.
+__global__ __launch_bounds__(E / 4) void gpt_embed_list_kernel(const int* tok_id, const int* tok_pos, const float* wte, const float* wpe, int V, int block, float* x,
+                                                                int* status) {
+    const int i = blockIdx.x, t = threadIdx.x;
+    int id = tok_id[i];
+    const int p = min(max(tok_pos[i], 0), block - 1);
     if (id < 0 || id >= V) {
         if (t == 0 && status) atomicOr(status, 1);
         id = min(max(id, 0), V - 1);
@@ -368,6 +386,9 @@ struct SampleArgs {
     int max_new, stop_token, block;
     int out_stride;           // ids of one row of out_ids (at_gpt_generate: max_new)
     const SampleRow* rows;    // nullable [B]: the long form's per-row rules; nullptr: the call's own scalars
+    // the queue (at_gpt_generate_queue; needs rows): workgroup j samples for cache row samp_slot[j] from logits row j, at that row's own step
+    int* step_ctr;            // nullable [slots]: steps sampled in the row's window so far; replaces `step`
+    const int* samp_slot;     // [gridDim.x]
 };
 
 // floats as unsigned keys in the same order
@@ -388,16 +409,20 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     __shared__ unsigned sel_prefix, sel_k;
     __shared__ float wave_part[SAMPLE_THREADS / 64];
     __shared__ int best_id, high_id;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool queued = a.rows && a.step_ctr;
+    const int b = queued ? a.samp_slot[blockIdx.x] : blockIdx.x;
     const bool generating = a.out == nullptr;
     if (generating && a.done[b] != GPT_RUNNING) return;   // a finished row writes nothing more (uniform over the workgroup)
     const int V = a.V;
-    const float* z = a.logits + (size_t)b * V;
-    // where the step's id, draw and logits live: row b at a.step, or the long form's row and stream position
+    const float* z = a.logits + (size_t)blockIdx.x * V;
+    // where the step's id, draw and logits live: row b at a.step, or the long form's row and stream position; the queue's rows count their own steps
+    // (every thread reads the counter here, thread 0 advances it after the last barrier)
+    const int step = queued ? a.step_ctr[b] : a.step;
     const SampleRow* pr = a.rows ? a.rows + b : nullptr;
-    if (pr && a.step >= pr->budget) return;
-    const int orow = pr ? pr->out_row : b, pos = (pr ? pr->base : 0) + a.step;
-    const Allow allow = pr ? pr->allow[a.step & 1] : a.allow;
+    if (pr && step >= pr->budget) return;
+    const int orow = pr ? pr->out_row : b, pos = (pr ? pr->base : 0) + step;
+    const Allow allow = pr ? pr->allow[step & 1] : a.allow;
     if (generating && a.logits_out) {
         float* dst = a.logits_out + ((size_t)orow * a.out_stride + pos) * V;
         for (int i = tid; i < V; i += SAMPLE_THREADS) dst[i] = z[i];
@@ -480,6 +505,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     const int tok = best_id < V ? best_id : max(high_id, 0);
     if (!generating) { a.out[b] = tok; return; }
     // ---- the row's bookkeeping: stop, max_new_tokens, block_size in that order
+    if (queued) a.step_ctr[b] = step + 1;
     if (tok == (pr ? pr->stop_token : a.stop_token)) {
         a.done[b] = a.finish[orow] = GPT_FINISH_STOP;
         return;
@@ -490,10 +516,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     const int total = a.len[b] + 1;
     a.len[b] = total;
     if (pr && !pr->final_window) {   // the window's count is exact; the row is done for this pass, not for the call
-        if (a.step + 1 >= pr->budget) a.done[b] = GPT_PASS_DONE;
+        if (step + 1 >= pr->budget) a.done[b] = GPT_PASS_DONE;
         return;
     }
-    if (a.step + 1 >= a.max_new) a.done[b] = a.finish[orow] = GPT_FINISH_MAX_NEW;
+    if (step + 1 >= a.max_new) a.done[b] = a.finish[orow] = GPT_FINISH_MAX_NEW;
     else if (total >= a.block) a.done[b] = a.finish[orow] = GPT_FINISH_BLOCK;
 }
 
@@ -591,15 +617,148 @@ LongState carve_long_state(void* base, int B, int cap, int vocab, int n_layer) {
     return s;
 }
 
+// What at_gpt_generate_long and at_gpt_generate_queue share: the checks of the geometry, the token space and the sampling arguments, and the rules they make
+int check_long_rules(const at_gpt* h, int S, int H, int r, int src_stride, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset,
+                     int codebook_size, int stop_token, int max_new, float temperature, int top_k, LongRules* out) {
+    const int V = h->vocab, block = h->block;
+    AT_REQUIRE(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0, "the window S and the hop H must be even, at least 2");
+    AT_REQUIRE(H <= S, "the hop H must not exceed the window S");
+    AT_REQUIRE(r >= 1 && r <= GPT_MAX_BLOCK, "r (acoustic ids per source id) must be 1 to 1024");
+    AT_REQUIRE((int64_t)S + 1 + (int64_t)r * S <= block, "a window does not fit: S + 1 + r S must not exceed the model's block size");
+    AT_REQUIRE(src_stride >= 1, "src_stride must be at least 1");
+    AT_REQUIRE(max_new >= 1 && max_new <= GPT_MAX_BLOCK, "max_new must be 1 to 1024");
+    if (int rc = check_sampling(temperature, top_k)) return rc;
+    AT_REQUIRE(semantic_offset >= 0 && semantic_vocab >= 1 && (int64_t)semantic_offset + semantic_vocab <= V, "the semantic ids must lie inside the vocabulary");
+    AT_REQUIRE(infer_token >= 0 && infer_token < V, "infer_token is not in the vocabulary");
+    AT_REQUIRE(acoustic_offset >= 0 && codebook_size >= 1 && (int64_t)acoustic_offset + 2 * (int64_t)codebook_size <= V,
+               "the two code books must lie inside the vocabulary");
+    AT_REQUIRE(stop_token < V, "stop_token is not in the vocabulary (negative: none)");
+    LongRules q{};
+    q.S = S; q.H = H; q.r = r; q.semantic_offset = semantic_offset; q.semantic_vocab = semantic_vocab; q.infer_token = infer_token;
+    q.stop_token = stop_token < 0 ? -1 : stop_token; q.max_new = max_new; q.block = block;
+    q.mid[0] = Allow{1, acoustic_offset, acoustic_offset + codebook_size, 0, 0};
+    q.mid[1] = Allow{1, acoustic_offset + codebook_size, acoustic_offset + 2 * codebook_size, 0, 0};
+    q.last[0] = q.mid[0];
+    q.last[1] = q.mid[1];
+    if (stop_token >= 0) { q.last[0].lo1 = stop_token; q.last[0].hi1 = stop_token + 1; }
+    *out = q;
+    return 0;
+}
+
+// ---- the queue: one tick of any mix of windows that begin and rows that step -----------------------------------------------------
+struct TickPlan {
+    int n_step, n_start, R;               // the list: n_step step tokens, then the prompts; R tokens in all
+    int off[GPT_MAX_B + 1];               // start j's prompt tokens are the list's [off[j], off[j + 1])
+    int src[GPT_MAX_B], k[GPT_MAX_B];     // start j: window k[j] of source src[j]
+    unsigned char slot[GPT_MAX_B];        //          in cache row slot[j]
+    unsigned char step_slot[GPT_MAX_B];   // the cache row of step token i
+    unsigned long long final_mask;        // bit j: start j is its source's last window
+};
+
+// Start of a tick: the resolved token list (row, position, id of every token), the sampling list (which token's logits each sampling row draws from and
+// whose cache row that is) and, for every window that begins, what gpt_window_kernel writes for a row of a pass, plus its zeroed step counter. A step
+// token is its row's last sampled id at position len - 1; the samplers before this launch wrote both, and the carry ids in out_ids, in stream order.
+// A slot either steps or begins in a tick, never both, so no word is read and written here. A source id outside [0, semantic_vocab) is clamped and reported.
+__global__ void gpt_tick_kernel(TickPlan p, LongRules q, const int* src, int src_stride, const int* out_ids, int out_stride, int* len, int* done, int* cur,
+                                int* step_ctr, int* last_row, int* samp_slot, int* tok_row, int* tok_pos, int* tok_id, SampleRow* rows, int* out_len,
+                                int* finish, int* status) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < p.n_step) {
+        const int slot = p.step_slot[i];
+        tok_row[i] = slot;
+        tok_pos[i] = min(max(len[slot] - 1, 0), q.block - 1);
+        tok_id[i] = cur[slot];
+        last_row[i] = i;
+        samp_slot[i] = slot;
+    } else if (i < p.R) {
+        int j = 0;
+        while (j + 1 < p.n_start && p.off[j + 1] <= i) ++j;
+        const int b = p.src[j], k = p.k[j], carry = k > 0 ? q.r * (q.S - q.H) : 0;
+        const int pos = i - p.off[j], n_src = p.off[j + 1] - p.off[j] - 1 - carry;
+        int id;
+        if (pos < n_src) {
+            id = src[(size_t)b * src_stride + k * q.H + pos];
+            if (id < 0 || id >= q.semantic_vocab) {
+                if (status) atomicOr(status, 1);
+                id = min(max(id, 0), q.semantic_vocab - 1);
+            }
+            id += q.semantic_offset;
+        } else if (pos == n_src) {
+            id = q.infer_token;
+        } else {
+            id = out_ids[(size_t)b * out_stride + q.r * k * q.H + (pos - n_src - 1)];
+        }
+        tok_row[i] = p.slot[j];
+        tok_pos[i] = pos;
+        tok_id[i] = id;
+    }
+    if (i < p.n_start) {
+        const int P = p.off[i + 1] - p.off[i], b = p.src[i], k = p.k[i], slot = p.slot[i], carry = k > 0 ? q.r * (q.S - q.H) : 0;
+        const bool last = (p.final_mask >> i) & 1ull;
+        len[slot] = P;
+        done[slot] = GPT_RUNNING;
+        cur[slot] = 0;
+        step_ctr[slot] = 0;
+        last_row[p.n_step + i] = p.off[i + 1] - 1;
+        samp_slot[p.n_step + i] = slot;
+        SampleRow s;
+        s.out_row = b;
+        s.base = q.r * k * q.H + carry;
+        s.budget = last ? min(q.max_new, q.block - P) : q.r * q.S - carry;
+        s.stop_token = last ? q.stop_token : -1;
+        s.final_window = last ? 1 : 0;
+        s.allow[0] = last ? q.last[0] : q.mid[0];
+        s.allow[1] = last ? q.last[1] : q.mid[1];
+        rows[slot] = s;
+        if (k == 0) { out_len[b] = 0; finish[b] = GPT_RUNNING; }
+    }
+}
+
+// K / V for `slots` rows of `cap` positions, activations for `T` token rows, nothing per source
+struct QueueState {
+    GptState g;
+    int *tok_id, *samp_slot, *step_ctr;
+    SampleRow* rows;   // [GPT_MAX_B], by slot
+    size_t bytes;
+};
+
+QueueState carve_queue_state(void* base, int slots, int cap, int T, int vocab, int n_layer) {
+    QueueState q{};
+    GptState& s = q.g;
+    char* p = static_cast<char*>(base);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += round256(bytes); return r; };
+    const size_t R = (size_t)T;
+    s.len = (int*)take(GPT_MAX_B * 4);
+    s.done = (int*)take(GPT_MAX_B * 4);
+    s.cur = (int*)take(GPT_MAX_B * 4);
+    s.last_row = (int*)take(GPT_MAX_B * 4);
+    q.samp_slot = (int*)take(GPT_MAX_B * 4);
+    q.step_ctr = (int*)take(GPT_MAX_B * 4);
+    q.rows = (SampleRow*)take(GPT_MAX_B * sizeof(SampleRow));
+    s.tok_row = (int*)take(R * 4);
+    s.tok_pos = (int*)take(R * 4);
+    q.tok_id = (int*)take(R * 4);
+    s.x = (float*)take(R * E * 4);
+    s.xn = (float*)take(R * E * 4);
+    s.q = (float*)take(R * 3 * E * 4);
+    s.h = (float*)take(R * FF * 4);
+    s.xh = (float*)take((size_t)GPT_MAX_B * E * 4);
+    s.logits = (float*)take((size_t)slots * vocab * 4);
+    s.layer_stride = (size_t)slots * cap * NH * HD;
+    s.kc = (float*)take(s.layer_stride * n_layer * 4);
+    s.vc = (float*)take(s.layer_stride * n_layer * 4);
+    s.bytes = q.bytes = off;
+    return q;
+}
+
 // ---- one pass of the model over R tokens: the prefill of every prompt (prompts != nullptr) or one step of every row (R = B) -----------------------------
-int run_pass(const at_gpt* h, const GptState& s, const int* prompts, int prompt_stride, int B, int R, int cap, int* status, hipStream_t stream) {
-    hipLaunchKernelGGL(gpt_embed_kernel, dim3(R), dim3(E / 4), 0, stream, prompts, prompt_stride, h->wte, h->wpe, h->vocab, h->block, s.len, s.cur, s.last_row,
-                       s.tok_row, s.tok_pos, s.x, status);
-    AT_CHECK_HIP(hipGetLastError());
+// The model over the R embedded tokens of s.x, each at (tok_row, tok_pos), then the head for the B tokens that s.last_row names: logits row j belongs to token last_row[j].
+int run_layers(const at_gpt* h, const GptState& s, int B, int R, int cap, hipStream_t stream) {
     const dim3 ln_grid((R + 3) / 4);
     // More rows than a step can have (a prefill of more than 64 tokens): the four linears on the fp32 matrix-core GEMM (gemm_f32.hip, an exact k-ordered fp32
     // chain). Otherwise the register-streaming kernel, in ceil(R / 16) passes.
-    const bool gemm = R > GPT_MAX_B;
+    const bool gemm = R > GPT_GEMM_ABOVE;
     auto dense = [&](const float* X, int K, const float* Wt, int N, float* C, const float* Res, int epi) {
         GemmArgs g;
         g.X = X; g.Tin = R; g.Cin = K; g.ldx = K; g.W = Wt; g.C = C; g.ldc = N; g.R = Res; g.ldr = N; g.M = R; g.N = N; g.K = K; g.epi = epi;
@@ -650,6 +809,13 @@ int run_pass(const at_gpt* h, const GptState& s, const int* prompts, int prompt_
     LinArgs o{};
     o.A = s.xh; o.W = h->wte; o.out = s.logits; o.R = B; o.N = h->vocab;
     return launch_linear<E, 192, LIN_NONE>(o, stream);
+}
+
+int run_pass(const at_gpt* h, const GptState& s, const int* prompts, int prompt_stride, int B, int R, int cap, int* status, hipStream_t stream) {
+    hipLaunchKernelGGL(gpt_embed_kernel, dim3(R), dim3(E / 4), 0, stream, prompts, prompt_stride, h->wte, h->wpe, h->vocab, h->block, s.len, s.cur, s.last_row,
+                       s.tok_row, s.tok_pos, s.x, status);
+    AT_CHECK_HIP(hipGetLastError());
+    return run_layers(h, s, B, R, cap, stream);
 }
 
 const GptHostTensor* staged(const at_gpt* h, const std::string& name) {
@@ -855,18 +1021,10 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
     AT_REQUIRE(src_dev && src_len && uniforms_dev && out_ids_dev && out_len_dev && finish_dev, "null pointer");
     AT_REQUIRE(state_dev != nullptr, "null state");
     const int V = h->vocab, block = h->block;
-    AT_REQUIRE(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0, "the window S and the hop H must be even, at least 2");
-    AT_REQUIRE(H <= S, "the hop H must not exceed the window S");
-    AT_REQUIRE(r >= 1 && r <= GPT_MAX_BLOCK, "r (acoustic ids per source id) must be 1 to 1024");
-    AT_REQUIRE((int64_t)S + 1 + (int64_t)r * S <= block, "a window does not fit: S + 1 + r S must not exceed the model's block size");
-    AT_REQUIRE(src_stride >= 1, "src_stride must be at least 1");
-    AT_REQUIRE(max_new >= 1 && max_new <= GPT_MAX_BLOCK, "max_new must be 1 to 1024");
-    if (int rc = check_sampling(temperature, top_k)) return rc;
-    AT_REQUIRE(semantic_offset >= 0 && semantic_vocab >= 1 && (int64_t)semantic_offset + semantic_vocab <= V, "the semantic ids must lie inside the vocabulary");
-    AT_REQUIRE(infer_token >= 0 && infer_token < V, "infer_token is not in the vocabulary");
-    AT_REQUIRE(acoustic_offset >= 0 && codebook_size >= 1 && (int64_t)acoustic_offset + 2 * (int64_t)codebook_size <= V,
-               "the two code books must lie inside the vocabulary");
-    AT_REQUIRE(stop_token < V, "stop_token is not in the vocabulary (negative: none)");
+    LongRules q{};
+    if (int rc = check_long_rules(h, S, H, r, src_stride, semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token, max_new,
+                                  temperature, top_k, &q))
+        return rc;
     // ---- the schedule: rows in descending order of their window counts, so that the rows of pass k are the first Bk of them
     int n_win[GPT_MAX_B], order[GPT_MAX_B];
     int n_max = 0, need_len = 0;
@@ -892,14 +1050,6 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
     }
     AT_REQUIRE(out_stride >= need_stride && u_stride >= need_stride, "out_stride and u_stride must hold the longest row's stream");
     AT_REQUIRE(max_len >= need_len && max_len <= block, "max_len must hold the longest window with its new ids and not exceed the block size");
-    LongRules q{};
-    q.S = S; q.H = H; q.r = r; q.semantic_offset = semantic_offset; q.semantic_vocab = semantic_vocab; q.infer_token = infer_token;
-    q.stop_token = stop_token < 0 ? -1 : stop_token; q.max_new = max_new; q.block = block;
-    q.mid[0] = Allow{1, acoustic_offset, acoustic_offset + codebook_size, 0, 0};
-    q.mid[1] = Allow{1, acoustic_offset + codebook_size, acoustic_offset + 2 * codebook_size, 0, 0};
-    q.last[0] = q.mid[0];
-    q.last[1] = q.mid[1];
-    if (stop_token >= 0) { q.last[0].lo1 = stop_token; q.last[0].hi1 = stop_token + 1; }
     const LongState ls = carve_long_state(state_dev, B, max_len, V, h->n_layer);
     const GptState& s = ls.g;
     AT_REQUIRE(state_bytes >= ls.bytes, "state too small: at_gpt_long_state_bytes(h, B, max_len)");
@@ -948,6 +1098,104 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
             }
         }
     }
+    return 0;
+}
+
+size_t at_gpt_queue_state_bytes(const at_gpt_t* h, int slots, int max_len, int tick_tokens) {
+    if (!(h && h->finalized)) { set_error("at_gpt_queue_state_bytes: the model is not finalized"); return 0; }
+    if (!(slots >= 1 && slots <= GPT_MAX_B)) { set_error("at_gpt_queue_state_bytes: slots must be 1 to 64"); return 0; }
+    if (!(max_len >= 1 && max_len <= h->block)) { set_error("at_gpt_queue_state_bytes: max_len must be 1 to the model's block size"); return 0; }
+    if (!(tick_tokens >= slots + max_len && tick_tokens <= GPT_MAX_TICK_TOKENS)) {
+        set_error("at_gpt_queue_state_bytes: tick_tokens must be slots + max_len to " + std::to_string(GPT_MAX_TICK_TOKENS));
+        return 0;
+    }
+    return carve_queue_state(nullptr, slots, max_len, tick_tokens, h->vocab, h->n_layer).bytes;
+}
+
+int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, int S, int H, int r, int semantic_offset,
+                          int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                          const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
+                          float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace, int trace_cap,
+                          int32_t* n_ticks, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized, "the model is not finalized");
+    AT_REQUIRE(n_src >= 1 && n_src <= GPT_MAX_QUEUE, "n_src must be 1 to 4096");
+    AT_REQUIRE(slots >= 1 && slots <= GPT_MAX_B, "slots must be 1 to 64");
+    AT_REQUIRE(src_dev && src_len && uniforms_dev && out_ids_dev && out_len_dev && finish_dev, "null pointer");
+    AT_REQUIRE(state_dev != nullptr, "null state");
+    AT_REQUIRE(trace_cap >= 0 && (trace != nullptr || trace_cap == 0), "trace_cap must be 0 without a trace and never negative");
+    const int V = h->vocab, block = h->block;
+    LongRules q{};
+    if (int rc = check_long_rules(h, S, H, r, src_stride, semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token, max_new,
+                                  temperature, top_k, &q))
+        return rc;
+    // ---- the schedule's extent: every source's stream and its longest window
+    const GptQueueSchedule geometry(src_len, n_src, S, H, r, max_new, block, slots, tick_tokens);
+    int need_len = 0;
+    int64_t need_stride = 0;
+    for (int i = 0; i < n_src; ++i) {
+        if (src_len[i] < 1 || src_len[i] > src_stride || src_len[i] > GPT_MAX_SOURCE) {
+            set_error("at_gpt_generate_queue: src_len of source " + std::to_string(i) + " must be 1 to min(src_stride, 65536)");
+            return -1;
+        }
+        const int n = gpt_long_windows(src_len[i], S, H);
+        int n_ids, P, budget;
+        bool fin;
+        geometry.window(src_len[i], n - 1, &n_ids, &P, &budget, &fin);
+        const int64_t end = (n > 1 ? (int64_t)r * (n - 1) * H + r * (S - H) : 0) + budget;
+        need_stride = end > need_stride ? end : need_stride;
+        need_len = P + budget > need_len ? P + budget : need_len;
+        if (n > 1 && S + 1 + r * S > need_len) need_len = S + 1 + r * S;
+    }
+    AT_REQUIRE(out_stride >= need_stride && u_stride >= need_stride, "out_stride and u_stride must hold the longest source's stream");
+    AT_REQUIRE(max_len >= need_len && max_len <= block, "max_len must hold the longest window with its new ids and not exceed the block size");
+    AT_REQUIRE(tick_tokens >= slots + max_len && tick_tokens <= GPT_MAX_TICK_TOKENS, "tick_tokens must be at least slots + max_len (one window always fits) and at most 65600");
+    const QueueState qs = carve_queue_state(state_dev, slots, max_len, tick_tokens, V, h->n_layer);
+    const GptState& s = qs.g;
+    AT_REQUIRE(state_bytes >= qs.bytes, "state too small: at_gpt_queue_state_bytes(h, slots, max_len, tick_tokens)");
+    // ---- nothing above touched the device
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    hipStream_t stream = (hipStream_t)stream_;
+    SampleArgs sa{};
+    sa.logits = s.logits; sa.V = V; sa.top_k = top_k; sa.temperature = temperature; sa.uniforms = uniforms_dev; sa.u_stride = u_stride;
+    sa.len = s.len; sa.done = s.done; sa.cur = s.cur; sa.out_ids = out_ids_dev; sa.out_len = out_len_dev; sa.finish = finish_dev;
+    sa.logits_out = logits_out_dev; sa.max_new = max_new; sa.stop_token = -1; sa.block = block; sa.out_stride = out_stride; sa.rows = qs.rows;
+    sa.step_ctr = qs.step_ctr; sa.samp_slot = qs.samp_slot;
+    GptQueueSchedule schedule(src_len, n_src, S, H, r, max_new, block, slots, tick_tokens);
+    GptQueueTick t;
+    while (schedule.next(&t)) {
+        TickPlan p{};
+        p.n_step = t.n_step; p.n_start = t.n_start; p.R = t.tokens();
+        for (int i = 0; i < t.n_step; ++i) p.step_slot[i] = (unsigned char)t.step_slot[i];
+        p.off[0] = t.n_step;
+        for (int j = 0; j < t.n_start; ++j) {
+            const GptQueueStart& w = t.start[j];
+            p.off[j + 1] = p.off[j] + w.P;
+            p.src[j] = w.src; p.k[j] = w.k; p.slot[j] = (unsigned char)w.slot;
+            if (w.final_window) p.final_mask |= 1ull << j;
+        }
+        const int ns = t.n_step + t.n_start;   // sampling rows: every slot with a token in the tick
+        hipLaunchKernelGGL(gpt_tick_kernel, dim3((p.R + 255) / 256), dim3(256), 0, stream, p, q, src_dev, src_stride, out_ids_dev, out_stride, s.len, s.done, s.cur,
+                           qs.step_ctr, s.last_row, qs.samp_slot, s.tok_row, s.tok_pos, qs.tok_id, qs.rows, out_len_dev, finish_dev, status_dev);
+        AT_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(gpt_embed_list_kernel, dim3(p.R), dim3(E / 4), 0, stream, qs.tok_id, s.tok_pos, h->wte, h->wpe, V, block, s.x, status_dev);
+        AT_CHECK_HIP(hipGetLastError());
+        if (int rc = run_layers(h, s, ns, p.R, max_len, stream)) return rc;
+        hipLaunchKernelGGL(gpt_sample_kernel, dim3(ns), dim3(SAMPLE_THREADS), 0, stream, sa);
+        AT_CHECK_HIP(hipGetLastError());
+        const int at = schedule.ticks() - 1;
+        if (at < trace_cap) {   // a trace too small loses its tail, the run goes on
+            int32_t* row = trace + 4 * (size_t)at;
+            row[0] = t.n_step; row[1] = t.n_start; row[2] = t.prefill_tokens; row[3] = t.route();
+        }
+        if (t.poll) {   // the host's only look at the device: some slot is in a final window, and when that ends only the device knows
+            AT_CHECK_HIP(hipMemcpyAsync(h->flags_host, s.done, slots * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            AT_CHECK_HIP(hipStreamSynchronize(stream));
+            schedule.seen(h->flags_host);
+        }
+    }
+    if (n_ticks) *n_ticks = schedule.ticks();
+    if (placement) std::memcpy(placement, schedule.placement().data(), (size_t)n_src * 3 * sizeof(int32_t));
     return 0;
 }
 

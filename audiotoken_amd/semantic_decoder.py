@@ -32,6 +32,8 @@ class AcousticGeneration:
     finish: List[str]                       # "stop" | "max_new_tokens" | "block_size"
     logits: Optional[List[torch.Tensor]] = None   # return_logits: float32 [n_b (+ 1 when the row stopped), V], the logits each id was drawn from
     windows: Optional[List[List[tuple]]] = None   # the long form: per row (source_start, source_len, carry, new_ids) of every window
+    ticks: Optional[List[tuple]] = None           # the queue (``slots=``): per tick (step tokens, windows started, prefill tokens, route)
+    placement: Optional[List[tuple]] = None       # the queue: per source (slot, first tick, last tick)
 
 
 def coarse_codes(ids, codebook_size: int = 1024, num_codebooks: int = 2) -> torch.Tensor:
@@ -103,6 +105,95 @@ def acoustic_windows(N: int, S: int, H: int, r: int = 3, block: int = 1024):
         carry = r * (S - H) if k else 0
         out.append((k * H, min(S, N - k * H), carry, None if k == n - 1 else r * S - carry))
     return out
+
+
+MAX_QUEUE_SOURCES = 4096   # of one queue call (csrc/gpt.h: GPT_MAX_QUEUE)
+MAX_SLOTS = 64             # cache rows (GPT_MAX_B)
+CHECK_EVERY = 16           # ticks between two looks of the host at the slots' flags (GPT_CHECK_EVERY)
+GEMM_ABOVE = 64            # a tick of more tokens takes the GEMM route (GPT_GEMM_ABOVE)
+DEFAULT_TICK_WINDOWS = 2   # the default tick_tokens is slots + this many windows of max_len
+
+
+def window_steps(plan, max_new: int, block: int):
+    """Per window of ``acoustic_windows``' plan: (prompt tokens, steps); the final window's steps are its budget."""
+    out = []
+    for start, n_src, carry, new in plan:
+        P = n_src + 1 + carry
+        out.append((P, min(max_new, block - P) if new is None else new))
+    return out
+
+
+def queue_ticks(lens, S: int, H: int, r: int, block: int, max_new: int, slots: int, tick_tokens: int, final_steps=None, detail: bool = False):
+    """The generation queue's host scheduler (``GptQueueSchedule`` in csrc/gpt.h is the same arithmetic): sources of ``lens`` ids run §19's
+    windows through ``slots`` cache rows. Waiting sources take empty slots in source order. A tick holds one step token of every slot that is mid-window
+    and the whole prompt of every window admitted, in slot order, while the list stays within ``tick_tokens``; the first window that does not fit waits,
+    and so does every slot after it. Every slot with a token samples once. A non-final window ends after its exact count and a final one after its budget,
+    which the host knows; a final window that ends earlier (``final_steps[i]`` sampler launches: its new ids, plus one for a sampled STOP) is seen at the
+    next poll, every ``CHECK_EVERY`` ticks while some slot is in a final window, and keeps stepping until then. Returns ``(ticks, placement)``: per tick
+    ``(step tokens, windows started, prefill tokens, route)`` with route 1 above ``GEMM_ABOVE`` tokens, per source ``(slot, first tick, last tick)``.
+    ``detail``: a third list, per tick ``(steps [(slot, source, window)], starts [(slot, source, window, prompt tokens)], polled, slots whose window waits)``."""
+    n_src = len(lens)
+    plans = [window_steps(acoustic_windows(int(N), S, H, r, block), max_new, block) for N in lens]
+    if not 1 <= slots <= MAX_SLOTS or not 1 <= n_src <= MAX_QUEUE_SOURCES:
+        raise ValueError(f"queue: 1 to {MAX_SLOTS} slots and 1 to {MAX_QUEUE_SOURCES} sources, got {slots} and {n_src}")
+    if tick_tokens < slots + max(P for plan in plans for P, _ in plan):
+        raise ValueError(f"queue: tick_tokens ({tick_tokens}) must hold a step of every slot and one whole window")
+    ends = [plan[-1][1] if final_steps is None else min(int(final_steps[i]), plan[-1][1]) for i, plan in enumerate(plans)]
+    slot = [None] * slots          # [source, window, running, steps sampled in the window]
+    placement = [[-1, -1, -1] for _ in range(n_src)]
+    ticks, events, next_src = [], [], 0
+    while True:
+        for j in range(slots):
+            if slot[j] is None and next_src < n_src:
+                slot[j] = [next_src, 0, False, 0]
+                placement[next_src][0] = j
+                next_src += 1
+        if all(s is None for s in slot):
+            break
+        at = len(ticks)
+        steps = [(j, s[0], s[1]) for j, s in enumerate(slot) if s is not None and s[2]]
+        starts, tokens = [], len(steps)
+        for j, s in enumerate(slot):
+            if s is None or s[2]:
+                continue
+            P = plans[s[0]][s[1]][0]
+            if tokens + P > tick_tokens:
+                break
+            starts.append((j, s[0], s[1], P))
+            tokens += P
+            s[2], s[3] = True, 0
+            if s[1] == 0:
+                placement[s[0]][1] = at
+        waiting = [j for j, s in enumerate(slot) if s is not None and not s[2]]
+        in_final = False
+        for j in [x[0] for x in steps] + [x[0] for x in starts]:
+            s = slot[j]
+            final = s[1] == len(plans[s[0]]) - 1
+            s[3] += 1
+            if s[3] < plans[s[0]][s[1]][1]:
+                in_final = in_final or final
+            elif final:
+                placement[s[0]][2] = at
+                slot[j] = None
+            else:
+                s[1], s[2] = s[1] + 1, False
+        ticks.append((len(steps), len(starts), tokens - len(steps), 1 if tokens > GEMM_ABOVE else 0))
+        poll = in_final and len(ticks) % CHECK_EVERY == 0
+        if poll:
+            for j, s in enumerate(slot):
+                if s is not None and s[2] and s[1] == len(plans[s[0]]) - 1 and s[3] >= ends[s[0]]:
+                    placement[s[0]][2] = at
+                    slot[j] = None
+        events.append((steps, starts, poll, waiting))
+    placement = [tuple(p) for p in placement]
+    return (ticks, placement, events) if detail else (ticks, placement)
+
+
+def queue_tick_bound(lens, S: int, H: int, r: int, block: int, max_new: int) -> int:
+    """No queue call runs more ticks than this, whatever ``slots``, ``tick_tokens`` and the final windows do: every tick either samples a step some window
+    still needs (there are at most the windows' budgets of those) or holds only finished slots the host has not seen, which lasts less than ``CHECK_EVERY``
+    ticks per source."""
+    return sum(sum(n for _, n in window_steps(acoustic_windows(int(N), S, H, r, block), max_new, block)) + CHECK_EVERY - 1 for N in lens)
 
 
 def seeded_uniforms(seed: int, batch: int, max_new_tokens: int) -> np.ndarray:
@@ -210,21 +301,35 @@ class SemanticToAcoustic(LibHandle):
         return AcousticGeneration(ids=ids, codes=codes, finish=finish, logits=logits, windows=windows)
 
     def to_acoustic_long(self, tokens, window: Optional[int] = None, hop: Optional[int] = None, max_new_tokens: int = 1024, temperature: float = 0.8,
-                         top_k: int = 100, seed: int = 0, uniforms: Optional[np.ndarray] = None, return_logits: bool = False) -> AcousticGeneration:
+                         top_k: int = 100, seed: int = 0, uniforms: Optional[np.ndarray] = None, return_logits: bool = False,
+                         slots: Optional[int] = None, tick_tokens: Optional[int] = None) -> AcousticGeneration:
         """``to_acoustic(constrain=True)`` for sources of any length up to 65536 ids: the source is walked in windows of ``window`` ids every
         ``hop`` ids (defaults: ``default_window``), each window prompted with the acoustic ids the window before produced for their overlap, all windows of up
         to 64 sources enqueued by one library call. Every window but a source's last produces exactly ``ids_per_source_token`` ids per source id and cannot
         stop; the last ends as ``to_acoustic`` does, within ``max_new_tokens``. ``uniforms``: float32 ``[B, L]``, the draw of a row's stream position (one per
         id of the result), ``L`` at least the longest row's capacity; from ``seed``: ``seeded_uniforms(seed, B, max(max_new_tokens, capacity))``. A source of
-        at most ``window`` ids gives what ``to_acoustic(constrain=True)`` gives. ``windows`` of the result is the schedule with the counts produced."""
+        at most ``window`` ids gives what ``to_acoustic(constrain=True)`` gives. ``windows`` of the result is the schedule with the counts produced.
+        ``slots`` (1 to 64) runs the sources through the generation queue instead: 1 to 4096 of them share ``slots`` cache rows, each starts
+        when a row is free and finishes on its own, and every source's result follows the same rule with the same draws, whatever its neighbours are.
+        ``tick_tokens``: the most tokens one model pass may hold (at least ``slots`` + the longest window; default ``slots + 2`` windows). The result then
+        carries ``ticks`` and ``placement`` (``queue_ticks``)."""
         cfg = self.config
         r, block = int(cfg.ids_per_source_token), self.block_size
         S = default_window(cfg, block)[0] if window is None else int(window)
         H = (S // 2) // 2 * 2 if hop is None else int(hop)
         batch = tokens if isinstance(tokens, (list, tuple)) else [tokens]
         B = len(batch)
-        if not 1 <= B <= 64:
-            raise ValueError(f"to_acoustic: 1 to 64 sources per call, got {B}")
+        if slots is None:
+            if tick_tokens is not None:
+                raise ValueError("to_acoustic: tick_tokens= belongs to slots=")
+            if not 1 <= B <= 64:
+                raise ValueError(f"to_acoustic: 1 to 64 sources per call, got {B}")
+        else:
+            slots = int(slots)
+            if not 1 <= slots <= MAX_SLOTS:
+                raise ValueError(f"to_acoustic: slots must be 1 to {MAX_SLOTS}, got {slots}")
+            if not 1 <= B <= MAX_QUEUE_SOURCES:
+                raise ValueError(f"to_acoustic: 1 to {MAX_QUEUE_SOURCES} sources per queue call, got {B}")
         max_new = int(max_new_tokens)
         if not 1 <= max_new <= 1024:
             raise ValueError(f"to_acoustic: max_new_tokens must be 1 to 1024, got {max_new}")
@@ -245,11 +350,17 @@ class SemanticToAcoustic(LibHandle):
         uniforms = np.ascontiguousarray(uniforms, dtype=np.float32)
         if uniforms.ndim != 2 or uniforms.shape[0] != B or uniforms.shape[1] < cap:
             raise ValueError(f"uniforms must be float32 [{B}, L] with L >= {cap} (one draw per row and stream position), got {uniforms.shape}")
+        if slots is not None:
+            tick_tokens = slots + DEFAULT_TICK_WINDOWS * longest if tick_tokens is None else int(tick_tokens)
+            if not slots + longest <= tick_tokens <= MAX_SLOTS * 1025:
+                raise ValueError(f"to_acoustic: tick_tokens must be at least slots + the longest window ({slots} + {longest}) and at most {MAX_SLOTS * 1025}, "
+                                 f"got {tick_tokens}")
         stride = max(lens)
         host = np.zeros((B, stride), dtype=np.int32)
         for b, s in enumerate(srcs):
             host[b, :lens[b]] = s.numpy()
         dev = self.device
+        ticks = placement = None
         with torch.cuda.device(dev):
             d_src = torch.from_numpy(host).to(dev)
             d_u = torch.from_numpy(uniforms).to(dev)
@@ -257,15 +368,28 @@ class SemanticToAcoustic(LibHandle):
             d_len = torch.zeros(B, dtype=torch.int32, device=dev)
             d_fin = torch.zeros(B, dtype=torch.int32, device=dev)
             d_logits = torch.empty((B, cap, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
-            nbytes = int(self._fn("long_state_bytes")(self.handle, B, longest))
-            state = self._workspace(max(nbytes, 256))
-            self._status.zero_()
             c_lens = (C.c_int32 * B)(*lens)
-            _cabi.check(self._fn("generate_long")(self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE,
-                                                  cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET, cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature),
-                                                  int(top_k), d_u.data_ptr(), uniforms.shape[1], d_ids.data_ptr(), cap, d_len.data_ptr(), d_fin.data_ptr(),
-                                                  _cabi.ptr(d_logits), state.data_ptr(), state.numel(), longest, _cabi.current_stream_handle(dev),
-                                                  self._status.data_ptr()), "at_gpt_generate_long")
+            if slots is not None:
+                nbytes = int(self._fn("queue_state_bytes")(self.handle, slots, longest, tick_tokens))
+                if nbytes == 0:
+                    raise ValueError(_cabi.last_error())
+                state = self._workspace(nbytes)
+                self._status.zero_()
+                cap_ticks = min(queue_tick_bound(lens, S, H, r, block, max_new), 1 << 20)   # past a million ticks the trace loses its tail
+                c_trace = (C.c_int32 * (4 * cap_ticks))()
+                c_n = C.c_int32(0)
+                c_place = (C.c_int32 * (3 * B))()
+                _cabi.check(self._fn("generate_queue")(self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE,
+                                                       cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET, cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature),
+                                                       int(top_k), d_u.data_ptr(), uniforms.shape[1], d_ids.data_ptr(), cap, d_len.data_ptr(),
+                                                       d_fin.data_ptr(), _cabi.ptr(d_logits), state.data_ptr(), state.numel(), longest, slots, tick_tokens,
+                                                       c_trace, cap_ticks, C.byref(c_n), c_place, _cabi.current_stream_handle(dev),
+                                                       self._status.data_ptr()), "at_gpt_generate_queue")
+                ticks = [tuple(c_trace[4 * i:4 * i + 4]) for i in range(min(c_n.value, cap_ticks))]
+                placement = [tuple(c_place[3 * i:3 * i + 3]) for i in range(B)]
+            else:
+                self._generate_long(d_src, stride, c_lens, B, S, H, r, max_new, temperature, top_k, d_u, uniforms.shape[1], d_ids, cap, d_len, d_fin, d_logits,
+                                    longest, dev)
             n = d_len.cpu().tolist()    # synchronises
             fin = d_fin.cpu().tolist()
             ids_all = d_ids.cpu().to(torch.int64)
@@ -277,7 +401,21 @@ class SemanticToAcoustic(LibHandle):
         if d_logits is not None:
             logits = [d_logits[b, :min(cap, n[b] + (1 if fin[b] == 1 else 0))].cpu() for b in range(B)]
         windows = [plan[:-1] + [plan[-1][:3] + (n[b] - base[b],)] for b, plan in enumerate(plans)]
-        return self._generation(ids, [FINISH[f] for f in fin], logits, windows)
+        out = self._generation(ids, [FINISH[f] for f in fin], logits, windows)
+        out.ticks, out.placement = ticks, placement
+        return out
+
+    def _generate_long(self, d_src, stride, c_lens, B, S, H, r, max_new, temperature, top_k, d_u, u_stride, d_ids, cap, d_len, d_fin, d_logits, longest, dev):
+        """The lockstep call: window k of every row as one batch."""
+        cfg = self.config
+        nbytes = int(self._fn("long_state_bytes")(self.handle, B, longest))
+        state = self._workspace(max(nbytes, 256))
+        self._status.zero_()
+        _cabi.check(self._fn("generate_long")(self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE,
+                                              cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET, cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature),
+                                              int(top_k), d_u.data_ptr(), u_stride, d_ids.data_ptr(), cap, d_len.data_ptr(), d_fin.data_ptr(),
+                                              _cabi.ptr(d_logits), state.data_ptr(), state.numel(), longest, _cabi.current_stream_handle(dev),
+                                              self._status.data_ptr()), "at_gpt_generate_long")
 
 
 def topk_sample(logits: torch.Tensor, temperature: float, top_k: int, uniforms: torch.Tensor, allow=None) -> torch.Tensor:

@@ -680,6 +680,26 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
                          int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
                          const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
                          float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev);
+/* The generation queue: n_src sources (1 to 4096) through `slots` cache rows (1 to 64). Every source follows at_gpt_generate_long's
+ * schedule unchanged (the same windows, carry, allow sets and finish rules, one draw per stream position); only when a window runs changes, and a slot
+ * that finishes a source takes the next waiting one, in the caller's order. All arrays are indexed by SOURCE: src_dev [n_src][src_stride], src_len HOST
+ * [n_src], uniforms_dev [n_src][u_stride], out_ids_dev [n_src][out_stride], out_len_dev / finish_dev [n_src], logits_out_dev NULL or
+ * [n_src][out_stride][V]; the draw of stream position p of source i is uniforms[i][p] whatever slot and tick it ran in. A tick is one model pass over one
+ * token list and one sampler launch: one step token of every slot that is mid-window, then the whole prompt of every window admitted this tick, in slot
+ * order while the list stays within tick_tokens (slots + max_len <= tick_tokens <= 65600, so one window always fits; a window that does not fit waits).
+ * A list of more than 64 tokens takes the GEMM route, a shorter one the streaming linear kernel, as a pass of at_gpt_generate does. The host reads the
+ * slots' flags every 16 ticks while some slot is in a final window, and nothing else. state_dev: at_gpt_queue_state_bytes(h, slots, max_len, tick_tokens)
+ * bytes (K / V for slots rows of max_len positions, activations for tick_tokens tokens, nothing per source); max_len as for at_gpt_generate_long.
+ * trace NULL or HOST int32 [trace_cap][4], one row per tick: step tokens, windows started, prefill tokens, route (1 = GEMM); n_ticks NULL or HOST: the
+ * ticks run (a trace too small loses its tail, the run goes on). placement NULL or HOST int32 [n_src][3]: slot, first tick, last tick of each source.
+ * With slots = 1 every tick is a lone prefill or a lone step, and the result is, id for id and logit for logit, the chain of one-row
+ * at_gpt_generate_long calls. Every argument and the schedule's extent are checked before the device is touched. Not re-entrant per handle. */
+size_t at_gpt_queue_state_bytes(const at_gpt_t* h, int slots, int max_len, int tick_tokens);
+int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, int S, int H, int r, int semantic_offset,
+                          int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                          const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
+                          float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace, int trace_cap,
+                          int32_t* n_ticks, int32_t* placement, at_stream_t stream, int32_t* status_dev);
 /* The sampling step alone, one workgroup per row, no float atomics (the same call twice gives the same ids). logits_dev device float32 [B][V], V <= 65536;
  * uniforms_dev device float32 [B]; allow NULL or a HOST array int32 [4] = two half-open id ranges; out_dev device int32 [B]. The rule:
  * 1. zt_i = z_i / temperature (one IEEE fp32 division). 2. ids outside the allow ranges become -inf. 3. v = the min(top_k, V)-th largest zt; every id
