@@ -1,5 +1,6 @@
-// The handle of the semantic-to-acoustic GPT (gpt.hip), declared apart from its code so that the stand-alone argument check
-// (tools/gpt_args.hip) can build a finalized handle with no device behind it: every entry point validates against `dims` alone before it touches one.
+// The handle of the semantic-to-acoustic GPT (gpt.hip, gpt_model.hip) and the pure host arithmetic of its schedules, declared apart from
+// the code so that the stand-alone argument checks (tools/gpt_*args.hip) can build a finalized handle with no device behind it: every entry point
+// validates against the handle's dimensions alone before it touches one.
 #pragma once
 #include <map>
 #include <string>
@@ -20,6 +21,41 @@ constexpr int GPT_MAX_SOURCE = 65536;  // source ids of one row of at_gpt_genera
 
 // The long form's schedule: windows of a source of N ids at window S and hop H; window k reads source ids [k H, k H + min(S, N - k H)).
 inline int gpt_long_windows(int N, int S, int H) { return N <= S ? 1 : (N - S + H - 1) / H + 1; }
+
+// Window k of a source of N ids: n_ids source ids, `carry` ids of the source's own stream behind them and INFER between make the P prompt tokens; the
+// window's step 0 lies at stream_base; it runs `budget` steps (a final window: at most). The one statement of this arithmetic for the three entry points,
+// the scheduler below and tools/gpt_queue_args.hip; acoustic_windows / window_steps in semantic_decoder.py are its Python twins.
+struct GptWindow {
+    int n_ids, P, budget, carry, stream_base;
+    bool final_window;
+};
+inline GptWindow gpt_window(int N, int k, int S, int H, int r, int max_new, int block) {
+    GptWindow w;
+    w.carry = k > 0 ? r * (S - H) : 0;
+    w.final_window = k == gpt_long_windows(N, S, H) - 1;
+    w.n_ids = w.final_window ? N - k * H : S;
+    w.P = w.n_ids + 1 + w.carry;
+    w.budget = w.final_window ? (max_new < block - w.P ? max_new : block - w.P) : r * S - w.carry;
+    w.stream_base = r * k * H + w.carry;
+    return w;
+}
+// What a set of sources needs: positions of a cache row (the longest window with its new ids) and ids of a row of the caller's stream arrays
+struct GptExtent {
+    int need_len = 0;
+    int64_t need_stride = 0;
+};
+inline GptExtent gpt_extent(const int32_t* src_len, int n_src, int S, int H, int r, int max_new, int block) {
+    GptExtent e;
+    for (int i = 0; i < n_src; ++i) {
+        const int n = gpt_long_windows(src_len[i], S, H);
+        const GptWindow w = gpt_window(src_len[i], n - 1, S, H, r, max_new, block);
+        const int64_t end = (int64_t)w.stream_base + w.budget;
+        e.need_stride = end > e.need_stride ? end : e.need_stride;
+        e.need_len = w.P + w.budget > e.need_len ? w.P + w.budget : e.need_len;
+        if (n > 1 && S + 1 + r * S > e.need_len) e.need_len = S + 1 + r * S;   // a non-final window fills up to here
+    }
+    return e;
+}
 
 // ---- the generation queue's scheduler: pure host code, shared by at_gpt_generate_queue and tools/gpt_queue_args.hip ------------------------
 // Sources run 19's windows through `slots` cache rows. A tick is one model pass over one token list: one step token of every slot that is mid-window, then
@@ -49,14 +85,6 @@ class GptQueueSchedule {
           placement_((size_t)n_src * 3, -1) {
         for (int j = 0; j < GPT_MAX_B; ++j) slot_[j] = Slot{};
     }
-    // window k of a source of N ids: its source ids, prompt tokens and steps (a final window's: at most)
-    void window(int N, int k, int* n_ids, int* P, int* budget, bool* final_window) const {
-        const int n = gpt_long_windows(N, S_, H_), carry = k > 0 ? r_ * (S_ - H_) : 0;
-        *final_window = k == n - 1;
-        *n_ids = *final_window ? N - k * H_ : S_;
-        *P = *n_ids + 1 + carry;
-        *budget = *final_window ? (max_new_ < block_ - *P ? max_new_ : block_ - *P) : r_ * S_ - carry;
-    }
     // The next tick, or false when every source has been retired. Waiting sources take empty slots in source order; every running slot steps; windows are
     // admitted in slot order while the list stays within tick_tokens (the first always fits, so no tick is empty and no slot starves).
     bool next(GptQueueTick* t) {
@@ -78,15 +106,13 @@ class GptQueueSchedule {
         for (int j = 0; j < slots_; ++j) {
             Slot& s = slot_[j];
             if (s.src < 0 || s.running) continue;
-            int n_ids, P, budget;
-            bool fin;
-            window(len_[s.src], s.k, &n_ids, &P, &budget, &fin);
-            if (t->tokens() + P > tick_tokens_) break;   // it waits, and so does every slot after it
-            t->start[t->n_start++] = GptQueueStart{j, s.src, s.k, fin ? 1 : 0, n_ids, P};
-            t->prefill_tokens += P;
+            const GptWindow w = gpt_window(len_[s.src], s.k, S_, H_, r_, max_new_, block_);
+            if (t->tokens() + w.P > tick_tokens_) break;   // it waits, and so does every slot after it
+            t->start[t->n_start++] = GptQueueStart{j, s.src, s.k, w.final_window ? 1 : 0, w.n_ids, w.P};
+            t->prefill_tokens += w.P;
             s.running = true;
-            s.final_window = fin;
-            s.budget = budget;
+            s.final_window = w.final_window;
+            s.budget = w.budget;
             s.t = 0;
             if (s.k == 0) placement_[3 * (size_t)s.src + 1] = tick_;
         }

@@ -123,6 +123,20 @@ def window_steps(plan, max_new: int, block: int):
     return out
 
 
+def stream_extent(plans, S: int, r: int, max_new: int, block: int):
+    """What a set of sources needs, from their ``acoustic_windows`` plans (``gpt_extent`` in csrc/gpt.h is the same arithmetic): ``(base, cap, longest)``,
+    per source the stream position of its final window's step 0, the ids of the longest source's stream, and the positions of the longest window with
+    its new ids (a non-final window fills ``S + 1 + r S``)."""
+    base, cap, longest = [], 0, 0
+    for plan in plans:
+        start, _, carry, _ = plan[-1]
+        P, budget = window_steps(plan, max_new, block)[-1]
+        base.append(r * start + carry)
+        cap = max(cap, base[-1] + budget)
+        longest = max(longest, P + budget, S + 1 + r * S if len(plan) > 1 else 0)
+    return base, cap, longest
+
+
 def queue_ticks(lens, S: int, H: int, r: int, block: int, max_new: int, slots: int, tick_tokens: int, final_steps=None, detail: bool = False):
     """The generation queue's host scheduler (``GptQueueSchedule`` in csrc/gpt.h is the same arithmetic): sources of ``lens`` ids run §19's
     windows through ``slots`` cache rows. Waiting sources take empty slots in source order. A tick holds one step token of every slot that is mid-window
@@ -247,35 +261,46 @@ class SemanticToAcoustic(LibHandle):
         for b, p in enumerate(prompts):
             host[b, :lens[b]] = np.asarray(p, dtype=np.int32)
         max_len = max(1, min(self.block_size, stride + max_new))
-        dev = self.device
-        with torch.cuda.device(dev):
-            d_prompts = torch.from_numpy(host).to(dev)
-            d_u = torch.from_numpy(uniforms).to(dev)
-            d_ids = torch.full((max(B, 1), max(max_new, 1)), -1, dtype=torch.int32, device=dev)
-            d_len = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
-            d_fin = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
-            d_logits = torch.empty((B, max_new, self.vocab), dtype=torch.float32, device=dev) if return_logits and B >= 1 and max_new >= 1 else None
+        c_lens = (C.c_int32 * max(B, 1))(*lens)
+        c_allow = None if allow is None else (C.c_int32 * 8)(*[int(v) for v in np.asarray(allow).reshape(8)])
+
+        def call(dev, d_prompts, d_u, d_ids, d_len, d_fin, d_logits):
             nbytes = int(self._fn("state_bytes")(self.handle, B, max_len))
             state = self._workspace(max(nbytes, 256))
             self._status.zero_()
-            c_lens = (C.c_int32 * max(B, 1))(*lens)
-            c_allow = None if allow is None else (C.c_int32 * 8)(*[int(v) for v in np.asarray(allow).reshape(8)])
             _cabi.check(self._fn("generate")(self.handle, d_prompts.data_ptr(), stride, c_lens, B, max_new, float(temperature), int(top_k), int(stop_token),
                                              d_u.data_ptr(), c_allow, d_ids.data_ptr(), d_len.data_ptr(), d_fin.data_ptr(), _cabi.ptr(d_logits),
                                              state.data_ptr(), state.numel(), max_len, _cabi.current_stream_handle(dev), self._status.data_ptr()),
                         "at_gpt_generate")
+
+        ids, _, fin, logits = self._run(call, host, uniforms, B, max_new, return_logits and B >= 1 and max_new >= 1,
+                                        "at_gpt_generate: a prompt id lies outside the model's vocabulary")
+        return ids, [FINISH[f] for f in fin], logits
+
+    def _run(self, call, host, uniforms, B, cap, return_logits, bad_id):
+        """One library call around its buffers: uploads ``host`` (int32 ids) and ``uniforms``, allocates ``ids [B, cap]`` (-1), the lengths, the finish flags
+        and (``return_logits``) ``logits [B, cap, V]``, runs ``call(dev, d_host, d_u, d_ids, d_len, d_fin, d_logits)``, reads back. Returns per row the ids,
+        the count, the finish code and the logits ``[n + stopped, V]`` (or None); ``last_raw_ids`` keeps the whole id buffer. Status bit 0 raises ``bad_id``."""
+        dev = self.device
+        with torch.cuda.device(dev):
+            d_host = torch.from_numpy(host).to(dev)
+            d_u = torch.from_numpy(uniforms).to(dev)
+            d_ids = torch.full((max(B, 1), max(cap, 1)), -1, dtype=torch.int32, device=dev)
+            d_len = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
+            d_fin = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
+            d_logits = torch.empty((B, cap, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
+            call(dev, d_host, d_u, d_ids, d_len, d_fin, d_logits)
             n = d_len.cpu().tolist()    # synchronises
             fin = d_fin.cpu().tolist()
             ids_all = d_ids.cpu().to(torch.int64)
         if self.last_status() & 1:
-            raise ValueError("at_gpt_generate: a prompt id lies outside the model's vocabulary")
-        self.last_raw_ids = ids_all   # the whole [B, max_new_tokens] buffer, -1 where nothing was written (tests)
+            raise ValueError(bad_id)
+        self.last_raw_ids = ids_all   # the whole [B, cap] buffer, -1 where nothing was written (tests)
         ids = [ids_all[b, :n[b]].clone() for b in range(B)]
-        finish = [FINISH[f] for f in fin]
         logits = None
         if d_logits is not None:
-            logits = [d_logits[b, :min(max_new, n[b] + (1 if fin[b] == 1 else 0))].cpu() for b in range(B)]
-        return ids, finish, logits
+            logits = [d_logits[b, :min(cap, n[b] + (1 if fin[b] == 1 else 0))].cpu() for b in range(B)]
+        return ids, n, fin, logits
 
     def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0,
                     uniforms: Optional[np.ndarray] = None, constrain: bool = False, return_logits: bool = False) -> AcousticGeneration:
@@ -336,15 +361,7 @@ class SemanticToAcoustic(LibHandle):
         srcs = [source_ids(t, cfg) for t in batch]
         plans = [acoustic_windows(int(s.numel()), S, H, r, block) for s in srcs]   # refuses a bad window / hop / length before anything is launched
         lens = [int(s.numel()) for s in srcs]
-        base, cap, longest = [], 0, 0
-        for plan in plans:
-            k = len(plan) - 1
-            start, n_src, carry, _ = plan[-1]
-            P = n_src + 1 + carry
-            budget = min(max_new, block - P)
-            base.append(r * start + carry)
-            cap = max(cap, base[-1] + budget)
-            longest = max(longest, P + budget, S + 1 + r * S if k else 0)
+        base, cap, longest = stream_extent(plans, S, r, max_new, block)
         if uniforms is None:
             uniforms = seeded_uniforms(seed, B, max(max_new, cap))
         uniforms = np.ascontiguousarray(uniforms, dtype=np.float32)
@@ -359,63 +376,40 @@ class SemanticToAcoustic(LibHandle):
         host = np.zeros((B, stride), dtype=np.int32)
         for b, s in enumerate(srcs):
             host[b, :lens[b]] = s.numpy()
-        dev = self.device
-        ticks = placement = None
-        with torch.cuda.device(dev):
-            d_src = torch.from_numpy(host).to(dev)
-            d_u = torch.from_numpy(uniforms).to(dev)
-            d_ids = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
-            d_len = torch.zeros(B, dtype=torch.int32, device=dev)
-            d_fin = torch.zeros(B, dtype=torch.int32, device=dev)
-            d_logits = torch.empty((B, cap, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
-            c_lens = (C.c_int32 * B)(*lens)
-            if slots is not None:
-                nbytes = int(self._fn("queue_state_bytes")(self.handle, slots, longest, tick_tokens))
-                if nbytes == 0:
-                    raise ValueError(_cabi.last_error())
-                state = self._workspace(nbytes)
+        c_lens = (C.c_int32 * B)(*lens)
+        queue = {}
+
+        def call(dev, d_src, d_u, d_ids, d_len, d_fin, d_logits):
+            # what the two entry points share: the sources, the geometry, the token space, the sampling arguments and the caller's arrays
+            head = (self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE, cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET,
+                    cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature), int(top_k), d_u.data_ptr(), uniforms.shape[1], d_ids.data_ptr(), cap,
+                    d_len.data_ptr(), d_fin.data_ptr(), _cabi.ptr(d_logits))
+            tail = (_cabi.current_stream_handle(dev), self._status.data_ptr())
+            if slots is None:   # the lockstep call: window k of every row as one batch
+                nbytes = int(self._fn("long_state_bytes")(self.handle, B, longest))
+                state = self._workspace(max(nbytes, 256))
                 self._status.zero_()
-                cap_ticks = min(queue_tick_bound(lens, S, H, r, block, max_new), 1 << 20)   # past a million ticks the trace loses its tail
-                c_trace = (C.c_int32 * (4 * cap_ticks))()
-                c_n = C.c_int32(0)
-                c_place = (C.c_int32 * (3 * B))()
-                _cabi.check(self._fn("generate_queue")(self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE,
-                                                       cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET, cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature),
-                                                       int(top_k), d_u.data_ptr(), uniforms.shape[1], d_ids.data_ptr(), cap, d_len.data_ptr(),
-                                                       d_fin.data_ptr(), _cabi.ptr(d_logits), state.data_ptr(), state.numel(), longest, slots, tick_tokens,
-                                                       c_trace, cap_ticks, C.byref(c_n), c_place, _cabi.current_stream_handle(dev),
-                                                       self._status.data_ptr()), "at_gpt_generate_queue")
-                ticks = [tuple(c_trace[4 * i:4 * i + 4]) for i in range(min(c_n.value, cap_ticks))]
-                placement = [tuple(c_place[3 * i:3 * i + 3]) for i in range(B)]
-            else:
-                self._generate_long(d_src, stride, c_lens, B, S, H, r, max_new, temperature, top_k, d_u, uniforms.shape[1], d_ids, cap, d_len, d_fin, d_logits,
-                                    longest, dev)
-            n = d_len.cpu().tolist()    # synchronises
-            fin = d_fin.cpu().tolist()
-            ids_all = d_ids.cpu().to(torch.int64)
-        if self.last_status() & 1:
-            raise ValueError("at_gpt_generate_long: a source id lies outside the semantic vocabulary")
-        self.last_raw_ids = ids_all   # the whole [B, capacity] buffer, -1 where nothing was written (tests)
-        ids = [ids_all[b, :n[b]].clone() for b in range(B)]
-        logits = None
-        if d_logits is not None:
-            logits = [d_logits[b, :min(cap, n[b] + (1 if fin[b] == 1 else 0))].cpu() for b in range(B)]
+                _cabi.check(self._fn("generate_long")(*head, state.data_ptr(), state.numel(), longest, *tail), "at_gpt_generate_long")
+                return
+            nbytes = int(self._fn("queue_state_bytes")(self.handle, slots, longest, tick_tokens))
+            if nbytes == 0:
+                raise ValueError(_cabi.last_error())
+            state = self._workspace(nbytes)
+            self._status.zero_()
+            cap_ticks = min(queue_tick_bound(lens, S, H, r, block, max_new), 1 << 20)   # past a million ticks the trace loses its tail
+            c_trace = (C.c_int32 * (4 * cap_ticks))()
+            c_n = C.c_int32(0)
+            c_place = (C.c_int32 * (3 * B))()
+            _cabi.check(self._fn("generate_queue")(*head, state.data_ptr(), state.numel(), longest, slots, tick_tokens, c_trace, cap_ticks, C.byref(c_n),
+                                                   c_place, *tail), "at_gpt_generate_queue")
+            queue["ticks"] = [tuple(c_trace[4 * i:4 * i + 4]) for i in range(min(c_n.value, cap_ticks))]
+            queue["placement"] = [tuple(c_place[3 * i:3 * i + 3]) for i in range(B)]
+
+        ids, n, fin, logits = self._run(call, host, uniforms, B, cap, return_logits, "at_gpt_generate_long: a source id lies outside the semantic vocabulary")
         windows = [plan[:-1] + [plan[-1][:3] + (n[b] - base[b],)] for b, plan in enumerate(plans)]
         out = self._generation(ids, [FINISH[f] for f in fin], logits, windows)
-        out.ticks, out.placement = ticks, placement
+        out.ticks, out.placement = queue.get("ticks"), queue.get("placement")
         return out
-
-    def _generate_long(self, d_src, stride, c_lens, B, S, H, r, max_new, temperature, top_k, d_u, u_stride, d_ids, cap, d_len, d_fin, d_logits, longest, dev):
-        """The lockstep call: window k of every row as one batch."""
-        cfg = self.config
-        nbytes = int(self._fn("long_state_bytes")(self.handle, B, longest))
-        state = self._workspace(max(nbytes, 256))
-        self._status.zero_()
-        _cabi.check(self._fn("generate_long")(self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE,
-                                              cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET, cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature),
-                                              int(top_k), d_u.data_ptr(), u_stride, d_ids.data_ptr(), cap, d_len.data_ptr(), d_fin.data_ptr(),
-                                              _cabi.ptr(d_logits), state.data_ptr(), state.numel(), longest, _cabi.current_stream_handle(dev),
-                                              self._status.data_ptr()), "at_gpt_generate_long")
 
 
 def topk_sample(logits: torch.Tensor, temperature: float, top_k: int, uniforms: torch.Tensor, allow=None) -> torch.Tensor:

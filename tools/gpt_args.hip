@@ -1,39 +1,9 @@
-// The argument checks of the GPT decoder's entry points (audiotoken_amd/csrc/gpt.hip: at_gpt_generate, at_gpt_state_bytes, at_op_topk_sample) under
+// The argument checks of the GPT decoder's entry points (audiotoken_amd/csrc/gpt.hip: at_gpt_generate, at_gpt_state_bytes; gpt_model.hip: at_op_topk_sample) under
 // AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program. Every case below is refused before anything is launched, so it needs no
-// device: the handle is a finalized at_gpt built here by hand (gpt.h), with dimensions and no device memory behind it. Built and run by
-// `make -C audiotoken_amd/csrc gpt_asan`:
-//   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined tools/gpt_args.hip audiotoken_amd/csrc/gpt.hip audiotoken_amd/csrc/gemm_f32.hip
-// (gemm_f32.hip only because gpt.hip's prefill calls its launcher; nothing of it runs here).
-// The host arrays (prompt lengths, allow ranges) live in heap blocks of exactly the size the call may read, so a read past them is a sanitizer report.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "../audiotoken_amd/csrc/gpt.h"
-#include "../include/audiotoken_hip.h"
-
-namespace at {
-static std::string g_error;
-void set_error(const std::string& msg) { g_error = msg; }   // the library's lives in encodec.hip, which this program does not link
-}  // namespace at
-
-static int failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        std::printf("FAILED: %s (last error: %s)\n", what, at::g_error.c_str());
-        ++failures;
-    }
-}
-static bool refused(int rc, const char* text) { return rc != 0 && at::g_error.find(text) != std::string::npos; }
-
-// stand-ins for device pointers: never dereferenced by a call that is refused
-static int32_t fake_i[4];
-static float fake_f[4];
+// device: the handle is a finalized at_gpt built by hand (gpt_args_common.h). Built and run by `make -C audiotoken_amd/csrc gpt_asan`:
+//   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined tools/gpt_args.hip audiotoken_amd/csrc/{gpt,gpt_model,gemm_f32}.hip
+// (gemm_f32.hip only because the model pass calls its launcher; nothing of it runs here).
+#include "gpt_args_common.h"
 
 struct Call {
     at_gpt* h;
@@ -51,23 +21,16 @@ struct Call {
     int max_len = 116;
 
     int run() const {
-        std::unique_ptr<int32_t[]> l(new int32_t[lens.size() ? lens.size() : 1]);
-        if (!lens.empty()) std::memcpy(l.get(), lens.data(), lens.size() * sizeof(int32_t));
-        std::unique_ptr<int32_t[]> a(new int32_t[allow.size() ? allow.size() : 1]);
-        if (!allow.empty()) std::memcpy(a.get(), allow.data(), allow.size() * sizeof(int32_t));
+        const auto l = exact_copy(lens), a = exact_copy(allow);
         at::g_error.clear();
-        return at_gpt_generate(h, prompts, stride, lens.empty() ? nullptr : l.get(), B, max_new, temperature, top_k, stop, uniforms,
-                               allow.empty() ? nullptr : a.get(), out_ids, out_len, finish, nullptr, state, state_bytes, max_len, nullptr, nullptr);
+        return at_gpt_generate(h, prompts, stride, l.get(), B, max_new, temperature, top_k, stop, uniforms, a.get(), out_ids, out_len, finish, nullptr, state,
+                               state_bytes, max_len, nullptr, nullptr);
     }
 };
 
 int main() {
     at_gpt model;
-    model.finalized = true;
-    model.n_layer = 2;
-    model.vocab = 128;
-    model.block = 128;
-    model.layers.resize(2);
+    finalize_by_hand(&model, 128);
     at_gpt raw;   // never finalized
 
     // ---- at_gpt_state_bytes
@@ -79,10 +42,10 @@ int main() {
     expect(at_gpt_state_bytes(&raw, 1, 64) == 0, "state bytes before finalize");
     expect(at_gpt_state_bytes(&model, 0, 64) == 0 && at::g_error.find("B must be") != std::string::npos, "state bytes, B = 0");
     expect(at_gpt_state_bytes(&model, 65, 64) == 0, "state bytes, B = 65");
-    expect(at_gpt_state_bytes(&model, std::numeric_limits<int>::min(), 64) == 0, "state bytes, B = INT_MIN");
+    expect(at_gpt_state_bytes(&model, INT_MIN_, 64) == 0, "state bytes, B = INT_MIN");
     expect(at_gpt_state_bytes(&model, 1, 0) == 0 && at::g_error.find("max_len") != std::string::npos, "state bytes, max_len = 0");
     expect(at_gpt_state_bytes(&model, 1, 129) == 0, "state bytes, max_len past the block");
-    expect(at_gpt_state_bytes(&model, 1, std::numeric_limits<int>::max()) == 0, "state bytes, max_len = INT_MAX");
+    expect(at_gpt_state_bytes(&model, 1, INT_MAX_) == 0, "state bytes, max_len = INT_MAX");
     expect(at_gpt_num_layers(&model) == 2 && at_gpt_vocab(&model) == 128 && at_gpt_block_size(&model) == 128, "the getters");
     expect(at_gpt_num_layers(&raw) == 0 && at_gpt_vocab(nullptr) == 0, "the getters before finalize");
 
@@ -109,11 +72,11 @@ int main() {
     { Call c = ok; c.lens = {100, 129}; expect(refused(c.run(), "longer than the model's block"), "a prompt longer than the block"); }
     { Call c = ok; c.lens = {100, 101}; expect(refused(c.run(), "row 1 must be 1 to prompt_stride"), "a prompt longer than its row"); }
     { Call c = ok; c.lens = {0, 7}; expect(refused(c.run(), "row 0 must be 1 to prompt_stride"), "an empty prompt"); }
-    { Call c = ok; c.lens = {100, std::numeric_limits<int32_t>::min()}; expect(refused(c.run(), "row 1"), "prompt_len = INT_MIN"); }
-    { Call c = ok; c.lens = {std::numeric_limits<int32_t>::max(), 7}; expect(refused(c.run(), "row 0"), "prompt_len = INT_MAX"); }
+    { Call c = ok; c.lens = {100, INT_MIN_}; expect(refused(c.run(), "row 1"), "prompt_len = INT_MIN"); }
+    { Call c = ok; c.lens = {INT_MAX_, 7}; expect(refused(c.run(), "row 0"), "prompt_len = INT_MAX"); }
     { Call c = ok; c.max_new = 0; expect(refused(c.run(), "max_new"), "max_new = 0"); }
     { Call c = ok; c.max_new = 1025; expect(refused(c.run(), "max_new"), "max_new = 1025"); }
-    { Call c = ok; c.max_new = std::numeric_limits<int>::max(); expect(refused(c.run(), "max_new"), "max_new = INT_MAX"); }
+    { Call c = ok; c.max_new = INT_MAX_; expect(refused(c.run(), "max_new"), "max_new = INT_MAX"); }
     { Call c = ok; c.temperature = 0.0f; expect(refused(c.run(), "temperature"), "temperature = 0"); }
     { Call c = ok; c.temperature = -1.0f; expect(refused(c.run(), "temperature"), "temperature < 0"); }
     { Call c = ok; c.temperature = std::nanf(""); expect(refused(c.run(), "temperature"), "temperature = NaN"); }
@@ -132,10 +95,9 @@ int main() {
 
     // ---- at_op_topk_sample
     auto sample = [&](const float* z, int B, int V, float t, int k, const float* u, std::vector<int32_t> allow, int32_t* out) {
-        std::unique_ptr<int32_t[]> a(new int32_t[allow.size() ? allow.size() : 1]);
-        if (!allow.empty()) std::memcpy(a.get(), allow.data(), allow.size() * sizeof(int32_t));
+        const auto a = exact_copy(allow);
         at::g_error.clear();
-        return at_op_topk_sample(z, B, V, t, k, u, allow.empty() ? nullptr : a.get(), out, nullptr);
+        return at_op_topk_sample(z, B, V, t, k, u, a.get(), out, nullptr);
     };
     expect(refused(sample(nullptr, 1, 128, 1.f, 1, fake_f, {}, fake_i), "null pointer"), "sample: null logits");
     expect(refused(sample(fake_f, 1, 128, 1.f, 1, nullptr, {}, fake_i), "null pointer"), "sample: null uniforms");
@@ -148,10 +110,5 @@ int main() {
     expect(refused(sample(fake_f, 1, 128, 1.f, 0, fake_f, {}, fake_i), "top_k"), "sample: top_k = 0");
     expect(refused(sample(fake_f, 1, 128, 1.f, 1, fake_f, {0, 129, 0, 0}, fake_i), "allow ranges"), "sample: an allow range past V");
     expect(refused(sample(fake_f, 1, 128, 1.f, 1, fake_f, {3, 3, 9, 9}, fake_i), "both empty"), "sample: allow ranges that allow nothing");
-    if (failures) {
-        std::printf("%d case(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("gpt argument checks: ok\n");
-    return 0;
+    return verdict("gpt argument checks");
 }

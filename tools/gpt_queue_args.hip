@@ -1,40 +1,16 @@
 // The generation queue's host side (audiotoken_amd/csrc/gpt.hip: at_gpt_generate_queue, at_gpt_queue_state_bytes; csrc/gpt.h: GptQueueSchedule) under
-// AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program, the way tools/gpt_long_args.hip checks the long form. Two modes:
-//   gpt_queue_args                                    every refusal path on a finalized at_gpt built here by hand, with no device memory behind it
+// AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program, the way tools/gpt_long_args.hip checks the long form. Three modes:
+//   gpt_queue_args                                    every refusal path on a finalized at_gpt built by hand (gpt_args_common.h)
 //   gpt_queue_args dry S H r block max_new slots tick_tokens N:e [N:e ...]
 //                                                     the scheduler alone: sources of N ids whose final window ends after e sampler launches; prints
 //                                                     "tick <steps> <starts> <prefill> <route>" per tick, then "source <slot> <first> <last>" per source
-// Built and run by `make -C audiotoken_amd/csrc gpt_queue_asan` (QUEUE_ARGS="dry ..." for the second mode).
-#include <cmath>
-#include <cstdio>
+//   gpt_queue_args extent S H r block max_new N [N ...]
+//                                                     the shared geometry alone (gpt.h: gpt_extent, gpt_window): prints "extent <need_len> <need_stride>", then
+//                                                     "window <source> <k> <n_ids> <P> <budget> <final> <stream_base>" per window
+// Built and run by `make -C audiotoken_amd/csrc gpt_queue_asan` (QUEUE_ARGS="dry ..." or "extent ..." for the other modes).
 #include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
-#include <vector>
 
-#include "../audiotoken_amd/csrc/gpt.h"
-#include "../include/audiotoken_hip.h"
-
-namespace at {
-static std::string g_error;
-void set_error(const std::string& msg) { g_error = msg; }   // the library's lives in encodec.hip, which this program does not link
-}  // namespace at
-
-static int failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        std::printf("FAILED: %s (last error: %s)\n", what, at::g_error.c_str());
-        ++failures;
-    }
-}
-static bool refused(int rc, const char* text) { return rc != 0 && at::g_error.find(text) != std::string::npos; }
-
-// stand-ins for device pointers: never dereferenced by a call that is refused
-static int32_t fake_i[4];
-static float fake_f[4];
+#include "gpt_args_common.h"
 
 // The model and the token space of tools/gpt_long_args.hip: 128 positions, 256 ids, S = 8, H = 4, r = 3; sources of 30 ids (7 windows, the stream reaches
 // 84 + 16 = 100 positions, the final window 6 + 1 + 12 + 16 = 35 tokens) and 5 ids, through 2 slots.
@@ -59,10 +35,9 @@ struct Call {
     int trace_cap = 0;
 
     int run() const {
-        std::unique_ptr<int32_t[]> l(new int32_t[lens.size() ? lens.size() : 1]);
-        if (!lens.empty()) std::memcpy(l.get(), lens.data(), lens.size() * sizeof(int32_t));
+        const auto l = exact_copy(lens);
         at::g_error.clear();
-        return at_gpt_generate_queue(h, src, stride, lens.empty() ? nullptr : l.get(), n_src, S, H, r, sem_off, sem_vocab, infer, ac_off, cb, stop, max_new,
+        return at_gpt_generate_queue(h, src, stride, l.get(), n_src, S, H, r, sem_off, sem_vocab, infer, ac_off, cb, stop, max_new,
                                      temperature, top_k, uniforms, u_stride, out_ids, out_stride, out_len, finish, nullptr, state, state_bytes, max_len, slots,
                                      tick_tokens, trace, trace_cap, nullptr, nullptr, nullptr, nullptr);
     }
@@ -70,13 +45,8 @@ struct Call {
 
 static int refusals() {
     at_gpt model;
-    model.finalized = true;
-    model.n_layer = 2;
-    model.vocab = 256;
-    model.block = 128;
-    model.layers.resize(2);
+    finalize_by_hand(&model, 256);
     at_gpt raw;   // never finalized
-    const int INT_MAX_ = std::numeric_limits<int>::max(), INT_MIN_ = std::numeric_limits<int>::min();
 
     // ---- at_gpt_queue_state_bytes
     at::g_error.clear();
@@ -155,12 +125,12 @@ static int refusals() {
     { Call c = ok; c.tick_tokens = INT_MIN_; c.state_bytes = need; expect(refused(c.run(), "tick_tokens"), "tick_tokens = INT_MIN"); }
     { Call c = ok; c.slots = 64; c.tick_tokens = 64 + 35; expect(refused(c.run(), "state too small"), "more slots than sources"); }
     { Call c = ok; c.n_src = 4096; c.lens.assign(4096, 30); c.lens[4095] = 1; expect(refused(c.run(), "state too small"), "4096 sources"); }
-    if (failures) {
-        std::printf("%d case(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("gpt queue argument checks: ok\n");
-    return 0;
+    return verdict("gpt queue argument checks");
+}
+
+// what at_gpt_generate_queue requires of the geometry before it builds a schedule
+static bool geometry_ok(int S, int H, int r, int block, int max_new) {
+    return S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0 && H <= S && r >= 1 && block <= at::GPT_MAX_BLOCK && (int64_t)S + 1 + (int64_t)r * S <= block && max_new >= 1;
 }
 
 static int dry_run(int argc, char** argv) {
@@ -180,20 +150,14 @@ static int dry_run(int argc, char** argv) {
         lens.push_back(N);
         ends.push_back(e);
     }
-    // what at_gpt_generate_queue requires before it builds a schedule
     int longest = 0;
-    const bool geometry = S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0 && H <= S && r >= 1 && block <= at::GPT_MAX_BLOCK && (int64_t)S + 1 + (int64_t)r * S <= block &&
-                          max_new >= 1 && slots >= 1 && slots <= at::GPT_MAX_B && (int)lens.size() <= at::GPT_MAX_QUEUE;
-    if (geometry) {
-        const at::GptQueueSchedule probe(lens.data(), (int)lens.size(), S, H, r, max_new, block, slots, tick_tokens);
+    const bool geometry = geometry_ok(S, H, r, block, max_new) && slots >= 1 && slots <= at::GPT_MAX_B && (int)lens.size() <= at::GPT_MAX_QUEUE;
+    if (geometry)
         for (int32_t N : lens)
             for (int k = 0; k < at::gpt_long_windows(N, S, H); ++k) {
-                int n_ids, P, budget;
-                bool fin;
-                probe.window(N, k, &n_ids, &P, &budget, &fin);
+                const int P = at::gpt_window(N, k, S, H, r, max_new, block).P;
                 longest = P > longest ? P : longest;
             }
-    }
     if (!geometry || tick_tokens < slots + longest) {
         std::printf("refused: the geometry, or tick_tokens below slots + the longest prompt\n");
         return 2;
@@ -210,7 +174,32 @@ static int dry_run(int argc, char** argv) {
     return 0;
 }
 
+static int extent_run(int argc, char** argv) {
+    if (argc < 8) {
+        std::printf("usage: gpt_queue_args extent S H r block max_new N [N ...]\n");
+        return 2;
+    }
+    const int S = std::atoi(argv[2]), H = std::atoi(argv[3]), r = std::atoi(argv[4]), block = std::atoi(argv[5]), max_new = std::atoi(argv[6]);
+    std::vector<int32_t> lens;
+    for (int i = 7; i < argc; ++i) lens.push_back(std::atoi(argv[i]));
+    bool ok = geometry_ok(S, H, r, block, max_new);
+    for (int32_t N : lens) ok = ok && N >= 1 && N <= at::GPT_MAX_SOURCE;
+    if (!ok) {
+        std::printf("refused: the geometry or a source's length\n");
+        return 2;
+    }
+    const at::GptExtent e = at::gpt_extent(lens.data(), (int)lens.size(), S, H, r, max_new, block);
+    std::printf("extent %d %lld\n", e.need_len, (long long)e.need_stride);
+    for (size_t i = 0; i < lens.size(); ++i)
+        for (int k = 0; k < at::gpt_long_windows(lens[i], S, H); ++k) {
+            const at::GptWindow w = at::gpt_window(lens[i], k, S, H, r, max_new, block);
+            std::printf("window %zu %d %d %d %d %d %d\n", i, k, w.n_ids, w.P, w.budget, w.final_window ? 1 : 0, w.stream_base);
+        }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && std::strcmp(argv[1], "dry") == 0) return dry_run(argc, argv);
+    if (argc >= 2 && std::strcmp(argv[1], "extent") == 0) return extent_run(argc, argv);
     return refusals();
 }
