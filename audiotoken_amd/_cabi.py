@@ -235,6 +235,10 @@ SIGNATURES = {
     "at_fine_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "at_fine_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_fine_queue_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "at_fine_generate_queue": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
 }
 
 

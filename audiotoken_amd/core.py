@@ -340,6 +340,34 @@ class AudioToken:
             raise ValueError("to_acoustic: window= and hop= belong to long_form=True")
         if not long_form and (slots is not None or tick_tokens is not None):
             raise ValueError("to_acoustic: slots= and tick_tokens= belong to long_form=True")
+        self._gpt()
+        if long_form:
+            return self.semantic_decoder.to_acoustic_long(tokens, window=window, hop=hop, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
+                                                          seed=seed, uniforms=uniforms, return_logits=return_logits, slots=slots, tick_tokens=tick_tokens)
+        return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
+                                                 constrain=constrain, return_logits=return_logits)
+
+    def to_fine(self, codes, temperature: Optional[float] = 0.5, seed: int = 0, uniforms=None, return_logits: bool = False, slots: Optional[int] = None):
+        """The two coarse EnCodec code books -> all eight: stage 2 of the reference's semantic decoder (bark's ``generate_fine``) on the HIP fine
+        transformer (fine_decoder.py, DESIGN.md §18). Acoustic codes in, acoustic codes out, so every tokenizer has it. ``codes``: integer ``[2, T]``, or a
+        list of up to 64 of them of their own lengths, run as one batch. Returns a ``FineGeneration``: ``codes`` (a list of int64 ``[8, T_b]`` that
+        ``AudioToken(Tokenizers.acoustic, num_codebooks=8).decode`` takes) and, with ``return_logits``, the logits and ids of every window and pass.
+        ``temperature=None`` takes the argmax; any number samples (1.0 too, where HF takes the argmax) with the draws ``uniforms`` (float32
+        ``[B, n_max, 6, W]``) or, from ``seed``, ``np.random.Generator(np.random.Philox(seed)).random(...)`` of that shape. Weights: the constructor's
+        ``fine_weights=`` (a checkpoint path or a ``{name: array}`` dict), else ``$AUDIOTOKEN_FINE_DECODER_WEIGHTS``, else the seeded synthetic model.
+        With ``slots=`` (1 to 64) the call is the window queue and takes 1 to 4096 rows: each row starts when a work array is free and
+        leaves after its last window, so a long row does not hold short ones back. ``uniforms`` is then a list of per-row float32 ``[n_b, 6, W]``; from
+        ``seed`` row b draws ``np.random.Generator(np.random.Philox(key=[seed, b])).random((n_b, 6, W), float32)``, whatever the other rows are. A row's
+        codes are those of the row alone with the same draws; the result also carries ``passes`` and ``placement``."""
+        from .fine_decoder import MAX_SLOTS, _as_rows
+        rows = _as_rows(codes)   # a malformed input is refused before any model is built
+        if slots is not None:
+            if not (isinstance(slots, (int, np.integer)) and 1 <= slots <= MAX_SLOTS):
+                raise ValueError(f"to_fine: slots must be 1 to {MAX_SLOTS}, got {slots!r}")
+            return self._fine().generate_queue(rows, slots=int(slots), temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
+        return self._fine().generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
+
+    def _gpt(self):
         if getattr(self, "semantic_decoder", None) is None:
             from .configs import HubertDecoderConfig, Wav2VecBertDecoderConfig
             from .semantic_decoder import SemanticToAcoustic
@@ -348,23 +376,13 @@ class AudioToken:
             if w is None and cfg.weights is None:
                 logger.warning("to_acoustic: no decoder_weights given; using the seeded synthetic GPT")
             self.semantic_decoder = SemanticToAcoustic(cfg, device=self.device, weights=w)
-        if long_form:
-            return self.semantic_decoder.to_acoustic_long(tokens, window=window, hop=hop, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
-                                                          seed=seed, uniforms=uniforms, return_logits=return_logits, slots=slots, tick_tokens=tick_tokens)
-        return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
-                                                 constrain=constrain, return_logits=return_logits)
+        return self.semantic_decoder
 
-    def to_fine(self, codes, temperature: Optional[float] = 0.5, seed: int = 0, uniforms=None, return_logits: bool = False):
-        """The two coarse EnCodec code books -> all eight: stage 2 of the reference's semantic decoder (bark's ``generate_fine``) on the HIP fine
-        transformer (fine_decoder.py, DESIGN.md §18). Acoustic codes in, acoustic codes out, so every tokenizer has it. ``codes``: integer ``[2, T]``, or a
-        list of up to 64 of them of their own lengths, run as one batch. Returns a ``FineGeneration``: ``codes`` (a list of int64 ``[8, T_b]`` that
-        ``AudioToken(Tokenizers.acoustic, num_codebooks=8).decode`` takes) and, with ``return_logits``, the logits and ids of every window and pass.
-        ``temperature=None`` takes the argmax; any number samples (1.0 too, where HF takes the argmax) with the draws ``uniforms`` (float32
-        ``[B, n_max, 6, W]``) or, from ``seed``, ``np.random.Generator(np.random.Philox(seed)).random(...)`` of that shape. Weights: the constructor's
-        ``fine_weights=`` (a checkpoint path or a ``{name: array}`` dict), else ``$AUDIOTOKEN_FINE_DECODER_WEIGHTS``, else the seeded synthetic model."""
-        from .fine_decoder import _as_rows
-        rows = _as_rows(codes)   # a malformed input is refused before any model is built
-        return self._fine().generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
+    def _fine_audio(self):
+        """The acoustic tokenizer at 8 code books that decodes what ``to_fine`` produced."""
+        if getattr(self, "fine_audio", None) is None:
+            self.fine_audio = AudioToken(Tokenizers.acoustic, device=self.device, num_codebooks=8, weights=self.kwargs.get("acoustic_weights"))
+        return self.fine_audio
 
     def _fine(self):
         if getattr(self, "fine_decoder", None) is None:
@@ -399,10 +417,66 @@ class AudioToken:
             fine = self.to_fine(coarse.codes, temperature=fine_temperature, seed=seed, uniforms=fine_uniforms)
         else:
             fine = self._to_fine_in_groups(coarse.codes, fine_temperature, seed, fine_uniforms)
-        if getattr(self, "fine_audio", None) is None:
-            self.fine_audio = AudioToken(Tokenizers.acoustic, device=self.device, num_codebooks=8, weights=self.kwargs.get("acoustic_weights"))
-        audio = [self.fine_audio.decode(c.unsqueeze(0)) for c in fine.codes]
+        audio = [self._fine_audio().decode(c.unsqueeze(0)) for c in fine.codes]
         return audio, coarse, fine
+
+    def to_audio_batch_files(self, batch_size: int, outdir: os.PathLike, token_files: Optional[List[os.PathLike]] = None,
+                             token_dir: Optional[Union[os.PathLike, Path]] = None, chunk_size: Optional[int] = None, num_workers: int = 12,
+                             audio_format: str = "wav", rescale: bool = False, stream: bool = False, seed: int = 0, temperature: float = 0.8,
+                             top_k: int = 100, fine_temperature: Optional[float] = 0.5, max_new_tokens: int = 1024, window: Optional[int] = None,
+                             hop: Optional[int] = None, slots: int = 64, fine_slots: int = 64, round_files: int = 1024,
+                             codes_dir: Optional[os.PathLike] = None, **kwargs) -> None:
+        """The way back from a semantic ``encode_batch_files``: ``.npy`` files of semantic ids -> audio files (semantic_files.py). Semantic
+        tokenizers only (``decode_batch_files`` stays the acoustic tokenizer's, and keeps raising here). Inputs, output names, overwriting, the skipping of
+        a second input that maps to one output name, sharding under ``torch.distributed``, ``audio_format`` ("wav" / "flac", checked before any model is
+        built), ``rescale``, ``stream``, ``run_summary`` / ``run_timings`` and ``skipped_files`` are ``decode_batch_files``'. An input is int16 / int64
+        ``[T]``, ``[1, T]`` or ``[1, 1, T]``; one that is unreadable, of another dtype or rank, empty, longer than 65536 ids, holds an id outside the
+        semantic vocabulary, or whose stage 1 produced no whole frame is skipped with its reason and the run goes on.
+        The valid sources are taken ``round_files`` (1 to 4096) at a time: ``to_acoustic(long_form=True, slots=slots, window=, hop=, ...)`` (the GPT's
+        generation queue), then ``to_fine(slots=fine_slots)`` (the fine stage's window queue, rows handed over longest first), and each file's ``[8, T]``
+        codes go through the decode run of ``decode_batch_files`` at 8 code books: ``chunk_size=None`` decodes a file as one clip, ``stream=True`` pushes
+        it through the decode stream pool. A round is generated when the decode side needs it: one round's ids and one decode batch's audio are held.
+        ``codes_dir=`` also writes each file's codes as ``<same relative stem>.npy`` (int16 ``[8, T]``), which ``decode_batch_files`` reads.
+        A file's draws (``semantic_files.file_draws``) come from ``np.random.Generator(np.random.Philox(key=[seed, fnv1a64(stem)]))``, ``stem`` its output
+        path relative to ``outdir`` without the extension, in posix form: first the stage 1 draws of the source's own stream capacity, then its
+        ``[n, 6, W]`` fine draws, so they do not depend on the other files, the round size or the ranks. ``run_summary`` gains ``rounds``, ``gpt_ticks``,
+        ``fine_passes`` and ``generated_frames``; ``run_timings`` gains ``gpt_s`` and ``fine_s`` (both inside ``stage_s``)."""
+        from . import semantic_files as SF
+        from . import writer as Wr
+        if audio_format not in Wr.AUDIO_FORMATS:
+            raise ValueError(f"audio_format must be one of {Wr.AUDIO_FORMATS}, got {audio_format!r}")
+        if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
+            raise ValueError(f"to_audio_batch_files maps files of semantic ids to audio files; {self.tokenizer_name} has no semantic ids "
+                             "(decode_batch_files is its way back)")
+        assert token_files or token_dir, "Either token_files or token_dir must be provided"
+        assert not (token_files and token_dir), "Provide either token_files or token_dir, not both"
+        for name, value, most in (("slots", slots, 64), ("fine_slots", fine_slots, 64), ("round_files", round_files, 4096)):
+            if not (isinstance(value, (int, np.integer)) and 1 <= value <= most):
+                raise ValueError(f"to_audio_batch_files: {name} must be 1 to {most}, got {value!r}")
+        known = {"shard_across_ranks", "device_writer", "max_held_bytes"}
+        decoder_kwargs = {k: v for k, v in kwargs.items() if k not in known}
+        stages = SF.Stages(self, seed, temperature, top_k, fine_temperature, max_new_tokens, window, hop, slots, fine_slots)
+        acoustic = self._fine_audio()
+        acoustic.load_decoder(**decoder_kwargs)
+        self.skipped_files = []
+        outdir = sanitize_path(outdir)
+        files = self._input_files(token_files, token_dir, exts=(".npy",))
+        files = runs.shard_if_distributed(self, files, kwargs.get("shard_across_ranks", True))
+        log = runs.RunLog(self, "to_audio_batch_files", "audio")
+        inputs, taken = [], {}
+        for f in files:
+            out = Wr.output_path(f, outdir, None if token_files else str(token_dir), audio_format)
+            if out in taken:
+                log.skipped(f, f"duplicate output name: {out} is already written from {taken[out]}")
+                continue
+            taken[out] = f
+            inputs.append((f, out))
+        on_gpu = torch.device(self.device).type == "cuda"
+        cfg = acoustic.model_config
+        SF.to_audio_files(self, acoustic.decoder, inputs, outdir, stages, self._gpt().config.SEMANTIC_VOCAB_SIZE, int(round_files), codes_dir,
+                          int(batch_size), chunk_size, int(num_workers), bool(rescale), bool(kwargs.get("device_writer", on_gpu)),
+                          int(kwargs.get("max_held_bytes", Wr.DEFAULT_MAX_HELD_BYTES)), cfg.model_sample_rate, cfg.model_token_rate, audio_format,
+                          bool(stream), log=log)
 
     def _to_fine_in_groups(self, codes, temperature, seed, uniforms, group: int = 64):
         """``to_fine`` over more than 64 rows: groups of at most ``group`` in order, one ``FineGeneration`` over all of them. A group's draws are its rows of

@@ -1,6 +1,7 @@
 // The handle of the fine stage (fine.hip), declared apart from its code so that the stand-alone argument check (tools/fine_args.hip) can
 // build a finalized handle with no device behind it: every entry point validates against the handle's dimensions alone before it touches one.
 #pragma once
+#include <cstdint>
 #include <map>
 #include <string>
 #include <vector>
@@ -33,6 +34,63 @@ inline int fine_windows(int T, int W) {
     const int H = W / 2;
     return (T > W ? (T - W + H - 1) / H : 0) + 1;
 }
+
+constexpr int FINE_MAX_QUEUE = 4096;   // rows of one at_fine_generate_queue call
+
+// ---- the window queue's schedule: pure host code, known from the lengths alone ------------------------------------------------
+// Rows take empty slots in the caller's order; a slot runs its row's windows 0 .. n - 1 in consecutive passes; a slot whose row ran its last window takes
+// the next waiting row in the next pass. Pass p is the current window of every occupied slot, in slot order.
+struct FineQueuePass {
+    int n = 0;                                                 // windows of the pass
+    int slot[FINE_MAX_B], row[FINE_MAX_B], k[FINE_MAX_B];      // of each window
+    int n_admit = 0, admit[FINE_MAX_B];                        // indices into the window list: windows whose row enters its slot in this pass (k = 0)
+    int n_retire = 0, retire[FINE_MAX_B];                      // indices into the window list: windows that are their row's last
+};
+
+class FineQueueSchedule {
+public:
+    // lens: n_rows lengths, each 1 to FINE_MAX_T; 1 <= slots <= FINE_MAX_B; the caller has checked both
+    FineQueueSchedule(const int32_t* lens, int n_rows, int W, int slots)
+        : n_rows_(n_rows), slots_(slots), windows_(n_rows), placement_(3 * (size_t)n_rows, -1) {
+        for (int b = 0; b < n_rows; ++b) windows_[b] = fine_windows(lens[b], W);
+        for (int j = 0; j < FINE_MAX_B; ++j) holds_[j] = -1;
+    }
+    // the next pass; false once every row has retired
+    bool next(FineQueuePass* p) {
+        *p = FineQueuePass();
+        for (int j = 0; j < slots_; ++j) {
+            if (holds_[j] < 0 && waiting_ < n_rows_) {
+                holds_[j] = waiting_++;
+                at_[j] = 0;
+                placement_[3 * (size_t)holds_[j]] = j;
+                placement_[3 * (size_t)holds_[j] + 1] = passes_;
+                p->admit[p->n_admit++] = p->n;
+            }
+            if (holds_[j] < 0) continue;
+            const int i = p->n++, b = holds_[j];
+            p->slot[i] = j;
+            p->row[i] = b;
+            p->k[i] = at_[j]++;
+            if (at_[j] == windows_[b]) {
+                p->retire[p->n_retire++] = i;
+                placement_[3 * (size_t)b + 2] = passes_;
+                holds_[j] = -1;
+            }
+        }
+        if (p->n == 0) return false;
+        ++passes_;
+        return true;
+    }
+    int passes() const { return passes_; }
+    const std::vector<int32_t>& placement() const { return placement_; }   // [n_rows][3]: slot, first pass, last pass
+    const std::vector<int>& windows() const { return windows_; }
+
+private:
+    int n_rows_, slots_, waiting_ = 0, passes_ = 0;
+    int holds_[FINE_MAX_B], at_[FINE_MAX_B] = {};
+    std::vector<int> windows_;
+    std::vector<int32_t> placement_;
+};
 
 }  // namespace at
 

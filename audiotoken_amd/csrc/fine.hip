@@ -3,12 +3,13 @@
 // without bias, E / 64 heads of 64, attention over the whole window without a mask, erf-GELU MLP), a final LayerNorm and 7 heads.
 // The matrix products, the attention and the LayerNorm are the library's own fp32 launchers (launch_gemm, launch_relpos_attention with its arithmetic set to
 // fp32, launch_layernorm). New here, all fp32:
-//   fine_init_kernel     the rows' work arrays [L][8]: the coarse codes, 1024 everywhere else
+//   fine_init_kernel     the work arrays [L][8] of the rows that enter a slot: the coarse codes, 1024 everywhere else
 //   fine_embed_kernel    x[t] = sum_{i <= c} wtes[i][cell[t][i]] + wpe[t], read straight from the work arrays at each row's window (no batch copy of the ids)
 //   fine_gather_kernel   the rows the head needs (positions >= rel of every window of the pass), where a window has rel > 0
 //   fine_sample_kernel   one wave per position over its 1024 logits: the argmax or the inverse-CDF draw, written straight into the work array
-//   fine_finish_kernel   the first T positions as [8][T]
+//   fine_finish_kernel   the first T positions of the rows that leave a slot, as [8][T]
 // A call enqueues every window of every row without looking at the device: the host knows the schedule from the lengths. No float is added atomically.
+// Both generators are one loop (run_passes) over the passes of FineQueueSchedule (fine.h): at_fine_generate is the queue with a slot per row.
 #include <cmath>
 #include <cstring>
 
@@ -51,14 +52,22 @@ FineState carve_state(void* base, int B, int max_T, int W, int E) {
 }
 
 // ---- the schedule of one pass, by value into the kernels ------------------------------------------------------------------------------------
+// A pass may hold windows of different rows AND of different k (the window queue), so everything a kernel needs of a window travels with it.
 struct FinePass {
     int n;                             // windows in the batch
-    int row[FINE_MAX_B];               // the call's row each belongs to
-    int start[FINE_MAX_B];             // first position of the window in the row's work array
+    int cell0[FINE_MAX_B];             // the cell, in the state's work arrays, of the window's first position: the slot's base + start
+    int draw[FINE_MAX_B];              // the window's draw cell: uniforms, logits_out and window_ids hold [6][W] per cell
     int rel[FINE_MAX_B];               // first buffer position that is predicted
     int head_off[FINE_MAX_B + 1];      // the window's predicted positions are head rows [head_off[j], head_off[j + 1])
 };
-struct RowLens { int T[FINE_MAX_B]; };
+// the rows that enter (fine_init_kernel) or leave (fine_finish_kernel) their slots in one pass: at most one per slot, so they go by value
+struct FineRows {
+    int n;
+    int T[FINE_MAX_B];                 // frames of the row
+    int cell0[FINE_MAX_B];             // the slot's base, in cells of the state's work arrays
+    int stride[FINE_MAX_B];            // distance between the row's planes in coarse_dev / out_dev
+    long long at[FINE_MAX_B];          // the row's first element in coarse_dev / out_dev
+};
 struct FineTables { const float* t[FINE_CODES]; };
 
 __device__ __forceinline__ int slot_of(const FinePass& p, int r) {
@@ -67,32 +76,35 @@ __device__ __forceinline__ int slot_of(const FinePass& p, int r) {
     return j;
 }
 
-// start of a call: thread i = (row, position). A coarse code outside [0, 1024) is clamped and reported in bit 0 of *status.
-__global__ __launch_bounds__(256) void fine_init_kernel(RowLens lens, int B, int Lmax, int n_ones, const int* coarse, int t_stride, int* work, float* ones, int* status) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)B * Lmax) return;
-    if (i < (size_t)n_ones) ones[i] = 1.0f;
-    const int b = (int)(i / Lmax), t = (int)(i % Lmax);
+// A row enters its slot: blockIdx.y = the row of the list, thread = position. Every one of the row's max(T, W) cells is rewritten (the coarse codes, 1024
+// everywhere else), which is all a window of the row can read: whatever the slot's previous row left behind lies past them or is overwritten.
+// A coarse code outside [0, 1024) is clamped and reported in bit 0 of *status. ones: the attention's key mask, written by the call's first launch.
+__global__ __launch_bounds__(256) void fine_init_kernel(FineRows rows, int W, const int* coarse, int* work, float* ones, int* status) {
+    const int j = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int T = rows.T[j];
+    if (t >= max(T, W)) return;
+    if (ones && t < W) ones[(size_t)j * W + t] = 1.0f;
     int c0 = FINE_VOCAB, c1 = FINE_VOCAB;
-    if (t < lens.T[b]) {
-        c0 = coarse[((size_t)b * 2 + 0) * t_stride + t];
-        c1 = coarse[((size_t)b * 2 + 1) * t_stride + t];
+    if (t < T) {
+        const int* src = coarse + rows.at[j];
+        c0 = src[t];
+        c1 = src[(size_t)rows.stride[j] + t];
         if (c0 < 0 || c0 >= FINE_VOCAB || c1 < 0 || c1 >= FINE_VOCAB) {
             if (status) atomicOr(status, 1);
             c0 = min(max(c0, 0), FINE_VOCAB - 1);
             c1 = min(max(c1, 0), FINE_VOCAB - 1);
         }
     }
-    int4* cell = reinterpret_cast<int4*>(work + i * FINE_CODES);
+    int4* cell = reinterpret_cast<int4*>(work + ((size_t)rows.cell0[j] + t) * FINE_CODES);
     cell[0] = make_int4(c0, c1, FINE_VOCAB, FINE_VOCAB);
     cell[1] = make_int4(FINE_VOCAB, FINE_VOCAB, FINE_VOCAB, FINE_VOCAB);
 }
 
 // Token i = (window i / W of the pass, buffer position i % W), E / 4 threads of 16 bytes each. Tables 0 to c in that order, the position last.
-__global__ __launch_bounds__(256) void fine_embed_kernel(FinePass p, FineTables tab, const float* wpe, const int* work, int Lmax, int W, int E, int c, float* x) {
+__global__ __launch_bounds__(256) void fine_embed_kernel(FinePass p, FineTables tab, const float* wpe, const int* work, int W, int E, int c, float* x) {
     const int i = blockIdx.x, tid = threadIdx.x;
     const int j = i / W, t = i % W;
-    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)p.row[j] * Lmax + p.start[j] + t) * FINE_CODES);
+    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)p.cell0[j] + t) * FINE_CODES);
     const int4 lo = cell[0], hi = cell[1];
     const int ids[FINE_CODES] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
     float4 a = reinterpret_cast<const float4*>(tab.t[0] + (size_t)ids[0] * E)[tid];
@@ -118,13 +130,13 @@ __global__ __launch_bounds__(256) void fine_gather_kernel(FinePass p, int W, int
 struct FineSampleArgs {
     const float* logits;      // [head rows][1024]
     int total;                // head rows of the pass
-    int W, Lmax, k, c, n_max;
+    int W, c;
     int greedy;
     float temperature;
-    const float* uniforms;    // [B][n_max][6][W]
+    const float* uniforms;    // [draw cells][6][W]
     int* work;
-    float* logits_out;        // nullable [B][n_max][6][W][1024]
-    int* ids_out;             // nullable [B][n_max][6][W]
+    float* logits_out;        // nullable [draw cells][6][W][1024]
+    int* ids_out;             // nullable [draw cells][6][W]
 };
 
 // One wave per head row; lane l owns ids [16 l, 16 l + 16). The rule: zt = z / temperature, m = max zt, p = expf(zt - m); the running sum of
@@ -134,7 +146,7 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void fine_sample_kernel(FinePass
     const int lane = threadIdx.x & 63, r = blockIdx.x * SAMPLE_WAVES + (threadIdx.x >> 6);
     if (r >= a.total) return;   // uniform over the wave
     const int j = slot_of(p, r);
-    const int t = p.rel[j] + (r - p.head_off[j]), b = p.row[j];
+    const int t = p.rel[j] + (r - p.head_off[j]);
     const float4* zr = reinterpret_cast<const float4*>(a.logits + (size_t)r * FINE_VOCAB) + 4 * lane;
     float z[16];
 #pragma unroll
@@ -142,7 +154,7 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void fine_sample_kernel(FinePass
         const float4 v = zr[q];
         z[4 * q] = v.x; z[4 * q + 1] = v.y; z[4 * q + 2] = v.z; z[4 * q + 3] = v.w;
     }
-    const size_t cell = (((size_t)b * a.n_max + a.k) * FINE_PASSES + (a.c - FINE_COARSE)) * a.W + t;
+    const size_t cell = ((size_t)p.draw[j] * FINE_PASSES + (a.c - FINE_COARSE)) * a.W + t;
     if (a.logits_out) {
         float4* dst = reinterpret_cast<float4*>(a.logits_out + cell * FINE_VOCAB) + 4 * lane;
 #pragma unroll
@@ -200,22 +212,21 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void fine_sample_kernel(FinePass
         tok = first < FINE_VOCAB ? first : max(top, 0);
     }
     if (lane == 0) {
-        a.work[((size_t)b * a.Lmax + p.start[j] + t) * FINE_CODES + a.c] = tok;
+        a.work[((size_t)p.cell0[j] + t) * FINE_CODES + a.c] = tok;
         if (a.ids_out) a.ids_out[cell] = tok;
     }
 }
 
-// out[b][ch][t] = work[b][t][ch] for t < T_b; the rest of out is left as it was
-__global__ __launch_bounds__(256) void fine_finish_kernel(RowLens lens, int B, int Lmax, int max_T, const int* work, int* out, int t_stride) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)B * max_T) return;
-    const int b = (int)(i / max_T), t = (int)(i % max_T);
-    if (t >= lens.T[b]) return;
-    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)b * Lmax + t) * FINE_CODES);
+// A row leaves its slot: out[ch][t] = work[t][ch] for t < T, at the row's place in out; the rest of out is left as it was
+__global__ __launch_bounds__(256) void fine_finish_kernel(FineRows rows, const int* work, int* out) {
+    const int j = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= rows.T[j]) return;
+    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)rows.cell0[j] + t) * FINE_CODES);
     const int4 lo = cell[0], hi = cell[1];
     const int ids[FINE_CODES] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    int* dst = out + rows.at[j];
 #pragma unroll
-    for (int ch = 0; ch < FINE_CODES; ++ch) out[((size_t)b * FINE_CODES + ch) * t_stride + t] = ids[ch];
+    for (int ch = 0; ch < FINE_CODES; ++ch) dst[(size_t)ch * rows.stride[j] + t] = ids[ch];
 }
 
 // ---- the forward of one pass for code book c: logits of the pass's head rows ----------------------------------------------------------------
@@ -223,7 +234,7 @@ int run_forward(const at_fine* h, const FineState& s, const FinePass& p, int c, 
     const int W = h->block, E = h->embd, M = p.n * W, total = p.head_off[p.n];
     FineTables tab;
     for (int i = 0; i < FINE_CODES; ++i) tab.t[i] = h->wtes[i];
-    hipLaunchKernelGGL(fine_embed_kernel, dim3(M), dim3(E / 4), 0, stream, p, tab, h->wpe, s.work, s.Lmax, W, E, c, s.x);
+    hipLaunchKernelGGL(fine_embed_kernel, dim3(M), dim3(E / 4), 0, stream, p, tab, h->wpe, s.work, W, E, c, s.x);
     AT_CHECK_HIP(hipGetLastError());
     auto dense = [&](const float* X, int rows, int K, const float* Wt, const float* bias, int N, float* C, const float* Res, int epi) {
         GemmArgs g;
@@ -280,6 +291,88 @@ void release(at_fine* h) {
 }
 
 const char* const kLinears[4] = {".attn.c_attn", ".attn.c_proj", ".mlp.c_fc", ".mlp.c_proj"};
+
+// ---- the passes of a call: the one loop behind at_fine_generate and at_fine_generate_queue ---------------------------------------------------------
+// Where a row's data lies: its first element in coarse_dev and in out_dev, the distance between its planes, and the draw cell of its window 0.
+struct FineRowMap {
+    long long src, dst;
+    int stride, draw0;
+};
+struct FineCall {
+    const int32_t* coarse;
+    int32_t* out;
+    float temperature;
+    int greedy;
+    const float* uniforms;
+    float* logits_out;
+    int32_t* window_ids;
+    int32_t *trace, *n_passes, *placement;   // nullable HOST arrays
+    int trace_cap;
+    int32_t* status;
+};
+
+int launch_rows(bool init, const FineRows& rows, int span, int W, const FineState& s, const FineCall& c, bool first, hipStream_t stream) {
+    if (rows.n == 0) return 0;   // nothing enters or leaves in this pass
+    const dim3 grid((unsigned)((span + 255) / 256), (unsigned)rows.n);
+    if (init) hipLaunchKernelGGL(fine_init_kernel, grid, dim3(256), 0, stream, rows, W, c.coarse, s.work, first ? s.ones : nullptr, c.status);
+    else hipLaunchKernelGGL(fine_finish_kernel, grid, dim3(256), 0, stream, rows, s.work, c.out);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// lens and map are indexed by row; everything has been checked. Slot j's work array is cells [j Lmax, (j + 1) Lmax) of the state.
+int run_passes(const at_fine* h, const FineState& s, const int32_t* lens, int n_rows, int slots, const FineRowMap* map, const FineCall& c, hipStream_t stream) {
+    const int W = h->block, H = W / 2;
+    FineSampleArgs sa{};
+    sa.logits = s.logits; sa.W = W; sa.greedy = c.greedy; sa.temperature = c.greedy ? 1.0f : c.temperature;
+    sa.uniforms = c.uniforms; sa.work = s.work; sa.logits_out = c.logits_out; sa.ids_out = c.window_ids;
+    FineQueueSchedule schedule(lens, n_rows, W, slots);
+    FineQueuePass q;
+    while (schedule.next(&q)) {
+        const int at = schedule.passes() - 1;
+        if (c.trace && at < c.trace_cap) {
+            c.trace[3 * at] = q.n;
+            c.trace[3 * at + 1] = q.n_admit;
+            c.trace[3 * at + 2] = q.n_retire;
+        }
+        FinePass p{};
+        FineRows in{}, outr{};
+        int span_in = 0, span_out = 0;
+        auto add = [&](FineRows& rows, int& span, int i, bool init) {
+            const int b = q.row[i], j = rows.n++, T = lens[b];
+            rows.T[j] = T;
+            rows.cell0[j] = q.slot[i] * s.Lmax;
+            rows.stride[j] = map[b].stride;
+            rows.at[j] = init ? map[b].src : map[b].dst;
+            const int cells = init && T < W ? W : T;
+            span = cells > span ? cells : span;
+        };
+        for (int a = 0; a < q.n_admit; ++a) add(in, span_in, q.admit[a], true);
+        for (int a = 0; a < q.n_retire; ++a) add(outr, span_out, q.retire[a], false);
+        for (int i = 0; i < q.n; ++i) {
+            const int b = q.row[i], k = q.k[i];
+            const int L = lens[b] > W ? lens[b] : W;
+            const int start = k * H < L - W ? k * H : L - W, fill = k * H < L - H ? k * H : L - H;
+            p.cell0[i] = q.slot[i] * s.Lmax + start;
+            p.draw[i] = map[b].draw0 + k;
+            p.rel[i] = fill - start;
+            p.head_off[i + 1] = p.head_off[i] + W - p.rel[i];
+        }
+        p.n = q.n;
+        if (int rc = launch_rows(true, in, span_in, W, s, c, at == 0, stream)) return rc;
+        sa.total = p.head_off[p.n];
+        for (int cb = FINE_COARSE; cb < FINE_CODES; ++cb) {
+            if (int rc = run_forward(h, s, p, cb, stream)) return rc;
+            sa.c = cb;
+            hipLaunchKernelGGL(fine_sample_kernel, dim3((sa.total + SAMPLE_WAVES - 1) / SAMPLE_WAVES), dim3(64 * SAMPLE_WAVES), 0, stream, p, sa);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+        if (int rc = launch_rows(false, outr, span_out, W, s, c, false, stream)) return rc;
+    }
+    if (c.n_passes) *c.n_passes = schedule.passes();
+    if (c.placement) std::memcpy(c.placement, schedule.placement().data(), 3 * (size_t)n_rows * sizeof(int32_t));
+    return 0;
+}
 
 }  // namespace
 
@@ -389,6 +482,15 @@ size_t at_fine_state_bytes(const at_fine_t* h, int B, int max_T) {
     return carve_state(nullptr, B, max_T, h->block, h->embd).bytes;
 }
 
+
+size_t at_fine_queue_state_bytes(const at_fine_t* h, int slots, int max_T) {
+    if (!(h && h->finalized)) { set_error("at_fine_queue_state_bytes: the model is not finalized"); return 0; }
+    if (!(slots >= 1 && slots <= FINE_MAX_B)) { set_error("at_fine_queue_state_bytes: slots must be 1 to 64"); return 0; }
+    if (!(max_T >= 1 && max_T <= FINE_MAX_T)) { set_error("at_fine_queue_state_bytes: max_T must be 1 to 262144"); return 0; }
+    return carve_state(nullptr, slots, max_T, h->block, h->embd).bytes;
+}
+
+// The queue with slots = B: every row is admitted in pass 0, and pass k is window k of every row that has one, in row order.
 int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
                      const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
                      int max_T, at_stream_t stream_, int32_t* status_dev) {
@@ -401,56 +503,67 @@ int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, cons
     AT_REQUIRE(state_dev != nullptr, "null state");
     AT_REQUIRE(max_T >= 1 && max_T <= FINE_MAX_T, "max_T must be 1 to 262144");
     AT_REQUIRE(t_stride >= 1 && t_stride <= FINE_MAX_T, "t_stride must be 1 to 262144");
-    const int W = h->block, H = W / 2;
-    RowLens rl{};
-    int n_b[FINE_MAX_B], n_most = 0;
+    const int W = h->block;
+    FineRowMap map[FINE_MAX_B];
+    int n_most = 0;
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 1 || lens[b] > t_stride || lens[b] > max_T) {
             set_error("at_fine_generate: the length of row " + std::to_string(b) + " must be 1 to min(t_stride, max_T)");
             return -1;
         }
-        rl.T[b] = lens[b];
-        n_b[b] = fine_windows(lens[b], W);
-        n_most = n_b[b] > n_most ? n_b[b] : n_most;
+        const int n = fine_windows(lens[b], W);
+        n_most = n > n_most ? n : n_most;
     }
     AT_REQUIRE(n_max >= n_most, "n_max must hold the windows of the longest row: at_fine_num_windows(h, T)");
+    AT_REQUIRE((long long)B * n_max <= INT32_MAX, "B * n_max must fit 31 bits");
+    for (int b = 0; b < B; ++b) map[b] = FineRowMap{(long long)b * 2 * t_stride, (long long)b * FINE_CODES * t_stride, t_stride, b * n_max};
     const FineState s = carve_state(state_dev, B, max_T, W, h->embd);
     AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_state_bytes(h, B, max_T)");
     // ---- nothing above touched the device
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    hipStream_t stream = (hipStream_t)stream_;
-    const size_t cells = (size_t)B * s.Lmax;
-    hipLaunchKernelGGL(fine_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, rl, B, s.Lmax, B * W, coarse_dev, t_stride, s.work, s.ones,
-                       status_dev);
-    AT_CHECK_HIP(hipGetLastError());
-    FineSampleArgs sa{};
-    sa.logits = s.logits; sa.W = W; sa.Lmax = s.Lmax; sa.n_max = n_max; sa.greedy = greedy; sa.temperature = greedy ? 1.0f : temperature;
-    sa.uniforms = uniforms_dev; sa.work = s.work; sa.logits_out = logits_out_dev; sa.ids_out = window_ids_dev;
-    for (int k = 0; k < n_most; ++k) {
-        FinePass p{};
-        for (int b = 0; b < B; ++b) {
-            if (n_b[b] <= k) continue;
-            const int L = rl.T[b] > W ? rl.T[b] : W, j = p.n++;
-            const int start = k * H < L - W ? k * H : L - W, fill = k * H < L - H ? k * H : L - H;
-            p.row[j] = b;
-            p.start[j] = start;
-            p.rel[j] = fill - start;
-            p.head_off[j + 1] = p.head_off[j] + W - p.rel[j];
+    FineCall c{};
+    c.coarse = coarse_dev; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
+    c.logits_out = logits_out_dev; c.window_ids = window_ids_dev; c.status = status_dev;
+    return run_passes(h, s, lens, B, B, map, c, (hipStream_t)stream_);
+}
+
+int at_fine_generate_queue(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy, const float* uniforms_dev,
+                           int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T, int slots,
+                           int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized, "the model is not finalized");
+    AT_REQUIRE(n_rows >= 1 && n_rows <= FINE_MAX_QUEUE, "n_rows must be 1 to 4096");
+    AT_REQUIRE(slots >= 1 && slots <= FINE_MAX_B, "slots must be 1 to 64");
+    AT_REQUIRE(coarse_dev && lens && out_dev, "null pointer");
+    AT_REQUIRE(greedy == 0 || greedy == 1, "greedy must be 0 or 1");
+    AT_REQUIRE(greedy || uniforms_dev, "null pointer: sampling needs the uniforms");
+    AT_REQUIRE(greedy || (std::isfinite(temperature) && temperature > 0.0f), "temperature must be a positive finite number");
+    AT_REQUIRE(state_dev != nullptr, "null state");
+    AT_REQUIRE(max_T >= 1 && max_T <= FINE_MAX_T, "max_T must be 1 to 262144");
+    AT_REQUIRE(trace_cap >= 0 && (trace != nullptr || trace_cap == 0), "trace_cap must be 0 without a trace, and never negative");
+    const int W = h->block;
+    std::vector<FineRowMap> map((size_t)n_rows);
+    long long off = 0, woff = 0;   // frames and windows of the rows before
+    for (int b = 0; b < n_rows; ++b) {
+        if (lens[b] < 1 || lens[b] > max_T) {
+            set_error("at_fine_generate_queue: the length of row " + std::to_string(b) + " must be 1 to max_T");
+            return -1;
         }
-        sa.k = k;
-        sa.total = p.head_off[p.n];
-        for (int c = FINE_COARSE; c < FINE_CODES; ++c) {
-            if (int rc = run_forward(h, s, p, c, stream)) return rc;
-            sa.c = c;
-            hipLaunchKernelGGL(fine_sample_kernel, dim3((sa.total + SAMPLE_WAVES - 1) / SAMPLE_WAVES), dim3(64 * SAMPLE_WAVES), 0, stream, p, sa);
-            AT_CHECK_HIP(hipGetLastError());
-        }
+        map[b] = FineRowMap{2 * off, FINE_CODES * off, lens[b], (int)woff};
+        off += lens[b];
+        woff += fine_windows(lens[b], W);
     }
-    const size_t outs = (size_t)B * max_T;
-    hipLaunchKernelGGL(fine_finish_kernel, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, stream, rl, B, s.Lmax, max_T, s.work, out_dev, t_stride);
-    AT_CHECK_HIP(hipGetLastError());
-    return 0;
+    AT_REQUIRE(woff <= INT32_MAX, "the rows' windows must number fewer than 2^31");
+    const FineState s = carve_state(state_dev, slots, max_T, W, h->embd);
+    AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_queue_state_bytes(h, slots, max_T)");
+    // ---- nothing above touched the device
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    FineCall c{};
+    c.coarse = coarse_dev; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
+    c.logits_out = logits_out_dev; c.window_ids = window_ids_dev; c.status = status_dev;
+    c.trace = trace; c.trace_cap = trace_cap; c.n_passes = n_passes; c.placement = placement;
+    return run_passes(h, s, lens, n_rows, slots, map.data(), c, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -48,12 +48,14 @@ class DecodeRun:
     TICK_LAPS = ("stage_s", "encode_call_s", "save_s", "device_wait_s")
 
     def __init__(self, tok, inputs: Sequence[Tuple[str, str]], batch_size: int, chunk_size, num_workers: int, rescale: bool, device_writer: bool,
-                 max_held_bytes: int, sample_rate: int, token_rate: int, audio_format: str = "wav", stream: bool = False, log: Optional[RunLog] = None):
+                 max_held_bytes: int, sample_rate: int, token_rate: int, audio_format: str = "wav", stream: bool = False, log: Optional[RunLog] = None,
+                 decoder=None):
+        """``decoder``: the acoustic decoder to run when it is not ``tok``'s own (semantic_files.py: the semantic tokenizers have none)."""
         self.log = log or RunLog(tok, "decode_batch_files", "audio")     # (the caller's, when it already had inputs to skip)
         self.tok, self.inputs, self.batch_size, self.num_workers, self.rescale, self.stream = tok, inputs, batch_size, num_workers, rescale, stream
         self.max_held_bytes, self.sample_rate, self.audio_format = max_held_bytes, sample_rate, audio_format
         self.chunk_frames = chunk_frames_of(chunk_size, token_rate)
-        self.dec = dec = tok.decoder
+        self.dec = dec = decoder if decoder is not None else tok.decoder
         self.device = device = torch.device(tok.device)
         self.num_codebooks = int(getattr(getattr(dec, "_h", None), "n_codebooks", tok.num_codebooks))
         assert audio_format in AUDIO_FORMATS

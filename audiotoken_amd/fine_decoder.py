@@ -27,6 +27,8 @@ class FineGeneration:
     codes: List[torch.Tensor]                          # int64 [8, T_b]: rows 0 and 1 are the input
     logits: Optional[List[torch.Tensor]] = None        # return_logits: float32 [n_b, 6, W, 1024]; positions below a window's ``rel`` hold NaN
     window_ids: Optional[List[torch.Tensor]] = None    # return_logits: int64 [n_b, 6, W], what each pass wrote (-1 below ``rel``), overwritten ones included
+    passes: Optional[List[tuple]] = None               # the window queue: per pass (windows, rows admitted, rows retired), as the library ran them
+    placement: Optional[List[tuple]] = None            # the window queue: per row (slot, first pass, last pass)
 
 
 def fine_windows(T: int, W: int):
@@ -39,6 +41,50 @@ def fine_windows(T: int, W: int):
 
 def seeded_uniforms(seed: int, batch: int, n_max: int, block: int) -> np.ndarray:
     return np.random.Generator(np.random.Philox(seed)).random((batch, n_max, N_PASSES, block), dtype=np.float32)
+
+
+def row_uniforms(seed: int, row: int, n_windows: int, block: int) -> np.ndarray:
+    """The queue's draws of row ``row`` from ``seed``: float32 ``[n_windows, 6, block]`` from a Philox stream keyed by (seed, row), so that a row's draws
+    do not depend on the other rows' lengths."""
+    return np.random.Generator(np.random.Philox(key=[seed, row])).random((n_windows, N_PASSES, block), dtype=np.float32)
+
+
+MAX_QUEUE_ROWS, MAX_SLOTS = 4096, 64
+
+
+def fine_queue_passes(lens, W: int, slots: int):
+    """The window queue's schedule (the twin of csrc/fine.h ``FineQueueSchedule``) for rows of ``lens`` frames through ``slots`` work
+    arrays: ``(passes, placement)``. ``passes[p]`` lists the ``(slot, row, k)`` of every window of pass p in slot order; ``placement[b]`` is row b's
+    ``(slot, first pass, last pass)``. Rows take empty slots in order; a slot runs its row's windows in consecutive passes and takes the next waiting row
+    in the pass after its row's last window."""
+    lens = [int(T) for T in lens]
+    if not 1 <= slots <= MAX_SLOTS:
+        raise ValueError(f"slots must be 1 to {MAX_SLOTS}, got {slots}")
+    if not 1 <= len(lens) <= MAX_QUEUE_ROWS:
+        raise ValueError(f"1 to {MAX_QUEUE_ROWS} rows per call, got {len(lens)}")
+    if min(lens) < 1:
+        raise ValueError("every row needs at least one frame")
+    n = [len(fine_windows(T, W)) for T in lens]
+    holds, at = [None] * slots, [0] * slots
+    waiting, passes, placement = 0, [], [None] * len(lens)
+    while True:
+        this = []
+        for j in range(slots):
+            if holds[j] is None and waiting < len(lens):
+                holds[j], at[j] = waiting, 0
+                placement[waiting] = (j, len(passes), None)
+                waiting += 1
+            if holds[j] is None:
+                continue
+            b = holds[j]
+            this.append((j, b, at[j]))
+            at[j] += 1
+            if at[j] == n[b]:
+                placement[b] = (placement[b][0], placement[b][1], len(passes))
+                holds[j] = None
+        if not this:
+            return passes, placement
+        passes.append(this)
 
 
 def _as_rows(codes) -> List[np.ndarray]:
@@ -132,4 +178,69 @@ class CoarseToFine(LibHandle):
         if return_logits:
             result.logits = [d_logits[b, :n[b]].cpu() for b in range(B)]
             result.window_ids = [d_ids[b, :n[b]].cpu().to(torch.int64) for b in range(B)]
+        return result
+
+    def generate_queue(self, codes, slots: int = 64, temperature: Optional[float] = 0.5, seed: int = 0, uniforms: Optional[List[np.ndarray]] = None,
+                       return_logits: bool = False) -> FineGeneration:
+        """The window queue: 1 to 4096 rows through ``slots`` (1 to 64) work arrays, each row starting when a slot is free and leaving
+        after its last window; a pass batches the current window of every occupied slot, whatever its ``k``. A row's result is what ``generate`` gives
+        on the row alone with the same draws. ``uniforms``: a list of per-row float32 ``[n_b, 6, W]``; from ``seed`` row b draws ``row_uniforms(seed, b,
+        n_b, W)``, which does not depend on the other rows. The result also carries ``passes`` and ``placement`` as the library ran them."""
+        rows = _as_rows(codes)
+        n_rows, W = len(rows), self.block_size
+        if not 1 <= n_rows <= MAX_QUEUE_ROWS:
+            raise ValueError(f"to_fine: 1 to {MAX_QUEUE_ROWS} rows per call with slots=, got {n_rows}")
+        if not (isinstance(slots, (int, np.integer)) and 1 <= slots <= MAX_SLOTS):
+            raise ValueError(f"to_fine: slots must be 1 to {MAX_SLOTS}, got {slots!r}")
+        slots = int(slots)
+        lens = [int(r.shape[1]) for r in rows]
+        n = [len(fine_windows(T, W)) for T in lens]
+        max_T, cells = max(lens), sum(n)
+        greedy = temperature is None
+        flat_u = None
+        if not greedy:
+            if uniforms is None:
+                uniforms = [row_uniforms(seed, b, n[b], W) for b in range(n_rows)]
+            if not isinstance(uniforms, (list, tuple)) or len(uniforms) != n_rows:
+                raise ValueError(f"uniforms must be a list of {n_rows} float32 arrays [n_b, {N_PASSES}, {W}], one per row")
+            for b, u in enumerate(uniforms):
+                if np.shape(u) != (n[b], N_PASSES, W):
+                    raise ValueError(f"uniforms[{b}] must be float32 [{n[b]}, {N_PASSES}, {W}] (window, code book, buffer position), got {np.shape(u)}")
+            flat_u = np.concatenate([np.asarray(u, dtype=np.float32).reshape(-1) for u in uniforms])
+        off = np.concatenate([[0], np.cumsum(lens)])
+        woff = np.concatenate([[0], np.cumsum(n)])
+        host = np.concatenate([np.clip(r, -1, self.config.codebook_size).astype(np.int32).reshape(-1) for r in rows])   # row b: [2][T_b] at 2 off[b]
+        dev = self.device
+        with torch.cuda.device(dev):
+            d_codes = torch.from_numpy(host).to(dev)
+            d_u = None if greedy else torch.from_numpy(flat_u).to(dev)
+            d_out = torch.full((8 * int(off[-1]),), -1, dtype=torch.int32, device=dev)
+            d_logits = d_ids = None
+            if return_logits:
+                d_logits = torch.full((cells, N_PASSES, W, 1024), float("nan"), dtype=torch.float32, device=dev)
+                d_ids = torch.full((cells, N_PASSES, W), -1, dtype=torch.int32, device=dev)
+            nbytes = int(self._fn("queue_state_bytes")(self.handle, slots, max_T))
+            if nbytes == 0:
+                raise _cabi.HipLibraryError(f"at_fine_queue_state_bytes failed: {_cabi.last_error()}")
+            state = self._workspace(nbytes)
+            self._status.zero_()
+            c_lens = (C.c_int32 * n_rows)(*lens)
+            cap = cells   # a pass holds at least one window
+            trace = (C.c_int32 * (3 * cap))()
+            n_passes = (C.c_int32 * 1)()
+            placement = (C.c_int32 * (3 * n_rows))()
+            _cabi.check(self._fn("generate_queue")(self.handle, d_codes.data_ptr(), c_lens, n_rows, 1.0 if greedy else float(temperature), 1 if greedy else 0,
+                                                   _cabi.ptr(d_u), d_out.data_ptr(), _cabi.ptr(d_logits), _cabi.ptr(d_ids), state.data_ptr(), state.numel(),
+                                                   max_T, slots, trace, cap, n_passes, placement, _cabi.current_stream_handle(dev),
+                                                   self._status.data_ptr()), "at_fine_generate_queue")
+            out = d_out.cpu().to(torch.int64)   # synchronises
+        if self.last_status() & 1:
+            raise ValueError("at_fine_generate_queue: a coarse code lies outside [0, 1024)")
+        self.last_raw_codes = out   # the whole ragged buffer (tests)
+        result = FineGeneration(codes=[out[8 * off[b]:8 * off[b + 1]].reshape(8, lens[b]).clone() for b in range(n_rows)])
+        result.passes = [tuple(trace[3 * p:3 * p + 3]) for p in range(n_passes[0])]
+        result.placement = [tuple(placement[3 * b:3 * b + 3]) for b in range(n_rows)]
+        if return_logits:
+            result.logits = [d_logits[woff[b]:woff[b + 1]].cpu() for b in range(n_rows)]
+            result.window_ids = [d_ids[woff[b]:woff[b + 1]].cpu().to(torch.int64) for b in range(n_rows)]
         return result

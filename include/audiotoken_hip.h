@@ -744,6 +744,27 @@ size_t at_fine_state_bytes(const at_fine_t* h, int B, int max_T);
 int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
                      const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
                      int max_T, at_stream_t stream, int32_t* status_dev);
+/* Bytes of the caller-owned device state of one at_fine_generate_queue call: `slots` (1 to 64) work arrays [max(max_T, W)][8] and the activations of
+ * `slots` windows, nothing per row: what at_fine_state_bytes(h, slots, max_T) gives. 0 = error. */
+size_t at_fine_queue_state_bytes(const at_fine_t* h, int slots, int max_T);
+/* The fine stage's window queue: n_rows rows (1 to 4096) through `slots` work arrays (1 to 64). Every row follows at_fine_generate's
+ * schedule unchanged (the same windows, start, rel, code-book order and write-back); only when a window runs changes. Rows take empty slots in the
+ * caller's order; a slot runs its row's windows 0 .. n - 1 in consecutive passes, and a slot whose row has run its last window takes the next waiting
+ * row in the next pass. Pass p is the current window of every occupied slot, in slot order, as one batch: windows of different k sit side by side. The
+ * schedule follows from the lengths alone; the call is enqueued on `stream`, allocates no device memory and never waits for the device.
+ * All arrays are ragged and indexed by ROW, never by slot: lens HOST int32 [n_rows] (1 <= lens[b] <= max_T); with off = the exclusive prefix sum of lens
+ * and woff = that of the rows' window counts, row b's coarse codes are device int32 [2][T_b] at coarse_dev + 2 off[b], its result [8][T_b] at
+ * out_dev + 8 off[b], and the draw of its window k, code book 2 + j, buffer position t is uniforms_dev[((woff[b] + k) * 6 + j) * W + t] whatever slot
+ * and pass it ran in. logits_out_dev NULL or float32 [sum n_b][6][W][1024], window_ids_dev NULL or int32 [sum n_b][6][W], by the same window cell;
+ * entries of positions < rel are left as they were. A row's work array is written when it enters its slot (all max(T_b, W) cells, so nothing of the
+ * slot's previous row can be read) and copied out when it leaves. trace NULL or HOST int32 [trace_cap][3], one row per pass: windows, rows admitted,
+ * rows retired; n_passes NULL or HOST: the passes run (a trace too small loses its tail, the run goes on). placement NULL or HOST int32 [n_rows][3]:
+ * slot, first pass, last pass of each row. greedy, temperature, the sampling rule and status_dev as at_fine_generate. state_dev:
+ * at_fine_queue_state_bytes(h, slots, max_T) bytes. With slots = 1 every pass is one window and a row's launches are those of at_fine_generate on the
+ * row alone. Every argument and the state's size are checked before the device is touched. Not re-entrant per handle. */
+int at_fine_generate_queue(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy, const float* uniforms_dev,
+                           int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T, int slots,
+                           int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream, int32_t* status_dev);
 
 #ifdef __cplusplus
 }
