@@ -222,6 +222,16 @@ SIGNATURES = {
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "at_gpt_long_num_windows_prompted": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "at_gpt_generate_long_prompted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_gpt_generate_queue_prompted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                 C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "at_op_topk_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "at_fine_create": (C.c_void_p, [C.c_int]),
     "at_fine_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -239,6 +249,16 @@ SIGNATURES = {
     "at_fine_generate_queue": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "at_fine_num_windows_hist": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "at_fine_state_bytes_hist": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "at_fine_queue_state_bytes_hist": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "at_fine_generate_hist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                        C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "at_fine_generate_queue_hist": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                              C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                              C.c_void_p, C.c_void_p]),
 }
 
 

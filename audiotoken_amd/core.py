@@ -319,7 +319,7 @@ class AudioToken:
 
     def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0, uniforms=None,
                     constrain: bool = False, return_logits: bool = False, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None,
-                    slots: Optional[int] = None, tick_tokens: Optional[int] = None):
+                    slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None):
         """Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoder (its GPT, ``decoder.py:210-239``) on the
         KV-cached HIP decoder (semantic_decoder.py). Semantic tokenizers only. ``tokens``: a tensor / array / path of semantic ids (any
         shape, flattened), or a list of up to 64 of them, generated as one batch. Returns an ``AcousticGeneration``: ``codes`` (a list of int64
@@ -333,21 +333,27 @@ class AudioToken:
         source (up to 65536 ids) in windows of ``window`` ids every ``hop`` ids, carrying the acoustic ids of the overlap: always
         constrained, ``uniforms`` indexed by the position in the row's result, ``windows`` of the result the schedule that ran. With ``slots=`` (1 to 64) the
         long form takes 1 to 4096 sources and runs them through that many cache rows, each source starting when a row is free and finishing on its own
-        (DESIGN.md §20); ``tick_tokens`` bounds the tokens of one model pass. A source's result does not depend on its neighbours."""
+        (DESIGN.md §20); ``tick_tokens`` bounds the tokens of one model pass. A source's result does not depend on its neighbours.
+        ``voice=`` (``long_form=True`` only): a ``VoicePrompt`` that every source continues, or a list with one (or None) per source. The
+        prompt's ids stand in front of the source's and its coarse codes are the first window's carry; the result covers the generated ids only."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_acoustic maps semantic ids to acoustic code books; {self.tokenizer_name} has no semantic ids")
         if not long_form and (window is not None or hop is not None):
             raise ValueError("to_acoustic: window= and hop= belong to long_form=True")
         if not long_form and (slots is not None or tick_tokens is not None):
             raise ValueError("to_acoustic: slots= and tick_tokens= belong to long_form=True")
+        if not long_form and voice is not None:
+            raise ValueError("to_acoustic: voice= belongs to long_form=True (the prompt is the first window's carry, which only the long form has)")
         self._gpt()
         if long_form:
             return self.semantic_decoder.to_acoustic_long(tokens, window=window, hop=hop, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
-                                                          seed=seed, uniforms=uniforms, return_logits=return_logits, slots=slots, tick_tokens=tick_tokens)
+                                                          seed=seed, uniforms=uniforms, return_logits=return_logits, slots=slots, tick_tokens=tick_tokens,
+                                                          voice=voice)
         return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
                                                  constrain=constrain, return_logits=return_logits)
 
-    def to_fine(self, codes, temperature: Optional[float] = 0.5, seed: int = 0, uniforms=None, return_logits: bool = False, slots: Optional[int] = None):
+    def to_fine(self, codes, temperature: Optional[float] = 0.5, seed: int = 0, uniforms=None, return_logits: bool = False, slots: Optional[int] = None,
+                history=None):
         """The two coarse EnCodec code books -> all eight: stage 2 of the reference's semantic decoder (bark's ``generate_fine``) on the HIP fine
         transformer (fine_decoder.py). Acoustic codes in, acoustic codes out, so every tokenizer has it. ``codes``: integer ``[2, T]``, or a
         list of up to 64 of them of their own lengths, run as one batch. Returns a ``FineGeneration``: ``codes`` (a list of int64 ``[8, T_b]`` that
@@ -358,14 +364,39 @@ class AudioToken:
         With ``slots=`` (1 to 64) the call is the window queue and takes 1 to 4096 rows: each row starts when a work array is free and
         leaves after its last window, so a long row does not hold short ones back. ``uniforms`` is then a list of per-row float32 ``[n_b, 6, W]``; from
         ``seed`` row b draws ``np.random.Generator(np.random.Philox(key=[seed, b])).random((n_b, 6, W), float32)``, whatever the other rows are. A row's
-        codes are those of the row alone with the same draws; the result also carries ``passes`` and ``placement``."""
-        from .fine_decoder import MAX_SLOTS, _as_rows
+        codes are those of the row alone with the same draws; the result also carries ``passes`` and ``placement``.
+        ``history=`` makes the rows continue a clip (bark's ``history_prompt["fine_prompt"]``): integer ``[8, Th]`` EnCodec codes that
+        every row continues, or a list with one such array (or None) per row. The last ``min(W / 2, Th)`` frames stand in front of the row's own and are
+        read, never written; the result holds the row's own frames only, and a row's windows (which ``uniforms`` counts) are
+        ``fine_decoder.fine_windows(T, W, history_cells(Th, W))``. Rows that name the SAME object share one entry of the device's table (one upload of its
+        last ``W / 2`` frames for a whole corpus); equal arrays that are distinct objects are uploaded once each."""
+        from .fine_decoder import MAX_SLOTS, _as_histories, _as_rows
         rows = _as_rows(codes)   # a malformed input is refused before any model is built
+        _as_histories(history, len(rows), 0, check_only=True)   # so is a malformed history, by its shape and dtype alone: generate converts it, once
         if slots is not None:
             if not (isinstance(slots, (int, np.integer)) and 1 <= slots <= MAX_SLOTS):
                 raise ValueError(f"to_fine: slots must be 1 to {MAX_SLOTS}, got {slots!r}")
-            return self._fine().generate_queue(rows, slots=int(slots), temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
-        return self._fine().generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits)
+            return self._fine().generate_queue(rows, slots=int(slots), temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits,
+                                               history=history)
+        return self._fine().generate(rows, temperature=temperature, seed=seed, uniforms=uniforms, return_logits=return_logits, history=history)
+
+    def voice_prompt(self, path, max_ids: Optional[int] = None):
+        """A ``VoicePrompt`` from an audio file: the file's semantic ids from this tokenizer's own encoder, its EnCodec codes from an
+        acoustic tokenizer at 8 code books held the way ``to_audio`` holds its decoder, and of both the latest aligned stretch
+        (``VoicePrompt.from_tokens``) of at most ``max_ids`` ids; default: window - hop of ``default_window``, the longest prompt the long form takes."""
+        from .semantic_decoder import default_window
+        from .voice import VoicePrompt
+        if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
+            raise ValueError(f"voice_prompt pairs semantic ids with acoustic codes; {self.tokenizer_name} has no semantic ids")
+        gpt = self._gpt()
+        if max_ids is None:
+            S, H = default_window(gpt.config, gpt.block_size)
+            max_ids = S - H
+        path = Path(path)
+        sem = self.encode(path)
+        codes = self._fine_audio().encode(path)
+        return VoicePrompt.from_tokens(torch.as_tensor(sem).cpu().reshape(-1), torch.as_tensor(codes).cpu().reshape(8, -1), int(max_ids),
+                                       gpt.config.SEMANTIC_VOCAB_SIZE)
 
     def _gpt(self):
         if getattr(self, "semantic_decoder", None) is None:
@@ -397,7 +428,7 @@ class AudioToken:
 
     def to_audio(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, fine_temperature: Optional[float] = 0.5,
                  seed: int = 0, uniforms=None, fine_uniforms=None, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None,
-                 slots: Optional[int] = None, tick_tokens: Optional[int] = None):
+                 slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None):
         """Semantic ids -> audio, this project's form of the reference's semantic ``decode`` (``decoder.py:210-243``): ``to_acoustic(constrain=True)``, then
         ``to_fine``, then the acoustic decoder at 8 code books (bandwidth 6). Semantic tokenizers only. ``tokens`` as ``to_acoustic`` takes them. Returns
         ``(audio, coarse, fine)``: a list of one float32 ``(1, 320 * T_b)`` CPU tensor per source, the ``AcousticGeneration`` and the ``FineGeneration``.
@@ -405,18 +436,31 @@ class AudioToken:
         ``long_form=True`` (with ``window`` / ``hop``) makes stage 1 the long form of ``to_acoustic``, so that the audio covers the whole source and not its
         first 5 s; the two later stages take any length as they are. With ``slots=`` stage 1 is the generation queue and takes up to 4096 sources; ``to_fine``
         then runs in groups of at most 64 in source order (``fine_uniforms``: ``[B, n_max, 6, W]`` over all sources, each group taking its rows and the windows
-        its longest member needs), and the returned ``FineGeneration`` holds every source's codes."""
+        its longest member needs), and the returned ``FineGeneration`` holds every source's codes.
+        ``voice=`` (``long_form=True`` only): a ``VoicePrompt`` with all 8 code books that every source continues, or a list with one (or
+        None) per source: its ids and code books 0 and 1 prompt stage 1, all 8 are ``to_fine``'s ``history``. The audio and both generations cover the
+        generated frames only."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_audio maps semantic ids to audio; {self.tokenizer_name} has no semantic ids (its own decode is the way back)")
+        history = None
+        if voice is not None:
+            if not long_form:
+                raise ValueError("to_audio: voice= belongs to long_form=True")
+            from .voice import per_row
+            n_src = len(tokens) if isinstance(tokens, (list, tuple)) else 1
+            rows = per_row(voice, n_src, "to_audio: voice")
+            if any(v is not None and v.codes.shape[0] != 8 for v in rows):
+                raise ValueError("to_audio: a voice prompt needs all 8 code books (the fine stage continues them)")
+            history = voice.codes if not isinstance(voice, (list, tuple)) else [None if v is None else v.codes for v in rows]
         coarse = self.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms, constrain=True,
-                                  long_form=long_form, window=window, hop=hop, slots=slots, tick_tokens=tick_tokens)
+                                  long_form=long_form, window=window, hop=hop, slots=slots, tick_tokens=tick_tokens, voice=voice)
         for b, c in enumerate(coarse.codes):
             if c is None or c.shape[1] < 1:
                 raise ValueError(f"to_audio: source {b} produced no whole frame of coarse codes (finish: {coarse.finish[b]})")
         if len(coarse.codes) <= 64:
-            fine = self.to_fine(coarse.codes, temperature=fine_temperature, seed=seed, uniforms=fine_uniforms)
+            fine = self.to_fine(coarse.codes, temperature=fine_temperature, seed=seed, uniforms=fine_uniforms, history=history)
         else:
-            fine = self._to_fine_in_groups(coarse.codes, fine_temperature, seed, fine_uniforms)
+            fine = self._to_fine_in_groups(coarse.codes, fine_temperature, seed, fine_uniforms, history=history)
         audio = [self._fine_audio().decode(c.unsqueeze(0)) for c in fine.codes]
         return audio, coarse, fine
 
@@ -425,7 +469,7 @@ class AudioToken:
                              audio_format: str = "wav", rescale: bool = False, stream: bool = False, seed: int = 0, temperature: float = 0.8,
                              top_k: int = 100, fine_temperature: Optional[float] = 0.5, max_new_tokens: int = 1024, window: Optional[int] = None,
                              hop: Optional[int] = None, slots: int = 64, fine_slots: int = 64, round_files: int = 1024,
-                             codes_dir: Optional[os.PathLike] = None, **kwargs) -> None:
+                             codes_dir: Optional[os.PathLike] = None, voice=None, **kwargs) -> None:
         """The way back from a semantic ``encode_batch_files``: ``.npy`` files of semantic ids -> audio files (semantic_files.py). Semantic
         tokenizers only (``decode_batch_files`` stays the acoustic tokenizer's, and keeps raising here). Inputs, output names, overwriting, the skipping of
         a second input that maps to one output name, sharding under ``torch.distributed``, ``audio_format`` ("wav" / "flac", checked before any model is
@@ -440,7 +484,9 @@ class AudioToken:
         A file's draws (``semantic_files.file_draws``) come from ``np.random.Generator(np.random.Philox(key=[seed, fnv1a64(stem)]))``, ``stem`` its output
         path relative to ``outdir`` without the extension, in posix form: first the stage 1 draws of the source's own stream capacity, then its
         ``[n, 6, W]`` fine draws, so they do not depend on the other files, the round size or the ranks. ``run_summary`` gains ``rounds``, ``gpt_ticks``,
-        ``fine_passes`` and ``generated_frames``; ``run_timings`` gains ``gpt_s`` and ``fine_s`` (both inside ``stage_s``)."""
+        ``fine_passes`` and ``generated_frames``; ``run_timings`` gains ``gpt_s`` and ``fine_s`` (both inside ``stage_s``).
+        ``voice=``: one ``VoicePrompt`` with all 8 code books that every file continues, as ``to_audio(long_form=True, voice=)`` does; a
+        file's ids and the prompt's may have 65536 together, and a file's fine draws count the windows of a row after the prompt's history."""
         from . import semantic_files as SF
         from . import writer as Wr
         if audio_format not in Wr.AUDIO_FORMATS:
@@ -455,7 +501,7 @@ class AudioToken:
                 raise ValueError(f"to_audio_batch_files: {name} must be 1 to {most}, got {value!r}")
         known = {"shard_across_ranks", "device_writer", "max_held_bytes"}
         decoder_kwargs = {k: v for k, v in kwargs.items() if k not in known}
-        stages = SF.Stages(self, seed, temperature, top_k, fine_temperature, max_new_tokens, window, hop, slots, fine_slots)
+        stages = SF.Stages(self, seed, temperature, top_k, fine_temperature, max_new_tokens, window, hop, slots, fine_slots, voice=voice)
         acoustic = self._fine_audio()
         acoustic.load_decoder(**decoder_kwargs)
         self.skipped_files = []
@@ -478,19 +524,22 @@ class AudioToken:
                           int(kwargs.get("max_held_bytes", Wr.DEFAULT_MAX_HELD_BYTES)), cfg.model_sample_rate, cfg.model_token_rate, audio_format,
                           bool(stream), log=log)
 
-    def _to_fine_in_groups(self, codes, temperature, seed, uniforms, group: int = 64):
+    def _to_fine_in_groups(self, codes, temperature, seed, uniforms, group: int = 64, history=None):
         """``to_fine`` over more than 64 rows: groups of at most ``group`` in order, one ``FineGeneration`` over all of them. A group's draws are its rows of
         ``uniforms`` cut to the windows its longest member has; from ``seed`` each group draws its own stream, seeded ``seed + its index``."""
-        from .fine_decoder import fine_windows
+        from .fine_decoder import fine_windows, history_cells
         W = self._fine().block_size
+        hist = history if isinstance(history, (list, tuple)) else [history] * len(codes)
         out = None
         for g, at in enumerate(range(0, len(codes), group)):
             rows = codes[at:at + group]
             u = None
             if uniforms is not None:
-                n_max = max(len(fine_windows(int(c.shape[1]), W)) for c in rows)
+                n_max = max(len(fine_windows(int(c.shape[1]), W, 0 if hh is None else history_cells(int(hh.shape[1]), W)))
+                            for c, hh in zip(rows, hist[at:at + group]))
                 u = np.ascontiguousarray(np.asarray(uniforms)[at:at + group, :n_max])
-            part = self.to_fine(rows, temperature=temperature, seed=seed + g, uniforms=u)
+            part = self.to_fine(rows, temperature=temperature, seed=seed + g, uniforms=u,
+                                history=history if not isinstance(history, (list, tuple)) else hist[at:at + group])
             if out is None:
                 out = part
             else:

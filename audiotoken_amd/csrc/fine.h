@@ -29,10 +29,21 @@ struct FineLayer {
     const float *qkv_b = nullptr, *proj_b = nullptr, *fc_b = nullptr, *fc_proj_b = nullptr;   // all four or none
 };
 
-// the windows of a row of T frames: n = max(0, ceil((T - W) / H)) + 1 with H = W / 2
-inline int fine_windows(int T, int W) {
+// The history rule, stated once: a row of T frames that continues a history of Th frames keeps the last h = min(H, Th) of them, H = W / 2,
+// in cells [0, h) of its work array of L = max(h + T, W) cells; its own frames are cells [h, h + T). h = 0 is the rule without a history.
+inline int fine_history(int Th, int W) { return Th < W / 2 ? Th : W / 2; }
+inline int fine_cells(int T, int W, int h = 0) { return h + T > W ? h + T : W; }
+// the windows of a row of T frames after h history cells: n = max(0, ceil((T - (W - h)) / H)) + 1
+inline int fine_windows(int T, int W, int h = 0) {
     const int H = W / 2;
-    return (T > W ? (T - W + H - 1) / H : 0) + 1;
+    return (h + T > W ? (h + T - W + H - 1) / H : 0) + 1;
+}
+// window k of that row reads cells [start, start + W) and predicts from cell fill on: buffer positions >= rel = fill - start, 0 <= rel <= H.
+// With h > 0 every window has rel > 0, and no window writes below cell h.
+inline void fine_window(int k, int T, int W, int h, int* start, int* fill) {
+    const int H = W / 2, L = fine_cells(T, W, h);
+    *start = k * H < L - W ? k * H : L - W;
+    *fill = h + k * H < L - H ? h + k * H : L - H;
 }
 
 constexpr int FINE_MAX_QUEUE = 4096;   // rows of one at_fine_generate_queue call
@@ -49,10 +60,10 @@ struct FineQueuePass {
 
 class FineQueueSchedule {
 public:
-    // lens: n_rows lengths, each 1 to FINE_MAX_T; 1 <= slots <= FINE_MAX_B; the caller has checked both
-    FineQueueSchedule(const int32_t* lens, int n_rows, int W, int slots)
+    // lens: n_rows lengths, each 1 to FINE_MAX_T; 1 <= slots <= FINE_MAX_B; the caller has checked both. hist: null, or the rows' history cells h
+    FineQueueSchedule(const int32_t* lens, int n_rows, int W, int slots, const int32_t* hist = nullptr)
         : n_rows_(n_rows), slots_(slots), windows_(n_rows), placement_(3 * (size_t)n_rows, -1) {
-        for (int b = 0; b < n_rows; ++b) windows_[b] = fine_windows(lens[b], W);
+        for (int b = 0; b < n_rows; ++b) windows_[b] = fine_windows(lens[b], W, hist ? hist[b] : 0);
         for (int j = 0; j < FINE_MAX_B; ++j) holds_[j] = -1;
     }
     // the next pass; false once every row has retired

@@ -3,11 +3,11 @@
 // without bias, E / 64 heads of 64, attention over the whole window without a mask, erf-GELU MLP), a final LayerNorm and 7 heads.
 // The matrix products, the attention and the LayerNorm are the library's own fp32 launchers (launch_gemm, launch_relpos_attention with its arithmetic set to
 // fp32, launch_layernorm). New here, all fp32:
-//   fine_init_kernel     the work arrays [L][8] of the rows that enter a slot: the coarse codes, 1024 everywhere else
+//   fine_init_kernel     the work arrays [L][8] of the rows that enter a slot: a history's last frames, the coarse codes, 1024 everywhere else
 //   fine_embed_kernel    x[t] = sum_{i <= c} wtes[i][cell[t][i]] + wpe[t], read straight from the work arrays at each row's window (no batch copy of the ids)
 //   fine_gather_kernel   the rows the head needs (positions >= rel of every window of the pass), where a window has rel > 0
 //   fine_sample_kernel   one wave per position over its 1024 logits: the argmax or the inverse-CDF draw, written straight into the work array
-//   fine_finish_kernel   the first T positions of the rows that leave a slot, as [8][T]
+//   fine_finish_kernel   the T cells after the history of the rows that leave a slot, as [8][T]
 // A call enqueues every window of every row without looking at the device: the host knows the schedule from the lengths. No float is added atomically.
 // Both generators are one loop (run_passes) over the passes of FineQueueSchedule (fine.h): at_fine_generate is the queue with a slot per row.
 #include <cmath>
@@ -33,13 +33,14 @@ struct FineState {
 
 size_t round256(size_t n) { return (n + 255) / 256 * 256; }
 
-FineState carve_state(void* base, int B, int max_T, int W, int E) {
+// max_hist: the longest history of the call (0 = none); a work array then holds min(H, max_hist) + max_T cells
+FineState carve_state(void* base, int B, int max_T, int max_hist, int W, int E) {
     FineState s{};
     char* p = static_cast<char*>(base);
     size_t off = 0;
     auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += round256(bytes); return r; };
     const size_t R = (size_t)B * W;
-    s.Lmax = max_T > W ? max_T : W;
+    s.Lmax = fine_cells(max_T, W, fine_history(max_hist, W));
     s.work = (int*)take((size_t)B * s.Lmax * FINE_CODES * 4);
     s.ones = (float*)take(R * 4);
     s.x = (float*)take(R * E * 4);
@@ -67,7 +68,10 @@ struct FineRows {
     int cell0[FINE_MAX_B];             // the slot's base, in cells of the state's work arrays
     int stride[FINE_MAX_B];            // distance between the row's planes in coarse_dev / out_dev
     long long at[FINE_MAX_B];          // the row's first element in coarse_dev / out_dev
+    int h[FINE_MAX_B];                 // history cells in front of the row's own; 0 = none
+    long long hat[FINE_MAX_B];         // the first of the history's last h frames, in plane 0 of its table entry
 };
+static_assert(sizeof(FineRows) + 64 <= 4096, "fine_init_kernel's arguments must stay under the launch limit");
 struct FineTables { const float* t[FINE_CODES]; };
 
 __device__ __forceinline__ int slot_of(const FinePass& p, int r) {
@@ -76,26 +80,42 @@ __device__ __forceinline__ int slot_of(const FinePass& p, int r) {
     return j;
 }
 
-// A row enters its slot: blockIdx.y = the row of the list, thread = position. Every one of the row's max(T, W) cells is rewritten (the coarse codes, 1024
-// everywhere else), which is all a window of the row can read: whatever the slot's previous row left behind lies past them or is overwritten.
-// A coarse code outside [0, 1024) is clamped and reported in bit 0 of *status. ones: the attention's key mask, written by the call's first launch.
-__global__ __launch_bounds__(256) void fine_init_kernel(FineRows rows, int W, const int* coarse, int* work, float* ones, int* status) {
+// A row enters its slot: blockIdx.y = the row of the list, thread = cell. Every one of the row's max(h + T, W) cells is rewritten (the last h history
+// frames in all 8 channels, the coarse codes, 1024 everywhere else), which is all a window of the row can read: whatever the slot's previous row left behind
+// lies past them or is overwritten. A coarse code outside [0, 1024) is clamped and reported in bit 0 of *status, a history id in bit 1. ones: the
+// attention's key mask, written by the call's first launch. hist: the call's history table, planes hstride apart (null and 0 where no row has one).
+__global__ __launch_bounds__(256) void fine_init_kernel(FineRows rows, int W, const int* coarse, const int* hist, int hstride, int* work, float* ones, int* status) {
     const int j = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int T = rows.T[j];
-    if (t >= max(T, W)) return;
+    const int T = rows.T[j], h = rows.h[j];
+    if (t >= max(h + T, W)) return;
     if (ones && t < W) ones[(size_t)j * W + t] = 1.0f;
+    int4* cell = reinterpret_cast<int4*>(work + ((size_t)rows.cell0[j] + t) * FINE_CODES);
+    if (t < h) {
+        const int* src = hist + rows.hat[j] + t;
+        int id[FINE_CODES];
+        bool bad = false;
+#pragma unroll
+        for (int ch = 0; ch < FINE_CODES; ++ch) {
+            const int v = src[(size_t)ch * hstride];
+            bad |= v < 0 || v >= FINE_VOCAB;
+            id[ch] = min(max(v, 0), FINE_VOCAB - 1);
+        }
+        if (bad && status) atomicOr(status, 2);
+        cell[0] = make_int4(id[0], id[1], id[2], id[3]);
+        cell[1] = make_int4(id[4], id[5], id[6], id[7]);
+        return;
+    }
     int c0 = FINE_VOCAB, c1 = FINE_VOCAB;
-    if (t < T) {
-        const int* src = coarse + rows.at[j];
-        c0 = src[t];
-        c1 = src[(size_t)rows.stride[j] + t];
+    if (t < h + T) {
+        const int* src = coarse + rows.at[j] + (t - h);
+        c0 = src[0];
+        c1 = src[(size_t)rows.stride[j]];
         if (c0 < 0 || c0 >= FINE_VOCAB || c1 < 0 || c1 >= FINE_VOCAB) {
             if (status) atomicOr(status, 1);
             c0 = min(max(c0, 0), FINE_VOCAB - 1);
             c1 = min(max(c1, 0), FINE_VOCAB - 1);
         }
     }
-    int4* cell = reinterpret_cast<int4*>(work + ((size_t)rows.cell0[j] + t) * FINE_CODES);
     cell[0] = make_int4(c0, c1, FINE_VOCAB, FINE_VOCAB);
     cell[1] = make_int4(FINE_VOCAB, FINE_VOCAB, FINE_VOCAB, FINE_VOCAB);
 }
@@ -217,11 +237,11 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void fine_sample_kernel(FinePass
     }
 }
 
-// A row leaves its slot: out[ch][t] = work[t][ch] for t < T, at the row's place in out; the rest of out is left as it was
+// A row leaves its slot: out[ch][t] = work[h + t][ch] for t < T (the history cells stay behind), at the row's place in out; the rest of out is left as it was
 __global__ __launch_bounds__(256) void fine_finish_kernel(FineRows rows, const int* work, int* out) {
     const int j = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= rows.T[j]) return;
-    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)rows.cell0[j] + t) * FINE_CODES);
+    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)rows.cell0[j] + rows.h[j] + t) * FINE_CODES);
     const int4 lo = cell[0], hi = cell[1];
     const int ids[FINE_CODES] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
     int* dst = out + rows.at[j];
@@ -297,9 +317,13 @@ const char* const kLinears[4] = {".attn.c_attn", ".attn.c_proj", ".mlp.c_fc", ".
 struct FineRowMap {
     long long src, dst;
     int stride, draw0;
+    int h = 0;             // history cells and where the first of them lies in the history table
+    long long hat = 0;
 };
 struct FineCall {
     const int32_t* coarse;
+    const int32_t* hist;   // the history table; null where no row has a history
+    int hstride;
     int32_t* out;
     float temperature;
     int greedy;
@@ -314,7 +338,7 @@ struct FineCall {
 int launch_rows(bool init, const FineRows& rows, int span, int W, const FineState& s, const FineCall& c, bool first, hipStream_t stream) {
     if (rows.n == 0) return 0;   // nothing enters or leaves in this pass
     const dim3 grid((unsigned)((span + 255) / 256), (unsigned)rows.n);
-    if (init) hipLaunchKernelGGL(fine_init_kernel, grid, dim3(256), 0, stream, rows, W, c.coarse, s.work, first ? s.ones : nullptr, c.status);
+    if (init) hipLaunchKernelGGL(fine_init_kernel, grid, dim3(256), 0, stream, rows, W, c.coarse, c.hist, c.hstride, s.work, first ? s.ones : nullptr, c.status);
     else hipLaunchKernelGGL(fine_finish_kernel, grid, dim3(256), 0, stream, rows, s.work, c.out);
     AT_CHECK_HIP(hipGetLastError());
     return 0;
@@ -322,11 +346,13 @@ int launch_rows(bool init, const FineRows& rows, int span, int W, const FineStat
 
 // lens and map are indexed by row; everything has been checked. Slot j's work array is cells [j Lmax, (j + 1) Lmax) of the state.
 int run_passes(const at_fine* h, const FineState& s, const int32_t* lens, int n_rows, int slots, const FineRowMap* map, const FineCall& c, hipStream_t stream) {
-    const int W = h->block, H = W / 2;
+    const int W = h->block;
     FineSampleArgs sa{};
     sa.logits = s.logits; sa.W = W; sa.greedy = c.greedy; sa.temperature = c.greedy ? 1.0f : c.temperature;
     sa.uniforms = c.uniforms; sa.work = s.work; sa.logits_out = c.logits_out; sa.ids_out = c.window_ids;
-    FineQueueSchedule schedule(lens, n_rows, W, slots);
+    std::vector<int32_t> hcells((size_t)n_rows);
+    for (int b = 0; b < n_rows; ++b) hcells[b] = map[b].h;
+    FineQueueSchedule schedule(lens, n_rows, W, slots, hcells.data());
     FineQueuePass q;
     while (schedule.next(&q)) {
         const int at = schedule.passes() - 1;
@@ -344,15 +370,17 @@ int run_passes(const at_fine* h, const FineState& s, const int32_t* lens, int n_
             rows.cell0[j] = q.slot[i] * s.Lmax;
             rows.stride[j] = map[b].stride;
             rows.at[j] = init ? map[b].src : map[b].dst;
-            const int cells = init && T < W ? W : T;
+            rows.h[j] = map[b].h;
+            rows.hat[j] = map[b].hat;
+            const int cells = init ? fine_cells(T, W, map[b].h) : T;
             span = cells > span ? cells : span;
         };
         for (int a = 0; a < q.n_admit; ++a) add(in, span_in, q.admit[a], true);
         for (int a = 0; a < q.n_retire; ++a) add(outr, span_out, q.retire[a], false);
         for (int i = 0; i < q.n; ++i) {
             const int b = q.row[i], k = q.k[i];
-            const int L = lens[b] > W ? lens[b] : W;
-            const int start = k * H < L - W ? k * H : L - W, fill = k * H < L - H ? k * H : L - H;
+            int start, fill;
+            fine_window(k, lens[b], W, map[b].h, &start, &fill);
             p.cell0[i] = q.slot[i] * s.Lmax + start;
             p.draw[i] = map[b].draw0 + k;
             p.rel[i] = fill - start;
@@ -469,31 +497,76 @@ int at_fine_hidden(const at_fine_t* h) { return h && h->finalized ? h->embd : 0;
 int at_fine_block_size(const at_fine_t* h) { return h && h->finalized ? h->block : 0; }
 int at_fine_has_bias(const at_fine_t* h) { return h && h->finalized && h->bias ? 1 : 0; }
 
-int at_fine_num_windows(const at_fine_t* h, int T) {
-    if (!(h && h->finalized)) { set_error("at_fine_num_windows: the model is not finalized"); return 0; }
-    if (!(T >= 1 && T <= FINE_MAX_T)) { set_error("at_fine_num_windows: T must be 1 to 262144"); return 0; }
-    return fine_windows(T, h->block);
+// the three size queries behind their two names each: `who` is the entry point the caller called
+static int num_windows(const char* who, const at_fine_t* h, int T, int Th) {
+    const std::string w(who);
+    if (!(h && h->finalized)) { set_error(w + ": the model is not finalized"); return 0; }
+    if (!(T >= 1 && T <= FINE_MAX_T)) { set_error(w + ": T must be 1 to 262144"); return 0; }
+    if (!(Th >= 0 && Th <= FINE_MAX_T)) { set_error(w + ": the history must be 0 to 262144 frames"); return 0; }
+    return fine_windows(T, h->block, fine_history(Th, h->block));
+}
+static size_t state_bytes_of(const char* who, const char* rows, const at_fine_t* h, int B, int max_T, int max_hist) {
+    const std::string w(who);
+    if (!(h && h->finalized)) { set_error(w + ": the model is not finalized"); return 0; }
+    if (!(B >= 1 && B <= FINE_MAX_B)) { set_error(w + ": " + rows + " must be 1 to 64"); return 0; }
+    if (!(max_T >= 1 && max_T <= FINE_MAX_T)) { set_error(w + ": max_T must be 1 to 262144"); return 0; }
+    if (!(max_hist >= 0 && max_hist <= FINE_MAX_T)) { set_error(w + ": max_hist must be 0 to 262144"); return 0; }
+    return carve_state(nullptr, B, max_T, max_hist, h->block, h->embd).bytes;
 }
 
-size_t at_fine_state_bytes(const at_fine_t* h, int B, int max_T) {
-    if (!(h && h->finalized)) { set_error("at_fine_state_bytes: the model is not finalized"); return 0; }
-    if (!(B >= 1 && B <= FINE_MAX_B)) { set_error("at_fine_state_bytes: B must be 1 to 64"); return 0; }
-    if (!(max_T >= 1 && max_T <= FINE_MAX_T)) { set_error("at_fine_state_bytes: max_T must be 1 to 262144"); return 0; }
-    return carve_state(nullptr, B, max_T, h->block, h->embd).bytes;
+int at_fine_num_windows(const at_fine_t* h, int T) { return num_windows("at_fine_num_windows", h, T, 0); }
+int at_fine_num_windows_hist(const at_fine_t* h, int T, int Th) { return num_windows("at_fine_num_windows_hist", h, T, Th); }
+size_t at_fine_state_bytes(const at_fine_t* h, int B, int max_T) { return state_bytes_of("at_fine_state_bytes", "B", h, B, max_T, 0); }
+size_t at_fine_state_bytes_hist(const at_fine_t* h, int B, int max_T, int max_hist) { return state_bytes_of("at_fine_state_bytes_hist", "B", h, B, max_T, max_hist); }
+size_t at_fine_queue_state_bytes(const at_fine_t* h, int slots, int max_T) { return state_bytes_of("at_fine_queue_state_bytes", "slots", h, slots, max_T, 0); }
+size_t at_fine_queue_state_bytes_hist(const at_fine_t* h, int slots, int max_T, int max_hist) {
+    return state_bytes_of("at_fine_queue_state_bytes_hist", "slots", h, slots, max_T, max_hist);
 }
 
+}  // extern "C"
 
-size_t at_fine_queue_state_bytes(const at_fine_t* h, int slots, int max_T) {
-    if (!(h && h->finalized)) { set_error("at_fine_queue_state_bytes: the model is not finalized"); return 0; }
-    if (!(slots >= 1 && slots <= FINE_MAX_B)) { set_error("at_fine_queue_state_bytes: slots must be 1 to 64"); return 0; }
-    if (!(max_T >= 1 && max_T <= FINE_MAX_T)) { set_error("at_fine_queue_state_bytes: max_T must be 1 to 262144"); return 0; }
-    return carve_state(nullptr, slots, max_T, h->block, h->embd).bytes;
+namespace {
+
+// The history table of a call, as the caller gave it; n = 0 and null pointers where the call has none.
+struct FineHistory {
+    const int32_t* dev;     // device int32 [n][8][stride]
+    int stride;
+    const int32_t* lens;    // HOST [n]
+    int n;
+    const int32_t* of_row;  // HOST [rows]: the entry of each row, -1 for none
+    int max_hist;
+};
+
+// Checks the table and writes every row's history cells and their place into map[b].h / map[b].hat. Touches no device.
+int place_history(const char* who, const FineHistory& hi, int n_rows, int W, FineRowMap* map) {
+    const std::string fn(who);
+    auto fail = [&](const std::string& msg) { set_error(fn + ": " + msg); return -1; };
+    if (hi.n < 0 || hi.n > FINE_MAX_QUEUE) return fail("n_hist must be 0 to 4096");
+    if (hi.max_hist < 0 || hi.max_hist > FINE_MAX_T) return fail("max_hist must be 0 to 262144");
+    if (hi.n == 0) {
+        if (hi.of_row)
+            for (int b = 0; b < n_rows; ++b)
+                if (hi.of_row[b] != -1) return fail("the history of row " + std::to_string(b) + " must be -1: the table is empty");
+        return 0;
+    }
+    if (!(hi.dev && hi.lens && hi.of_row)) return fail("null pointer: a history table needs its ids, its lengths and the history of every row");
+    if (hi.stride < 1 || hi.stride > FINE_MAX_T) return fail("h_stride must be 1 to 262144");
+    for (int i = 0; i < hi.n; ++i)
+        if (hi.lens[i] < 1 || hi.lens[i] > hi.stride || hi.lens[i] > hi.max_hist)
+            return fail("the length of history " + std::to_string(i) + " must be 1 to min(h_stride, max_hist)");
+    for (int b = 0; b < n_rows; ++b) {
+        const int i = hi.of_row[b];
+        if (i < -1 || i >= hi.n) return fail("the history of row " + std::to_string(b) + " must be -1 or an entry of the table");
+        if (i < 0) continue;
+        map[b].h = fine_history(hi.lens[i], W);
+        map[b].hat = (long long)i * FINE_CODES * hi.stride + (hi.lens[i] - map[b].h);
+    }
+    return 0;
 }
 
-// The queue with slots = B: every row is admitted in pass 0, and pass k is window k of every row that has one, in row order.
-int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
-                     const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
-                     int max_T, at_stream_t stream_, int32_t* status_dev) {
+int generate_lockstep(const char* who, at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
+                      const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev,
+                      size_t state_bytes, int max_T, const FineHistory& hi, at_stream_t stream_, int32_t* status_dev) {
     AT_REQUIRE(h && h->finalized, "the model is not finalized");
     AT_REQUIRE(B >= 1 && B <= FINE_MAX_B, "B must be 1 to 64");
     AT_REQUIRE(coarse_dev && lens && out_dev, "null pointer");
@@ -505,32 +578,41 @@ int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, cons
     AT_REQUIRE(t_stride >= 1 && t_stride <= FINE_MAX_T, "t_stride must be 1 to 262144");
     const int W = h->block;
     FineRowMap map[FINE_MAX_B];
-    int n_most = 0;
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 1 || lens[b] > t_stride || lens[b] > max_T) {
-            set_error("at_fine_generate: the length of row " + std::to_string(b) + " must be 1 to min(t_stride, max_T)");
+            set_error(std::string(who) + ": the length of row " + std::to_string(b) + " must be 1 to min(t_stride, max_T)");
             return -1;
         }
-        const int n = fine_windows(lens[b], W);
+    }
+    if (int rc = place_history(who, hi, B, W, map)) return rc;
+    int n_most = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = fine_windows(lens[b], W, map[b].h);
         n_most = n > n_most ? n : n_most;
     }
     AT_REQUIRE(n_max >= n_most, "n_max must hold the windows of the longest row: at_fine_num_windows(h, T)");
     AT_REQUIRE((long long)B * n_max <= INT32_MAX, "B * n_max must fit 31 bits");
-    for (int b = 0; b < B; ++b) map[b] = FineRowMap{(long long)b * 2 * t_stride, (long long)b * FINE_CODES * t_stride, t_stride, b * n_max};
-    const FineState s = carve_state(state_dev, B, max_T, W, h->embd);
+    for (int b = 0; b < B; ++b) {
+        map[b].src = (long long)b * 2 * t_stride;
+        map[b].dst = (long long)b * FINE_CODES * t_stride;
+        map[b].stride = t_stride;
+        map[b].draw0 = b * n_max;
+    }
+    const FineState s = carve_state(state_dev, B, max_T, hi.max_hist, W, h->embd);
     AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_state_bytes(h, B, max_T)");
     // ---- nothing above touched the device
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
     FineCall c{};
-    c.coarse = coarse_dev; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
+    c.coarse = coarse_dev; c.hist = hi.dev; c.hstride = hi.stride; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
     c.logits_out = logits_out_dev; c.window_ids = window_ids_dev; c.status = status_dev;
     return run_passes(h, s, lens, B, B, map, c, (hipStream_t)stream_);
 }
 
-int at_fine_generate_queue(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy, const float* uniforms_dev,
-                           int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T, int slots,
-                           int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
+int generate_queue(const char* who, at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy,
+                   const float* uniforms_dev, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T,
+                   int slots, const FineHistory& hi, int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_,
+                   int32_t* status_dev) {
     AT_REQUIRE(h && h->finalized, "the model is not finalized");
     AT_REQUIRE(n_rows >= 1 && n_rows <= FINE_MAX_QUEUE, "n_rows must be 1 to 4096");
     AT_REQUIRE(slots >= 1 && slots <= FINE_MAX_B, "slots must be 1 to 64");
@@ -543,27 +625,71 @@ int at_fine_generate_queue(at_fine_t* h, const int32_t* coarse_dev, const int32_
     AT_REQUIRE(trace_cap >= 0 && (trace != nullptr || trace_cap == 0), "trace_cap must be 0 without a trace, and never negative");
     const int W = h->block;
     std::vector<FineRowMap> map((size_t)n_rows);
-    long long off = 0, woff = 0;   // frames and windows of the rows before
     for (int b = 0; b < n_rows; ++b) {
         if (lens[b] < 1 || lens[b] > max_T) {
-            set_error("at_fine_generate_queue: the length of row " + std::to_string(b) + " must be 1 to max_T");
+            set_error(std::string(who) + ": the length of row " + std::to_string(b) + " must be 1 to max_T");
             return -1;
         }
-        map[b] = FineRowMap{2 * off, FINE_CODES * off, lens[b], (int)woff};
+    }
+    if (int rc = place_history(who, hi, n_rows, W, map.data())) return rc;
+    long long off = 0, woff = 0;   // frames and windows of the rows before
+    for (int b = 0; b < n_rows; ++b) {
+        map[b].src = 2 * off;
+        map[b].dst = FINE_CODES * off;
+        map[b].stride = lens[b];
+        map[b].draw0 = (int)woff;
         off += lens[b];
-        woff += fine_windows(lens[b], W);
+        woff += fine_windows(lens[b], W, map[b].h);
     }
     AT_REQUIRE(woff <= INT32_MAX, "the rows' windows must number fewer than 2^31");
-    const FineState s = carve_state(state_dev, slots, max_T, W, h->embd);
+    const FineState s = carve_state(state_dev, slots, max_T, hi.max_hist, W, h->embd);
     AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_queue_state_bytes(h, slots, max_T)");
     // ---- nothing above touched the device
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
     FineCall c{};
-    c.coarse = coarse_dev; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
+    c.coarse = coarse_dev; c.hist = hi.dev; c.hstride = hi.stride; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
     c.logits_out = logits_out_dev; c.window_ids = window_ids_dev; c.status = status_dev;
     c.trace = trace; c.trace_cap = trace_cap; c.n_passes = n_passes; c.placement = placement;
     return run_passes(h, s, lens, n_rows, slots, map.data(), c, (hipStream_t)stream_);
+}
+
+}  // namespace
+
+extern "C" {
+
+// The queue with slots = B: every row is admitted in pass 0, and pass k is window k of every row that has one, in row order.
+int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
+                     const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
+                     int max_T, at_stream_t stream_, int32_t* status_dev) {
+    return generate_lockstep("at_fine_generate", h, coarse_dev, t_stride, lens, B, temperature, greedy, uniforms_dev, n_max, out_dev, logits_out_dev,
+                             window_ids_dev, state_dev, state_bytes, max_T, FineHistory{}, stream_, status_dev);
+}
+
+int at_fine_generate_hist(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, const int32_t* hist_dev, int h_stride,
+                          const int32_t* hist_lens, int n_hist, const int32_t* hist_of_row, int max_hist, float temperature, int greedy,
+                          const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev,
+                          size_t state_bytes, int max_T, at_stream_t stream_, int32_t* status_dev) {
+    return generate_lockstep("at_fine_generate_hist", h, coarse_dev, t_stride, lens, B, temperature, greedy, uniforms_dev, n_max, out_dev, logits_out_dev,
+                             window_ids_dev, state_dev, state_bytes, max_T, FineHistory{hist_dev, h_stride, hist_lens, n_hist, hist_of_row, max_hist}, stream_,
+                             status_dev);
+}
+
+int at_fine_generate_queue(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy, const float* uniforms_dev,
+                           int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T, int slots,
+                           int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
+    return generate_queue("at_fine_generate_queue", h, coarse_dev, lens, n_rows, temperature, greedy, uniforms_dev, out_dev, logits_out_dev, window_ids_dev,
+                          state_dev, state_bytes, max_T, slots, FineHistory{}, trace, trace_cap, n_passes, placement, stream_, status_dev);
+}
+
+int at_fine_generate_queue_hist(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, const int32_t* hist_dev, int h_stride,
+                                const int32_t* hist_lens, int n_hist, const int32_t* hist_of_row, int max_hist, float temperature, int greedy,
+                                const float* uniforms_dev, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
+                                int max_T, int slots, int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_,
+                                int32_t* status_dev) {
+    return generate_queue("at_fine_generate_queue_hist", h, coarse_dev, lens, n_rows, temperature, greedy, uniforms_dev, out_dev, logits_out_dev,
+                          window_ids_dev, state_dev, state_bytes, max_T, slots, FineHistory{hist_dev, h_stride, hist_lens, n_hist, hist_of_row, max_hist},
+                          trace, trace_cap, n_passes, placement, stream_, status_dev);
 }
 
 }  // extern "C"

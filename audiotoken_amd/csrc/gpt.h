@@ -20,23 +20,28 @@ constexpr int GPT_PASS_DONE = 4;       // done[] of a row whose non-final window
 constexpr int GPT_MAX_SOURCE = 65536;  // source ids of one row of at_gpt_generate_long
 
 // The long form's schedule: windows of a source of N ids at window S and hop H; window k reads source ids [k H, k H + min(S, N - k H)).
-inline int gpt_long_windows(int N, int S, int H) { return N <= S ? 1 : (N - S + H - 1) / H + 1; }
+// A row with a voice prompt of pv ids (0: none) follows the same schedule on the concatenated source, prompt ids then source ids.
+inline int gpt_long_windows(int N, int S, int H, int pv = 0) { return pv + N <= S ? 1 : (pv + N - S + H - 1) / H + 1; }
+// what a voice prompt must satisfy: even, 2 <= pv <= S - H, so that no window's prompt exceeds S + 1 + r (S - H) tokens
+inline bool gpt_voice_prompt_ok(int pv, int N, int S, int H) { return pv >= 2 && pv % 2 == 0 && pv <= S - H && N >= 1 && (int64_t)pv + N <= GPT_MAX_SOURCE; }
 
 // Window k of a source of N ids: n_ids source ids, `carry` ids of the source's own stream behind them and INFER between make the P prompt tokens; the
 // window's step 0 lies at stream_base; it runs `budget` steps (a final window: at most). The one statement of this arithmetic for the three entry points,
 // the scheduler below and tools/gpt_queue_args.hip; acoustic_windows / window_steps in semantic_decoder.py are its Python twins.
+// With a voice prompt of pv ids, N stays the source's own count: window k reads ids [k H, ..) of the concatenated source, window 0 carries the prompt's
+// r pv coarse ids, which are given and not generated, and stream_base is the RESULT position: the stream position minus r pv.
 struct GptWindow {
     int n_ids, P, budget, carry, stream_base;
     bool final_window;
 };
-inline GptWindow gpt_window(int N, int k, int S, int H, int r, int max_new, int block) {
+inline GptWindow gpt_window(int N, int k, int S, int H, int r, int max_new, int block, int pv = 0) {
     GptWindow w;
-    w.carry = k > 0 ? r * (S - H) : 0;
-    w.final_window = k == gpt_long_windows(N, S, H) - 1;
-    w.n_ids = w.final_window ? N - k * H : S;
+    w.carry = k > 0 ? r * (S - H) : r * pv;
+    w.final_window = k == gpt_long_windows(N, S, H, pv) - 1;
+    w.n_ids = w.final_window ? pv + N - k * H : S;
     w.P = w.n_ids + 1 + w.carry;
     w.budget = w.final_window ? (max_new < block - w.P ? max_new : block - w.P) : r * S - w.carry;
-    w.stream_base = r * k * H + w.carry;
+    w.stream_base = r * k * H + w.carry - r * pv;
     return w;
 }
 // What a set of sources needs: positions of a cache row (the longest window with its new ids) and ids of a row of the caller's stream arrays
@@ -44,11 +49,13 @@ struct GptExtent {
     int need_len = 0;
     int64_t need_stride = 0;
 };
-inline GptExtent gpt_extent(const int32_t* src_len, int n_src, int S, int H, int r, int max_new, int block) {
+// (need_stride counts result ids; pv NULL or the voice prompt length of each source)
+inline GptExtent gpt_extent(const int32_t* src_len, int n_src, int S, int H, int r, int max_new, int block, const int32_t* pv = nullptr) {
     GptExtent e;
     for (int i = 0; i < n_src; ++i) {
-        const int n = gpt_long_windows(src_len[i], S, H);
-        const GptWindow w = gpt_window(src_len[i], n - 1, S, H, r, max_new, block);
+        const int v = pv ? pv[i] : 0;
+        const int n = gpt_long_windows(src_len[i], S, H, v);
+        const GptWindow w = gpt_window(src_len[i], n - 1, S, H, r, max_new, block, v);
         const int64_t end = (int64_t)w.stream_base + w.budget;
         e.need_stride = end > e.need_stride ? end : e.need_stride;
         e.need_len = w.P + w.budget > e.need_len ? w.P + w.budget : e.need_len;
@@ -79,9 +86,10 @@ struct GptQueueTick {
 
 class GptQueueSchedule {
   public:
-    // src_len must outlive the schedule; every argument has been validated by the caller (tick_tokens >= slots + the longest prompt)
-    GptQueueSchedule(const int32_t* src_len, int n_src, int S, int H, int r, int max_new, int block, int slots, int tick_tokens)
-        : len_(src_len), n_src_(n_src), S_(S), H_(H), r_(r), max_new_(max_new), block_(block), slots_(slots), tick_tokens_(tick_tokens),
+    // src_len (and pv: NULL or each source's voice prompt length) must outlive the schedule; every argument has been validated by the caller
+    // (tick_tokens >= slots + the longest prompt)
+    GptQueueSchedule(const int32_t* src_len, int n_src, int S, int H, int r, int max_new, int block, int slots, int tick_tokens, const int32_t* pv = nullptr)
+        : len_(src_len), pv_(pv), n_src_(n_src), S_(S), H_(H), r_(r), max_new_(max_new), block_(block), slots_(slots), tick_tokens_(tick_tokens),
           placement_((size_t)n_src * 3, -1) {
         for (int j = 0; j < GPT_MAX_B; ++j) slot_[j] = Slot{};
     }
@@ -106,7 +114,7 @@ class GptQueueSchedule {
         for (int j = 0; j < slots_; ++j) {
             Slot& s = slot_[j];
             if (s.src < 0 || s.running) continue;
-            const GptWindow w = gpt_window(len_[s.src], s.k, S_, H_, r_, max_new_, block_);
+            const GptWindow w = gpt_window(len_[s.src], s.k, S_, H_, r_, max_new_, block_, pv_ ? pv_[s.src] : 0);
             if (t->tokens() + w.P > tick_tokens_) break;   // it waits, and so does every slot after it
             t->start[t->n_start++] = GptQueueStart{j, s.src, s.k, w.final_window ? 1 : 0, w.n_ids, w.P};
             t->prefill_tokens += w.P;
@@ -157,7 +165,7 @@ class GptQueueSchedule {
         placement_[3 * (size_t)slot_[j].src + 2] = tick_;
         slot_[j] = Slot{};
     }
-    const int32_t* len_;
+    const int32_t *len_, *pv_;
     int n_src_, S_, H_, r_, max_new_, block_, slots_, tick_tokens_;
     int next_src_ = 0, n_ticks_ = 0, tick_ = 0;   // tick_: the index of the tick next() made last
     Slot slot_[GPT_MAX_B];

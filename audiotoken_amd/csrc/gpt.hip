@@ -57,6 +57,9 @@ struct Rules {
     int S, H, r, semantic_offset, semantic_vocab, infer_token, stop_token, max_new, block;
     Allow mid[2], last[2];           // even / odd steps of a non-final and of a final window
     int* status;
+    // the voice prompt table, NULL without one: entry e has semantic ids vp_sem[e][vp_stride] and coarse codes vp_codes[e][2][vf_stride]
+    const int *vp_sem, *vp_codes;
+    int vp_stride, vf_stride, acoustic_offset, codebook_size;
 };
 struct TickPlan {
     StepSlots steps;                      // the list: steps.n step tokens, then the prompts; R tokens in all
@@ -64,16 +67,19 @@ struct TickPlan {
     int off[GPT_MAX_B + 1];               // start j's prompt tokens are the list's [off[j], off[j + 1]); off[0] = steps.n
     int src[GPT_MAX_B], k[GPT_MAX_B];     // start j: window k[j] of source src[j]
     unsigned char slot[GPT_MAX_B];        //          in cache row slot[j]
+    unsigned short pv[GPT_MAX_B];         //          after a voice prompt of pv[j] ids (0: none),
+    short entry[GPT_MAX_B];               //          entry[j] of the prompt table
     unsigned long long final_mask;        // bit j: start j is its source's last window
-    void start(int slot_, int src_, int k_, int P, bool final_window) {
+    void start(int slot_, int src_, int k_, int P, bool final_window, int pv_ = 0, int entry_ = 0) {
         const int j = n_start++;
         if (j == 0) off[0] = steps.n;
         off[j + 1] = off[j] + P;
-        src[j] = src_; k[j] = k_; slot[j] = (unsigned char)slot_;
+        src[j] = src_; k[j] = k_; slot[j] = (unsigned char)slot_; pv[j] = (unsigned short)pv_; entry[j] = (short)entry_;
         if (final_window) final_mask |= 1ull << j;
         R = off[j + 1];
     }
 };
+constexpr int GPT_MAX_VOICE_PROMPTS = 4096;   // entries of a prompt table: what TickPlan::entry holds (a prompt's length is below GPT_MAX_BLOCK)
 // rows 0 .. B - 1 step: every tick of a lockstep generator after the one in which they began
 TickPlan lockstep_steps(int B) {
     TickPlan p{};
@@ -87,16 +93,21 @@ TickPlan lockstep_steps(int B) {
 // counter, its entry of the sampling list and its rule for the sampler. A prompt that fills the block leaves no room for a new token: the row is born
 // finished. A row either steps or begins in a tick, never both, and the step tokens are the embedding's, so no word is read by one thread and written
 // by another. A source id outside [0, semantic_vocab) is clamped and reported in bit 0 of *status (a raw id: by the embedding, against the vocabulary).
+// A start with a voice prompt (p.pv[j] ids of table entry p.entry[j]) walks the concatenated source: index c below pv is the prompt's id,
+// above it src[c - pv]; a carry id at stream position sp below r pv is the prompt's code (sp & 1 its code book, sp >> 1 its frame; outside
+// [0, codebook_size) clamped, bit 1 of *status), above it the row's own out_ids[sp - r pv]. The sampler's base is the result position.
+static_assert(sizeof(TickPlan) + sizeof(Rules) + sizeof(GptState) + 4 * sizeof(void*) <= 4096, "gpt_begin_kernel's arguments must stay under the launch limit");
 __global__ void gpt_begin_kernel(TickPlan p, Rules q, GptState s, const int* out_ids, int out_stride, int* out_len, int* finish) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x, i = p.steps.n + t;
     if (i < p.R) {
         int j = 0;
         while (j + 1 < p.n_start && p.off[j + 1] <= i) ++j;
-        const int b = p.src[j], k = p.k[j], carry = k > 0 ? q.r * (q.S - q.H) : 0;
+        const int b = p.src[j], k = p.k[j], pv = p.pv[j], carry = k > 0 ? q.r * (q.S - q.H) : q.r * pv;
         const int pos = i - p.off[j], P = p.off[j + 1] - p.off[j], n_src = q.raw ? P : P - 1 - carry;
         int id;
         if (pos < n_src) {
-            id = q.src[(size_t)b * q.src_stride + k * q.H + pos];
+            const int c = k * q.H + pos;
+            id = c < pv ? q.vp_sem[(size_t)p.entry[j] * q.vp_stride + c] : q.src[(size_t)b * q.src_stride + c - pv];
             if (!q.raw) {
                 if (id < 0 || id >= q.semantic_vocab) {
                     if (q.status) atomicOr(q.status, 1);
@@ -107,14 +118,24 @@ __global__ void gpt_begin_kernel(TickPlan p, Rules q, GptState s, const int* out
         } else if (pos == n_src) {
             id = q.infer_token;
         } else {
-            id = out_ids[(size_t)b * out_stride + q.r * k * q.H + (pos - n_src - 1)];
+            const int sp = q.r * k * q.H + (pos - n_src - 1);
+            if (sp < q.r * pv) {
+                id = q.vp_codes[((size_t)p.entry[j] * 2 + (sp & 1)) * q.vf_stride + (sp >> 1)];
+                if (id < 0 || id >= q.codebook_size) {
+                    if (q.status) atomicOr(q.status, 2);
+                    id = min(max(id, 0), q.codebook_size - 1);
+                }
+                id += q.acoustic_offset + (sp & 1) * q.codebook_size;
+            } else {
+                id = out_ids[(size_t)b * out_stride + sp - q.r * pv];
+            }
         }
         s.tok_row[i] = p.slot[j];
         s.tok_pos[i] = pos;
         s.tok_id[i] = id;
     }
     if (t < p.n_start) {
-        const int P = p.off[t + 1] - p.off[t], b = p.src[t], k = p.k[t], slot = p.slot[t], carry = k > 0 ? q.r * (q.S - q.H) : 0;
+        const int P = p.off[t + 1] - p.off[t], b = p.src[t], k = p.k[t], slot = p.slot[t], carry = k > 0 ? q.r * (q.S - q.H) : q.r * p.pv[t];
         const bool last = (p.final_mask >> t) & 1ull;
         const int born = P >= q.block ? GPT_FINISH_BLOCK : GPT_RUNNING;
         s.len[slot] = P;
@@ -125,7 +146,7 @@ __global__ void gpt_begin_kernel(TickPlan p, Rules q, GptState s, const int* out
         s.samp_slot[p.steps.n + t] = slot;
         SampleRow w;
         w.out_row = b;
-        w.base = q.r * k * q.H + carry;
+        w.base = q.r * k * q.H + carry - q.r * p.pv[t];
         w.budget = last ? min(q.max_new, q.block - P) : q.r * q.S - carry;
         w.stop_token = last ? q.stop_token : -1;
         w.final_window = last ? 1 : 0;
@@ -185,6 +206,7 @@ int check_long_rules(const at_gpt* h, int S, int H, int r, const int32_t* src_de
     q.src = src_dev; q.src_stride = src_stride; q.status = status_dev;
     q.S = S; q.H = H; q.r = r; q.semantic_offset = semantic_offset; q.semantic_vocab = semantic_vocab; q.infer_token = infer_token;
     q.stop_token = stop_token < 0 ? -1 : stop_token; q.max_new = max_new; q.block = block;
+    q.acoustic_offset = acoustic_offset; q.codebook_size = codebook_size;
     q.mid[0] = Allow{1, acoustic_offset, acoustic_offset + codebook_size, 0, 0};
     q.mid[1] = Allow{1, acoustic_offset + codebook_size, acoustic_offset + 2 * codebook_size, 0, 0};
     q.last[0] = q.mid[0];
@@ -194,6 +216,50 @@ int check_long_rules(const at_gpt* h, int S, int H, int r, const int32_t* src_de
     return 0;
 }
 
+// A call's voice prompts as the caller hands them over: the table on the device, the lengths and each source's entry (-1: none) on the host
+struct VoiceTable {
+    const int32_t *sem = nullptr, *codes = nullptr, *len = nullptr, *of_src = nullptr;
+    int p_stride = 0, f_stride = 0, n = 0;
+    bool on = false;   // a prompted entry point was called
+};
+// The checks of a prompted call, and per source its prompt's length (0: none) and entry: pv and entry are left empty when no source has a prompt
+int check_voice(const char* who, const VoiceTable& vt, const int32_t* src_len, int n_src, int S, int H, int r, std::vector<int32_t>* pv, std::vector<int32_t>* entry) {
+    if (!vt.on) return 0;
+    AT_REQUIRE(vt.n >= 0 && vt.n <= GPT_MAX_VOICE_PROMPTS, "n_prompts must be 0 to 4096");
+    AT_REQUIRE(vt.of_src != nullptr, "null prompt_of_src");
+    AT_REQUIRE(vt.n == 0 || (vt.sem && vt.codes && vt.len), "null prompt table");
+    AT_REQUIRE(vt.n == 0 || (vt.p_stride >= 1 && vt.f_stride >= 1), "p_stride and f_stride must be at least 1");
+    for (int e = 0; e < vt.n; ++e) {
+        const int P = vt.len[e];
+        if (!(P >= 2 && P % 2 == 0 && P <= S - H)) {
+            set_error(std::string(who) + ": the length of prompt " + std::to_string(e) + " must be even, 2 to S - H");
+            return -1;
+        }
+        if (P > vt.p_stride || (int64_t)r * P / 2 > vt.f_stride) {
+            set_error(std::string(who) + ": prompt " + std::to_string(e) + " does not fit p_stride ids and f_stride frames (r P / 2)");
+            return -1;
+        }
+    }
+    bool any = false;
+    for (int i = 0; i < n_src; ++i) {
+        const int e = vt.of_src[i];
+        if (e < -1 || e >= vt.n) {
+            set_error(std::string(who) + ": prompt_of_src of source " + std::to_string(i) + " must be -1 or an entry of the table");
+            return -1;
+        }
+        if (e >= 0 && !gpt_voice_prompt_ok(vt.len[e], src_len[i], S, H)) {
+            set_error(std::string(who) + ": source " + std::to_string(i) + " with its prompt exceeds 65536 ids");
+            return -1;
+        }
+        any = any || e >= 0;
+    }
+    if (!any) return 0;
+    pv->assign(n_src, 0);
+    entry->assign(n_src, 0);
+    for (int i = 0; i < n_src; ++i)
+        if (vt.of_src[i] >= 0) { (*pv)[i] = vt.len[vt.of_src[i]]; (*entry)[i] = vt.of_src[i]; }
+    return 0;
+}
 
 const GptHostTensor* staged(const at_gpt* h, const std::string& name) {
     auto it = h->staged.find(name);
@@ -371,6 +437,14 @@ int at_gpt_long_num_windows(int N, int S, int H) {
     return gpt_long_windows(N, S, H);
 }
 
+int at_gpt_long_num_windows_prompted(int P, int N, int S, int H) {
+    if (!(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0 && H <= S && gpt_voice_prompt_ok(P, N, S, H))) {
+        set_error("at_gpt_long_num_windows_prompted: S and H must be even with 2 <= H <= S, P even with 2 <= P <= S - H, N at least 1, P + N at most 65536");
+        return 0;
+    }
+    return gpt_long_windows(N, S, H, P);
+}
+
 size_t at_gpt_long_state_bytes(const at_gpt_t* h, int B, int max_len) {
     if (!(h && h->finalized)) { set_error("at_gpt_long_state_bytes: the model is not finalized"); return 0; }
     if (!(B >= 1 && B <= GPT_MAX_B)) { set_error("at_gpt_long_state_bytes: B must be 1 to 64"); return 0; }
@@ -378,9 +452,9 @@ size_t at_gpt_long_state_bytes(const at_gpt_t* h, int B, int max_len) {
     return carve_state(nullptr, B, max_len, B * max_len, h->vocab, h->n_layer).bytes;
 }
 
-int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, int S, int H, int r, int semantic_offset,
-                         int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
-                         const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
+static int generate_long(const char* who, const VoiceTable& vt, at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, int S, int H, int r,
+                         int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature,
+                         int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
                          float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream_, int32_t* status_dev) {
     AT_REQUIRE(h && h->finalized, "the model is not finalized");
     AT_REQUIRE(B >= 1 && B <= GPT_MAX_B, "B must be 1 to 64");
@@ -394,18 +468,23 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
     // ---- the schedule: rows in descending order of their window counts, so that the rows of pass k are the first Bk of them
     int n_win[GPT_MAX_B], order[GPT_MAX_B];
     int n_max = 0;
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < B; ++b)
         if (src_len[b] < 1 || src_len[b] > src_stride || src_len[b] > GPT_MAX_SOURCE) {
-            set_error("at_gpt_generate_long: src_len of row " + std::to_string(b) + " must be 1 to min(src_stride, 65536)");
+            set_error(std::string(who) + ": src_len of row " + std::to_string(b) + " must be 1 to min(src_stride, 65536)");
             return -1;
         }
-        const int n = n_win[b] = gpt_long_windows(src_len[b], S, H);
+    std::vector<int32_t> pv, entry;
+    if (int rc = check_voice(who, vt, src_len, B, S, H, r, &pv, &entry)) return rc;
+    const bool voiced = !pv.empty();
+    q.vp_sem = vt.sem; q.vp_codes = vt.codes; q.vp_stride = vt.p_stride; q.vf_stride = vt.f_stride;
+    for (int b = 0; b < B; ++b) {
+        const int n = n_win[b] = gpt_long_windows(src_len[b], S, H, voiced ? pv[b] : 0);
         n_max = n > n_max ? n : n_max;
         int at = b;
         while (at > 0 && n_win[order[at - 1]] < n) { order[at] = order[at - 1]; --at; }
         order[at] = b;
     }
-    const auto [need_len, need_stride] = gpt_extent(src_len, B, S, H, r, max_new, block);
+    const auto [need_len, need_stride] = gpt_extent(src_len, B, S, H, r, max_new, block, voiced ? pv.data() : nullptr);
     AT_REQUIRE(out_stride >= need_stride && u_stride >= need_stride, "out_stride and u_stride must hold the longest row's stream");
     AT_REQUIRE(max_len >= need_len && max_len <= block, "max_len must hold the longest window with its new ids and not exceed the block size");
     const GptState s = carve_state(state_dev, B, max_len, B * max_len, V, h->n_layer);
@@ -421,8 +500,8 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
         int Bk = 0, steps = 0, mid_steps = 0;
         while (Bk < B && n_win[order[Bk]] > k) {
             const int b = order[Bk];
-            const GptWindow w = gpt_window(src_len[b], k, S, H, r, max_new, block);
-            begin.start(Bk, b, k, w.P, w.final_window);
+            const GptWindow w = gpt_window(src_len[b], k, S, H, r, max_new, block, voiced ? pv[b] : 0);
+            begin.start(Bk, b, k, w.P, w.final_window, voiced ? pv[b] : 0, voiced ? entry[b] : 0);
             if (!w.final_window) mid_steps = w.budget > mid_steps ? w.budget : mid_steps;
             steps = w.budget > steps ? w.budget : steps;
             ++Bk;
@@ -441,6 +520,28 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
     return 0;
 }
 
+int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, int S, int H, int r, int semantic_offset,
+                         int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                         const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
+                         float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev) {
+    return generate_long("at_gpt_generate_long", VoiceTable{}, h, src_dev, src_stride, src_len, B, S, H, r, semantic_offset, semantic_vocab, infer_token, acoustic_offset,
+                         codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev, finish_dev,
+                         logits_out_dev, state_dev, state_bytes, max_len, stream, status_dev);
+}
+
+int at_gpt_generate_long_prompted(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, const int32_t* prompt_sem_dev, int p_stride,
+                                  const int32_t* prompt_codes_dev, int f_stride, const int32_t* prompt_len, int n_prompts, const int32_t* prompt_of_src, int S, int H,
+                                  int r, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
+                                  float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
+                                  int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev) {
+    VoiceTable vt;
+    vt.sem = prompt_sem_dev; vt.codes = prompt_codes_dev; vt.len = prompt_len; vt.of_src = prompt_of_src;
+    vt.p_stride = p_stride; vt.f_stride = f_stride; vt.n = n_prompts; vt.on = true;
+    return generate_long("at_gpt_generate_long_prompted", vt, h, src_dev, src_stride, src_len, B, S, H, r, semantic_offset, semantic_vocab, infer_token, acoustic_offset,
+                         codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev, finish_dev,
+                         logits_out_dev, state_dev, state_bytes, max_len, stream, status_dev);
+}
+
 size_t at_gpt_queue_state_bytes(const at_gpt_t* h, int slots, int max_len, int tick_tokens) {
     if (!(h && h->finalized)) { set_error("at_gpt_queue_state_bytes: the model is not finalized"); return 0; }
     if (!(slots >= 1 && slots <= GPT_MAX_B)) { set_error("at_gpt_queue_state_bytes: slots must be 1 to 64"); return 0; }
@@ -452,11 +553,11 @@ size_t at_gpt_queue_state_bytes(const at_gpt_t* h, int slots, int max_len, int t
     return carve_state(nullptr, slots, max_len, tick_tokens, h->vocab, h->n_layer).bytes;
 }
 
-int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, int S, int H, int r, int semantic_offset,
-                          int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
-                          const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
-                          float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace, int trace_cap,
-                          int32_t* n_ticks, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
+static int generate_queue(const char* who, const VoiceTable& vt, at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, int S, int H,
+                          int r, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
+                          float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
+                          int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace,
+                          int trace_cap, int32_t* n_ticks, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
     AT_REQUIRE(h && h->finalized, "the model is not finalized");
     AT_REQUIRE(n_src >= 1 && n_src <= GPT_MAX_QUEUE, "n_src must be 1 to 4096");
     AT_REQUIRE(slots >= 1 && slots <= GPT_MAX_B, "slots must be 1 to 64");
@@ -470,10 +571,14 @@ int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, c
         return rc;
     for (int i = 0; i < n_src; ++i)
         if (src_len[i] < 1 || src_len[i] > src_stride || src_len[i] > GPT_MAX_SOURCE) {
-            set_error("at_gpt_generate_queue: src_len of source " + std::to_string(i) + " must be 1 to min(src_stride, 65536)");
+            set_error(std::string(who) + ": src_len of source " + std::to_string(i) + " must be 1 to min(src_stride, 65536)");
             return -1;
         }
-    const auto [need_len, need_stride] = gpt_extent(src_len, n_src, S, H, r, max_new, block);
+    std::vector<int32_t> pv, entry;
+    if (int rc = check_voice(who, vt, src_len, n_src, S, H, r, &pv, &entry)) return rc;
+    const bool voiced = !pv.empty();
+    q.vp_sem = vt.sem; q.vp_codes = vt.codes; q.vp_stride = vt.p_stride; q.vf_stride = vt.f_stride;
+    const auto [need_len, need_stride] = gpt_extent(src_len, n_src, S, H, r, max_new, block, voiced ? pv.data() : nullptr);
     AT_REQUIRE(out_stride >= need_stride && u_stride >= need_stride, "out_stride and u_stride must hold the longest source's stream");
     AT_REQUIRE(max_len >= need_len && max_len <= block, "max_len must hold the longest window with its new ids and not exceed the block size");
     AT_REQUIRE(tick_tokens >= slots + max_len && tick_tokens <= GPT_MAX_TICK_TOKENS, "tick_tokens must be at least slots + max_len (one window always fits) and at most 65600");
@@ -484,13 +589,16 @@ int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, c
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
     hipStream_t stream = (hipStream_t)stream_;
     const SampleArgs sa = generation_args(h, s, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev, max_new);
-    GptQueueSchedule schedule(src_len, n_src, S, H, r, max_new, block, slots, tick_tokens);
+    GptQueueSchedule schedule(src_len, n_src, S, H, r, max_new, block, slots, tick_tokens, voiced ? pv.data() : nullptr);
     GptQueueTick t;
     while (schedule.next(&t)) {
         TickPlan p{};
         p.steps.n = p.R = t.n_step;
         for (int i = 0; i < t.n_step; ++i) p.steps.slot[i] = (unsigned char)t.step_slot[i];
-        for (int j = 0; j < t.n_start; ++j) p.start(t.start[j].slot, t.start[j].src, t.start[j].k, t.start[j].P, t.start[j].final_window != 0);
+        for (int j = 0; j < t.n_start; ++j) {
+            const GptQueueStart& st = t.start[j];
+            p.start(st.slot, st.src, st.k, st.P, st.final_window != 0, voiced ? pv[st.src] : 0, voiced ? entry[st.src] : 0);
+        }
         if (int rc = run_tick(h, s, p, q, sa, stream)) return rc;
         const int at = schedule.ticks() - 1;
         if (at < trace_cap) {   // a trace too small loses its tail, the run goes on
@@ -506,6 +614,30 @@ int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, c
     if (n_ticks) *n_ticks = schedule.ticks();
     if (placement) std::memcpy(placement, schedule.placement().data(), (size_t)n_src * 3 * sizeof(int32_t));
     return 0;
+}
+
+int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, int S, int H, int r, int semantic_offset,
+                          int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                          const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
+                          float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace, int trace_cap,
+                          int32_t* n_ticks, int32_t* placement, at_stream_t stream, int32_t* status_dev) {
+    return generate_queue("at_gpt_generate_queue", VoiceTable{}, h, src_dev, src_stride, src_len, n_src, S, H, r, semantic_offset, semantic_vocab, infer_token,
+                          acoustic_offset, codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev,
+                          finish_dev, logits_out_dev, state_dev, state_bytes, max_len, slots, tick_tokens, trace, trace_cap, n_ticks, placement, stream, status_dev);
+}
+
+int at_gpt_generate_queue_prompted(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, const int32_t* prompt_sem_dev, int p_stride,
+                                   const int32_t* prompt_codes_dev, int f_stride, const int32_t* prompt_len, int n_prompts, const int32_t* prompt_of_src, int S, int H,
+                                   int r, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
+                                   float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
+                                   int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens,
+                                   int32_t* trace, int trace_cap, int32_t* n_ticks, int32_t* placement, at_stream_t stream, int32_t* status_dev) {
+    VoiceTable vt;
+    vt.sem = prompt_sem_dev; vt.codes = prompt_codes_dev; vt.len = prompt_len; vt.of_src = prompt_of_src;
+    vt.p_stride = p_stride; vt.f_stride = f_stride; vt.n = n_prompts; vt.on = true;
+    return generate_queue("at_gpt_generate_queue_prompted", vt, h, src_dev, src_stride, src_len, n_src, S, H, r, semantic_offset, semantic_vocab, infer_token,
+                          acoustic_offset, codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev,
+                          finish_dev, logits_out_dev, state_dev, state_bytes, max_len, slots, tick_tokens, trace, trace_cap, n_ticks, placement, stream, status_dev);
 }
 
 }  // extern "C"

@@ -91,19 +91,32 @@ def default_window(config: HubertDecoderConfig, block: int):
     return S, (S // 2) // 2 * 2
 
 
-def acoustic_windows(N: int, S: int, H: int, r: int = 3, block: int = 1024):
+def check_prompt(P: int, N: int, S: int, H: int) -> None:
+    """What a voice prompt of ``P`` ids in front of a source of ``N`` must satisfy (``gpt_voice_prompt_ok`` in csrc/gpt.h)."""
+    if P < 2 or P % 2 or P > S - H:
+        raise ValueError(f"voice prompt: its length ({P}) must be even, 2 to window - hop ({S - H})")
+    if N < 1 or P + N > MAX_SOURCE_IDS:
+        raise ValueError(f"voice prompt: the prompt and the source have 1 + 2 to {MAX_SOURCE_IDS} ids together, got {P} + {N}")
+
+
+def acoustic_windows(N: int, S: int, H: int, r: int = 3, block: int = 1024, prompt: int = 0):
     """The long form's schedule for a source of ``N`` ids (csrc/gpt.h has the same arithmetic): a list of
     ``(source_start, source_len, carry, new_ids)``, one per window. Window k reads source ids ``[k H, k H + source_len)``, is prompted with the ``carry``
     stream ids ``[r k H, r k H + carry)`` the window before produced, and produces exactly ``new_ids`` ids from stream position ``r k H + carry`` on;
-    ``new_ids`` of the last window is None: it runs until STOP or its budget."""
+    ``new_ids`` of the last window is None: it runs until STOP or its budget.
+    After a voice prompt of ``prompt`` ids the schedule is that of the concatenated source, prompt ids then the ``N`` source ids, and all
+    positions are the concatenated source's and its stream's: window 0 carries the prompt's ``r * prompt`` given ids, stream positions ``[0, r * prompt)``."""
     check_windows(S, H, r, block)
     if N < 1 or N > MAX_SOURCE_IDS:
         raise ValueError(f"long form: a source has 1 to {MAX_SOURCE_IDS} ids, got {N}")
-    n = 1 if N <= S else -(-(N - S) // H) + 1
+    if prompt:
+        check_prompt(prompt, N, S, H)
+    M = prompt + N
+    n = 1 if M <= S else -(-(M - S) // H) + 1
     out = []
     for k in range(n):
-        carry = r * (S - H) if k else 0
-        out.append((k * H, min(S, N - k * H), carry, None if k == n - 1 else r * S - carry))
+        carry = r * (S - H) if k else r * prompt
+        out.append((k * H, min(S, M - k * H), carry, None if k == n - 1 else r * S - carry))
     return out
 
 
@@ -123,21 +136,22 @@ def window_steps(plan, max_new: int, block: int):
     return out
 
 
-def stream_extent(plans, S: int, r: int, max_new: int, block: int):
+def stream_extent(plans, S: int, r: int, max_new: int, block: int, prompts=None):
     """What a set of sources needs, from their ``acoustic_windows`` plans (``gpt_extent`` in csrc/gpt.h is the same arithmetic): ``(base, cap, longest)``,
     per source the stream position of its final window's step 0, the ids of the longest source's stream, and the positions of the longest window with
-    its new ids (a non-final window fills ``S + 1 + r S``)."""
+    its new ids (a non-final window fills ``S + 1 + r S``). ``prompts``: per source its voice prompt's length; ``base`` and ``cap`` count RESULT positions,
+    stream positions minus ``r`` times that length."""
     base, cap, longest = [], 0, 0
-    for plan in plans:
+    for i, plan in enumerate(plans):
         start, _, carry, _ = plan[-1]
         P, budget = window_steps(plan, max_new, block)[-1]
-        base.append(r * start + carry)
+        base.append(r * start + carry - r * (prompts[i] if prompts else 0))
         cap = max(cap, base[-1] + budget)
         longest = max(longest, P + budget, S + 1 + r * S if len(plan) > 1 else 0)
     return base, cap, longest
 
 
-def queue_ticks(lens, S: int, H: int, r: int, block: int, max_new: int, slots: int, tick_tokens: int, final_steps=None, detail: bool = False):
+def queue_ticks(lens, S: int, H: int, r: int, block: int, max_new: int, slots: int, tick_tokens: int, final_steps=None, detail: bool = False, prompts=None):
     """The generation queue's host scheduler (``GptQueueSchedule`` in csrc/gpt.h is the same arithmetic): sources of ``lens`` ids run §19's
     windows through ``slots`` cache rows. Waiting sources take empty slots in source order. A tick holds one step token of every slot that is mid-window
     and the whole prompt of every window admitted, in slot order, while the list stays within ``tick_tokens``; the first window that does not fit waits,
@@ -147,7 +161,7 @@ def queue_ticks(lens, S: int, H: int, r: int, block: int, max_new: int, slots: i
     ``(step tokens, windows started, prefill tokens, route)`` with route 1 above ``GEMM_ABOVE`` tokens, per source ``(slot, first tick, last tick)``.
     ``detail``: a third list, per tick ``(steps [(slot, source, window)], starts [(slot, source, window, prompt tokens)], polled, slots whose window waits)``."""
     n_src = len(lens)
-    plans = [window_steps(acoustic_windows(int(N), S, H, r, block), max_new, block) for N in lens]
+    plans = [window_steps(acoustic_windows(int(N), S, H, r, block, prompts[i] if prompts else 0), max_new, block) for i, N in enumerate(lens)]
     if not 1 <= slots <= MAX_SLOTS or not 1 <= n_src <= MAX_QUEUE_SOURCES:
         raise ValueError(f"queue: 1 to {MAX_SLOTS} slots and 1 to {MAX_QUEUE_SOURCES} sources, got {slots} and {n_src}")
     if tick_tokens < slots + max(P for plan in plans for P, _ in plan):
@@ -203,11 +217,12 @@ def queue_ticks(lens, S: int, H: int, r: int, block: int, max_new: int, slots: i
     return (ticks, placement, events) if detail else (ticks, placement)
 
 
-def queue_tick_bound(lens, S: int, H: int, r: int, block: int, max_new: int) -> int:
+def queue_tick_bound(lens, S: int, H: int, r: int, block: int, max_new: int, prompts=None) -> int:
     """No queue call runs more ticks than this, whatever ``slots``, ``tick_tokens`` and the final windows do: every tick either samples a step some window
     still needs (there are at most the windows' budgets of those) or holds only finished slots the host has not seen, which lasts less than ``CHECK_EVERY``
     ticks per source."""
-    return sum(sum(n for _, n in window_steps(acoustic_windows(int(N), S, H, r, block), max_new, block)) + CHECK_EVERY - 1 for N in lens)
+    return sum(sum(n for _, n in window_steps(acoustic_windows(int(N), S, H, r, block, prompts[i] if prompts else 0), max_new, block)) + CHECK_EVERY - 1
+               for i, N in enumerate(lens))
 
 
 def seeded_uniforms(seed: int, batch: int, max_new_tokens: int) -> np.ndarray:
@@ -295,6 +310,8 @@ class SemanticToAcoustic(LibHandle):
             ids_all = d_ids.cpu().to(torch.int64)
         if self.last_status() & 1:
             raise ValueError(bad_id)
+        if self.last_status() & 2:
+            raise ValueError("a voice prompt's code lies outside its code book")
         self.last_raw_ids = ids_all   # the whole [B, cap] buffer, -1 where nothing was written (tests)
         ids = [ids_all[b, :n[b]].clone() for b in range(B)]
         logits = None
@@ -327,7 +344,7 @@ class SemanticToAcoustic(LibHandle):
 
     def to_acoustic_long(self, tokens, window: Optional[int] = None, hop: Optional[int] = None, max_new_tokens: int = 1024, temperature: float = 0.8,
                          top_k: int = 100, seed: int = 0, uniforms: Optional[np.ndarray] = None, return_logits: bool = False,
-                         slots: Optional[int] = None, tick_tokens: Optional[int] = None) -> AcousticGeneration:
+                         slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None) -> AcousticGeneration:
         """``to_acoustic(constrain=True)`` for sources of any length up to 65536 ids: the source is walked in windows of ``window`` ids every
         ``hop`` ids (defaults: ``default_window``), each window prompted with the acoustic ids the window before produced for their overlap, all windows of up
         to 64 sources enqueued by one library call. Every window but a source's last produces exactly ``ids_per_source_token`` ids per source id and cannot
@@ -337,7 +354,11 @@ class SemanticToAcoustic(LibHandle):
         ``slots`` (1 to 64) runs the sources through the generation queue instead: 1 to 4096 of them share ``slots`` cache rows, each starts
         when a row is free and finishes on its own, and every source's result follows the same rule with the same draws, whatever its neighbours are.
         ``tick_tokens``: the most tokens one model pass may hold (at least ``slots`` + the longest window; default ``slots + 2`` windows). The result then
-        carries ``ticks`` and ``placement`` (``queue_ticks``)."""
+        carries ``ticks`` and ``placement`` (``queue_ticks``).
+        ``voice``: a ``VoicePrompt`` that every source continues, or a list with one (or None) per source. Such a source follows the schedule
+        of the prompt's ids followed by its own, its first window carrying the prompt's coarse codes as if the row had produced them; ``ids``, ``codes``,
+        ``logits`` and ``uniforms`` cover what was generated only, position 0 the first id after the prompt, while ``windows`` is the schedule of the
+        concatenated source. Prompts that are one object share one entry of the device's table."""
         cfg = self.config
         r, block = int(cfg.ids_per_source_token), self.block_size
         S = default_window(cfg, block)[0] if window is None else int(window)
@@ -359,9 +380,13 @@ class SemanticToAcoustic(LibHandle):
         if not 1 <= max_new <= 1024:
             raise ValueError(f"to_acoustic: max_new_tokens must be 1 to 1024, got {max_new}")
         srcs = [source_ids(t, cfg) for t in batch]
-        plans = [acoustic_windows(int(s.numel()), S, H, r, block) for s in srcs]   # refuses a bad window / hop / length before anything is launched
+        from .voice import voice_table
+        table = voice_table(voice, B, cfg.SEMANTIC_VOCAB_SIZE, cfg.codebook_size, r)   # None, or (sem [n, p], codes [n, 2, f], lens, entry of each source)
+        prompts = None if table is None else [int(table[2][e]) if e >= 0 else 0 for e in table[3]]
+        # refuses a bad window / hop / length / prompt before anything is launched
+        plans = [acoustic_windows(int(s.numel()), S, H, r, block, prompts[b] if prompts else 0) for b, s in enumerate(srcs)]
         lens = [int(s.numel()) for s in srcs]
-        base, cap, longest = stream_extent(plans, S, r, max_new, block)
+        base, cap, longest = stream_extent(plans, S, r, max_new, block, prompts)
         if uniforms is None:
             uniforms = seeded_uniforms(seed, B, max(max_new, cap))
         uniforms = np.ascontiguousarray(uniforms, dtype=np.float32)
@@ -381,7 +406,13 @@ class SemanticToAcoustic(LibHandle):
 
         def call(dev, d_src, d_u, d_ids, d_len, d_fin, d_logits):
             # what the two entry points share: the sources, the geometry, the token space, the sampling arguments and the caller's arrays
-            head = (self.handle, d_src.data_ptr(), stride, c_lens, B, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE, cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET,
+            vt, form = (), ""
+            if table is not None:   # the prompted forms take the table between the sources and the geometry
+                d_sem, d_codes = torch.from_numpy(table[0]).to(dev), torch.from_numpy(table[1]).to(dev)
+                n_p = len(table[2])
+                vt = (d_sem.data_ptr(), table[0].shape[1], d_codes.data_ptr(), table[1].shape[2], (C.c_int32 * n_p)(*table[2]), n_p, (C.c_int32 * B)(*table[3]))
+                form = "_prompted"
+            head = (self.handle, d_src.data_ptr(), stride, c_lens, B, *vt, S, H, r, cfg.SEMANTIC_OFFSET, cfg.SEMANTIC_VOCAB_SIZE, cfg.INFER_TOKEN, cfg.ACOUSTIC_OFFSET,
                     cfg.codebook_size, cfg.STOP_TOKEN, max_new, float(temperature), int(top_k), d_u.data_ptr(), uniforms.shape[1], d_ids.data_ptr(), cap,
                     d_len.data_ptr(), d_fin.data_ptr(), _cabi.ptr(d_logits))
             tail = (_cabi.current_stream_handle(dev), self._status.data_ptr())
@@ -389,19 +420,19 @@ class SemanticToAcoustic(LibHandle):
                 nbytes = int(self._fn("long_state_bytes")(self.handle, B, longest))
                 state = self._workspace(max(nbytes, 256))
                 self._status.zero_()
-                _cabi.check(self._fn("generate_long")(*head, state.data_ptr(), state.numel(), longest, *tail), "at_gpt_generate_long")
+                _cabi.check(self._fn("generate_long" + form)(*head, state.data_ptr(), state.numel(), longest, *tail), "at_gpt_generate_long" + form)
                 return
             nbytes = int(self._fn("queue_state_bytes")(self.handle, slots, longest, tick_tokens))
             if nbytes == 0:
                 raise ValueError(_cabi.last_error())
             state = self._workspace(nbytes)
             self._status.zero_()
-            cap_ticks = min(queue_tick_bound(lens, S, H, r, block, max_new), 1 << 20)   # past a million ticks the trace loses its tail
+            cap_ticks = min(queue_tick_bound(lens, S, H, r, block, max_new, prompts), 1 << 20)   # past a million ticks the trace loses its tail
             c_trace = (C.c_int32 * (4 * cap_ticks))()
             c_n = C.c_int32(0)
             c_place = (C.c_int32 * (3 * B))()
-            _cabi.check(self._fn("generate_queue")(*head, state.data_ptr(), state.numel(), longest, slots, tick_tokens, c_trace, cap_ticks, C.byref(c_n),
-                                                   c_place, *tail), "at_gpt_generate_queue")
+            _cabi.check(self._fn("generate_queue" + form)(*head, state.data_ptr(), state.numel(), longest, slots, tick_tokens, c_trace, cap_ticks,
+                                                          C.byref(c_n), c_place, *tail), "at_gpt_generate_queue" + form)
             queue["ticks"] = [tuple(c_trace[4 * i:4 * i + 4]) for i in range(min(c_n.value, cap_ticks))]
             queue["placement"] = [tuple(c_place[3 * i:3 * i + 3]) for i in range(B)]
 

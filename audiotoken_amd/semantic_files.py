@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .decode_files import DecodeRun, _File
-from .fine_decoder import MAX_QUEUE_ROWS, N_PASSES, fine_windows
+from .fine_decoder import MAX_QUEUE_ROWS, N_PASSES, fine_windows, history_cells
 from .prefetch import ordered_map
 from .runs import RunLog
 from .semantic_decoder import MAX_SOURCE_IDS, acoustic_windows, check_windows, default_window, stream_extent
@@ -58,7 +58,7 @@ def output_stem(out: str, outdir: str) -> str:
     return os.path.splitext(os.path.relpath(out, start=str(outdir)))[0].replace(os.sep, "/")
 
 
-def read_semantic_file(path, vocab: int) -> np.ndarray:
+def read_semantic_file(path, vocab: int, max_ids: int = MAX_SOURCE_IDS) -> np.ndarray:
     """The int64 ``[T]`` semantic ids of a token file (int16 or int64 ``[T]``, ``[1, T]`` or ``[1, 1, T]``), validated on the host."""
     try:
         arr = np.load(str(path), allow_pickle=False)
@@ -73,8 +73,8 @@ def read_semantic_file(path, vocab: int) -> np.ndarray:
     arr = arr.reshape(-1).astype(np.int64)
     if arr.size == 0:
         raise TokenFileError("empty token file (T = 0)")
-    if arr.size > MAX_SOURCE_IDS:
-        raise TokenFileError(f"{arr.size} semantic ids, more than the {MAX_SOURCE_IDS} one source may have")
+    if arr.size > max_ids:
+        raise TokenFileError(f"{arr.size} semantic ids, more than the {max_ids} one source may have")
     lo, hi = int(arr.min()), int(arr.max())
     if lo < 0 or hi >= vocab:
         raise TokenFileError(f"semantic id {lo if lo < 0 else hi} outside [0, {vocab - 1}]")
@@ -95,7 +95,7 @@ class SemanticRun(DecodeRun):
     def load(self, item):
         i, (path, out) = item
         try:
-            return i, path, out, read_semantic_file(path, self.vocab), None
+            return i, path, out, read_semantic_file(path, self.vocab, MAX_SOURCE_IDS - len(getattr(self.stages, "voice", None) or ())), None
         except TokenFileError as e:
             return i, path, out, None, str(e)
 
@@ -147,7 +147,9 @@ class Stages:
     """One round through the two generators of ``tok`` (a semantic ``AudioToken``): the GPT's generation queue with each file's own draws, then the fine
     stage's window queue, its rows handed over longest first to cut the tail (rows are independent of each other, so the order changes no result)."""
 
-    def __init__(self, tok, seed: int, temperature: float, top_k: int, fine_temperature, max_new_tokens: int, window, hop, slots: int, fine_slots: int):
+    def __init__(self, tok, seed: int, temperature: float, top_k: int, fine_temperature, max_new_tokens: int, window, hop, slots: int, fine_slots: int,
+                 voice=None):
+        self.voice = voice         # one VoicePrompt that every file continues (DESIGN.md §22), or None
         self.tok, self.seed, self.temperature, self.top_k, self.fine_temperature = tok, int(seed), temperature, top_k, fine_temperature
         self.max_new, self.slots, self.fine_slots = int(max_new_tokens), int(slots), int(fine_slots)
         gpt = tok._gpt()
@@ -159,11 +161,18 @@ class Stages:
         if not 1 <= self.max_new <= 1024:
             raise ValueError(f"to_audio_batch_files: max_new_tokens must be 1 to 1024, got {self.max_new}")
         self.W = tok._fine().block_size
+        if voice is not None:      # a prompt that no source can follow is refused before any file is read
+            from .semantic_decoder import check_prompt
+            from .voice import VoicePrompt
+            if not isinstance(voice, VoicePrompt) or voice.codes.shape[0] != 8:
+                raise ValueError("to_audio_batch_files: voice must be one VoicePrompt with all 8 code books")
+            check_prompt(len(voice), 1, self.S, self.H)
         self.last_coarse = None    # the last round's AcousticGeneration (tests)
 
     def capacity(self, n_ids: int) -> int:
         """The positions of a source's own stage 1 stream."""
-        return stream_extent([acoustic_windows(n_ids, self.S, self.H, self.r, self.block)], self.S, self.r, self.max_new, self.block)[1]
+        P = len(self.voice) if self.voice is not None else 0
+        return stream_extent([acoustic_windows(n_ids, self.S, self.H, self.r, self.block, P)], self.S, self.r, self.max_new, self.block, [P])[1]
 
     def __call__(self, sources, stems):
         tok, W = self.tok, self.W
@@ -171,7 +180,7 @@ class Stages:
         t0 = time.perf_counter()
         u = stack_gpt_draws([file_draws(self.seed, stem, cap)[0] for stem, cap in zip(stems, caps)])
         coarse = tok.to_acoustic(list(sources), max_new_tokens=self.max_new, temperature=self.temperature, top_k=self.top_k, uniforms=u, long_form=True,
-                                 window=self.S, hop=self.H, slots=self.slots)
+                                 window=self.S, hop=self.H, slots=self.slots, voice=self.voice)
         self.last_coarse = coarse
         t1 = time.perf_counter()
         have = [b for b, c in enumerate(coarse.codes) if c is not None and c.shape[1] >= 1]
@@ -181,8 +190,10 @@ class Stages:
         if order:
             draws = None
             if self.fine_temperature is not None:
-                draws = [file_draws(self.seed, stems[b], caps[b], len(fine_windows(int(coarse.codes[b].shape[1]), W)), W)[1] for b in order]
-            fine = tok.to_fine([coarse.codes[b] for b in order], temperature=self.fine_temperature, uniforms=draws, slots=self.fine_slots)
+                h = history_cells(self.voice.frames, W) if self.voice is not None else 0
+                draws = [file_draws(self.seed, stems[b], caps[b], len(fine_windows(int(coarse.codes[b].shape[1]), W, h)), W)[1] for b in order]
+            fine = tok.to_fine([coarse.codes[b] for b in order], temperature=self.fine_temperature, uniforms=draws, slots=self.fine_slots,
+                               history=None if self.voice is None else self.voice.codes)
             for b, c in zip(order, fine.codes):
                 codes[b] = c.numpy()
             info["fine_passes"] = len(fine.passes)

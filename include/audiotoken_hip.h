@@ -700,6 +700,29 @@ int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, c
                           const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
                           float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace, int trace_cap,
                           int32_t* n_ticks, int32_t* placement, at_stream_t stream, int32_t* status_dev);
+/* Voice prompts: the prompted forms of the two calls above. A source with a prompt of P semantic ids and their r P coarse ids follows the
+ * same schedule on the concatenated source, prompt ids then source ids. Stream positions [0, r P) are given: position p is
+ * codes[p & 1][p >> 1] + acoustic_offset + (p & 1) codebook_size. Window 0 carries those r P ids instead of none and, unless final, produces r S - r P ids.
+ * The carry of a later window comes from the prompt below stream position r P and from the row's output above it. The result excludes the prompt:
+ * out_ids_dev, out_len_dev, uniforms_dev and logits_out_dev are indexed by result position q = stream position - r P, and the strides count result ids.
+ * The table: prompt_sem_dev device int32 [n_prompts][p_stride], prompt_codes_dev device int32 [n_prompts][2][f_stride], prompt_len HOST int32 [n_prompts]
+ * (even, 2 <= P <= S - H, P <= p_stride, r P / 2 <= f_stride), prompt_of_src HOST int32 per source: its entry or -1 for none; n_prompts 0 to 4096. A source's
+ * P + N must not exceed 65536. One entry serves any number of sources. A prompt id outside [0, semantic_vocab) is clamped like a source id (status bit 0);
+ * a code outside [0, codebook_size) is clamped and sets status bit 1. The state sizes do not depend on the prompt: at_gpt_long_state_bytes and
+ * at_gpt_queue_state_bytes serve, with max_len for the windows of the concatenated sources. A call whose sources all have -1 is the prompt-free call, bit
+ * for bit. at_gpt_long_num_windows_prompted: the windows of a source of N ids after a prompt of P (0 = error). */
+int at_gpt_long_num_windows_prompted(int P, int N, int S, int H);
+int at_gpt_generate_long_prompted(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, const int32_t* prompt_sem_dev, int p_stride,
+                                  const int32_t* prompt_codes_dev, int f_stride, const int32_t* prompt_len, int n_prompts, const int32_t* prompt_of_src, int S, int H,
+                                  int r, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
+                                  float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
+                                  int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev);
+int at_gpt_generate_queue_prompted(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, const int32_t* prompt_sem_dev, int p_stride,
+                                   const int32_t* prompt_codes_dev, int f_stride, const int32_t* prompt_len, int n_prompts, const int32_t* prompt_of_src, int S, int H,
+                                   int r, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
+                                   float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
+                                   int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens,
+                                   int32_t* trace, int trace_cap, int32_t* n_ticks, int32_t* placement, at_stream_t stream, int32_t* status_dev);
 /* The sampling step alone, one workgroup per row, no float atomics (the same call twice gives the same ids). logits_dev device float32 [B][V], V <= 65536;
  * uniforms_dev device float32 [B]; allow NULL or a HOST array int32 [4] = two half-open id ranges; out_dev device int32 [B]. The rule:
  * 1. zt_i = z_i / temperature (one IEEE fp32 division). 2. ids outside the allow ranges become -inf. 3. v = the min(top_k, V)-th largest zt; every id
@@ -765,6 +788,30 @@ size_t at_fine_queue_state_bytes(const at_fine_t* h, int slots, int max_T);
 int at_fine_generate_queue(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy, const float* uniforms_dev,
                            int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T, int slots,
                            int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream, int32_t* status_dev);
+/* ---- the fine stage with a history prompt: BarkFineModel.generate with history_prompt["fine_prompt"] ---------------------------
+ * A row of T frames may continue a history of Th frames of all 8 code books. With H = W / 2 and h = min(H, Th), the row's work array is [L][8] with
+ * L = max(h + T, W): cells [0, h) hold the LAST h history frames in every channel, cells [h, h + T) the coarse codes, 1024 everywhere else. The row has
+ * n = max(0, ceil((T - (W - h)) / H)) + 1 windows; window k has start = min(k H, L - W), fill = min(h + k H, L - H) and rel = fill - start, which is
+ * positive in every window of a row with a history. History cells are never written; the result is cells [h, h + T). h = 0 is the rule above, unchanged,
+ * and the entry points above are these with an empty table, bit for bit.
+ * The history table: hist_dev device int32 [n_hist][8][h_stride]; hist_lens HOST int32 [n_hist], 1 <= hist_lens[i] <= min(h_stride, max_hist);
+ * hist_of_row HOST int32 [B or n_rows], the entry each row continues or -1 for none, so one entry serves any number of rows. n_hist = 0 (0 to 4096): no
+ * table; the three pointers are not read, except that a non-null hist_of_row must then hold -1 everywhere. max_hist (0 to 262144) sizes the state:
+ * work arrays of max(min(H, max_hist) + max_T, W) cells. A history id outside [0, 1024) is clamped and sets bit 1 of *status_dev.
+ * uniforms, logits_out and window_ids keep their layouts: per window cell and buffer position, positions below rel left as they were; n_max and the
+ * queue's window offsets count a row's windows by at_fine_num_windows_hist(h, T, Th). */
+int at_fine_num_windows_hist(const at_fine_t* h, int T, int Th);
+size_t at_fine_state_bytes_hist(const at_fine_t* h, int B, int max_T, int max_hist);
+size_t at_fine_queue_state_bytes_hist(const at_fine_t* h, int slots, int max_T, int max_hist);
+int at_fine_generate_hist(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, const int32_t* hist_dev, int h_stride,
+                          const int32_t* hist_lens, int n_hist, const int32_t* hist_of_row, int max_hist, float temperature, int greedy,
+                          const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev,
+                          size_t state_bytes, int max_T, at_stream_t stream, int32_t* status_dev);
+int at_fine_generate_queue_hist(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, const int32_t* hist_dev, int h_stride,
+                                const int32_t* hist_lens, int n_hist, const int32_t* hist_of_row, int max_hist, float temperature, int greedy,
+                                const float* uniforms_dev, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
+                                int max_T, int slots, int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream,
+                                int32_t* status_dev);
 
 #ifdef __cplusplus
 }
