@@ -352,6 +352,34 @@ class AudioToken:
         return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
                                                  constrain=constrain, return_logits=return_logits)
 
+    def score_acoustic(self, tokens, codes, temperature: float = 1.0, constrain: bool = False, include_stop: bool = True, long_form: bool = False,
+                       window: Optional[int] = None, hop: Optional[int] = None, return_logits: bool = False):
+        """How likely given coarse codes are under the semantic decoder's GPT, teacher-forced: the evaluation half of the reference's model
+        (``GPT.forward(idx, targets)``, ``gpt2_model.py:161-164``) on the HIP decoder (semantic_decoder.py). Nothing is drawn. Semantic
+        tokenizers only. ``tokens`` as ``to_acoustic`` takes them: one source, or a list of up to 4096. ``codes``: integer ``[2, T]`` per source (of
+        ``[K >= 2, T]`` rows 0 and 1), what ``AudioToken(Tokenizers.acoustic).encode`` and ``AcousticGeneration.codes`` give. A source's sequence is what
+        generation would have written: ids + SEMANTIC_OFFSET, INFER, the codes interleaved (the inverse of ``coarse_codes``), then STOP with
+        ``include_stop``; every acoustic position is scored. Returns an ``AcousticScore``: per source ``logprob`` and ``rank`` at stream positions (STOP
+        last), ``nll`` (the mean of ``-logprob``, what the reference's cross-entropy gives the source alone) and, with ``return_logits``, the logits.
+        The default scores the model's own distribution over all ids at ``temperature`` 1, the reference's cross-entropy. ``constrain=True`` scores under
+        the allow sets ``to_acoustic(constrain=True)`` draws under, and with its ``temperature`` that is the distribution generation draws from before
+        top-k; ``rank < top_k`` says whether top-k would have kept the id. A source longer than ``max_source_tokens`` is refused without ``long_form``:
+        generation would cut it, and a cut here would score the wrong pairing. ``long_form=True`` walks ``acoustic_windows`` with ``window`` / ``hop`` as
+        ``to_acoustic(long_form=True)`` does: window k sees its source ids and the carry out of the GIVEN codes and scores its own new ids, the final
+        window everything that is left; always constrained; ``windows`` of the result is the schedule with the counts scored. Voice prompts, the fine
+        stage and files are not scored."""
+        if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
+            raise ValueError(f"score_acoustic scores acoustic code books against semantic ids; {self.tokenizer_name} has no semantic ids")
+        if not long_form and (window is not None or hop is not None):
+            raise ValueError("score_acoustic: window= and hop= belong to long_form=True")
+        if not long_form:   # refused before a model is built, by the rule and the configuration the decoder itself will use
+            from .semantic_decoder import refuse_long_source, source_ids
+            cfg = self._decoder_config()
+            for t in tokens if isinstance(tokens, (list, tuple)) else [tokens]:
+                refuse_long_source(int(source_ids(t, cfg).numel()), cfg)
+        return self._gpt().score_acoustic(tokens, codes, temperature=temperature, constrain=constrain, include_stop=include_stop, long_form=long_form,
+                                          window=window, hop=hop, return_logits=return_logits)
+
     def to_fine(self, codes, temperature: Optional[float] = 0.5, seed: int = 0, uniforms=None, return_logits: bool = False, slots: Optional[int] = None,
                 history=None):
         """The two coarse EnCodec code books -> all eight: stage 2 of the reference's semantic decoder (bark's ``generate_fine``) on the HIP fine
@@ -398,11 +426,17 @@ class AudioToken:
         return VoicePrompt.from_tokens(torch.as_tensor(sem).cpu().reshape(-1), torch.as_tensor(codes).cpu().reshape(8, -1), int(max_ids),
                                        gpt.config.SEMANTIC_VOCAB_SIZE)
 
+    def _decoder_config(self):
+        """The semantic decoder's configuration of this tokenizer: the loaded decoder's own, else the one ``_gpt`` will build it with."""
+        if getattr(self, "semantic_decoder", None) is not None:
+            return self.semantic_decoder.config
+        from .configs import HubertDecoderConfig, Wav2VecBertDecoderConfig
+        return HubertDecoderConfig() if self.tokenizer_name == Tokenizers.semantic_s else Wav2VecBertDecoderConfig()
+
     def _gpt(self):
         if getattr(self, "semantic_decoder", None) is None:
-            from .configs import HubertDecoderConfig, Wav2VecBertDecoderConfig
             from .semantic_decoder import SemanticToAcoustic
-            cfg = HubertDecoderConfig() if self.tokenizer_name == Tokenizers.semantic_s else Wav2VecBertDecoderConfig()
+            cfg = self._decoder_config()
             w = self.kwargs.get("decoder_weights")
             if w is None and cfg.weights is None:
                 logger.warning("to_acoustic: no decoder_weights given; using the seeded synthetic GPT")

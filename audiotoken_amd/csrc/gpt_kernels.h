@@ -57,7 +57,24 @@ int check_sampling(float temperature, int top_k);
 
 // One pass of the model over the R tokens of the state's list: the `steps.n` step tokens, which the embedding resolves, then the prompt tokens the begin
 // kernel wrote; then the head for the `ns` sampling rows that s.last_row names. An id outside [0, V) is clamped and reported in bit 0 of *status.
-int gpt_forward(const at_gpt* h, const GptState& s, const StepSlots& steps, int ns, int R, int* status, hipStream_t stream);
+// with_head = false ends after the last layer and leaves the residual stream in s.x: the scorer applies the head itself, to every scored position.
+int gpt_forward(const at_gpt* h, const GptState& s, const StepSlots& steps, int ns, int R, int* status, hipStream_t stream, bool with_head = true);
 int gpt_sample(const SampleArgs& a, int rows, hipStream_t stream);
+// The final LayerNorm alone (gpt_ln_kernel with ln_f): y[r] = LN(x[gather[r]]) for n rows
+int gpt_final_ln(const at_gpt* h, const float* x, const int* gather, float* y, int n, hipStream_t stream);
+
+// Teacher-forced scoring (gpt_score.hip): workgroup j scores logits row j against targets[j] under allow[parity ? parity[j] & 1 : 0] and
+// writes logprob / rank (and the row itself into logits_out, when given) at index out_index ? out_index[j] : j.
+struct ScoreArgs {
+    const float* logits;      // [rows][V]
+    int V;
+    float temperature;
+    const int *targets, *parity, *out_index;
+    Allow allow[2];
+    float* logprob;
+    int* rank;
+    float* logits_out;        // nullable [.][V]
+};
+int gpt_score_rows(const ScoreArgs& a, int rows, hipStream_t stream);
 
 }  // namespace at

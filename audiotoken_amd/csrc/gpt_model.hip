@@ -412,7 +412,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
 
 // ---- one pass of the model ------------------------------------------------------------------------------------------------------------------
 // The model over the R embedded tokens of s.x, each at (tok_row, tok_pos), then the head for the B tokens that s.last_row names: logits row j belongs to token last_row[j].
-int run_layers(const at_gpt* h, const GptState& s, int B, int R, int cap, hipStream_t stream) {
+// Without with_head the pass ends after the last layer (the scorer, gpt_score.hip, applies the head to every scored position itself).
+int run_layers(const at_gpt* h, const GptState& s, int B, int R, int cap, hipStream_t stream, bool with_head) {
     const dim3 ln_grid((R + 3) / 4);
     // More rows than a step can have (a prefill of more than 64 tokens): the four linears on the fp32 matrix-core GEMM (gemm_f32.hip, an exact k-ordered fp32
     // chain). Otherwise the register-streaming kernel, in ceil(R / 16) passes.
@@ -461,6 +462,7 @@ int run_layers(const at_gpt* h, const GptState& s, int B, int R, int cap, hipStr
             if (int rc = launch_linear<FF, 256, LIN_RESID>(g, stream)) return rc;
         }
     }
+    if (!with_head) return 0;
     // the head, for the last token of every row only; its B <= R input rows take the place of LN2's output, which the last layer has consumed
     hipLaunchKernelGGL(gpt_ln_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, s.x, h->ln_f, (const int*)s.last_row, s.xn, B);
     AT_CHECK_HIP(hipGetLastError());
@@ -489,10 +491,16 @@ int check_sampling(float temperature, int top_k) {
     return 0;
 }
 
-int gpt_forward(const at_gpt* h, const GptState& s, const StepSlots& steps, int ns, int R, int* status, hipStream_t stream) {
+int gpt_forward(const at_gpt* h, const GptState& s, const StepSlots& steps, int ns, int R, int* status, hipStream_t stream, bool with_head) {
     hipLaunchKernelGGL(gpt_embed_kernel, dim3(R), dim3(E / 4), 0, stream, steps, h->wte, h->wpe, h->vocab, h->block, s, status);
     AT_CHECK_HIP(hipGetLastError());
-    return run_layers(h, s, ns, R, s.cap, stream);
+    return run_layers(h, s, ns, R, s.cap, stream, with_head);
+}
+
+int gpt_final_ln(const at_gpt* h, const float* x, const int* gather, float* y, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(gpt_ln_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, x, h->ln_f, gather, y, n);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 int gpt_sample(const SampleArgs& a, int rows, hipStream_t stream) {

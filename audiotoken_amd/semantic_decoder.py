@@ -225,6 +225,97 @@ def queue_tick_bound(lens, S: int, H: int, r: int, block: int, max_new: int, pro
                for i, N in enumerate(lens))
 
 
+@dataclass
+class AcousticScore:
+    """What ``score_acoustic`` returns, one entry per source."""
+    logprob: List[torch.Tensor]             # float32 [2 T_b (+ 1 with include_stop)]: the log-probability of the id at each stream position, STOP last
+    rank: List[torch.Tensor]                # int32, the same shape: ids the model puts above it (top_k = k keeps the id exactly when rank < k)
+    nll: List[float]                        # the mean of -logprob over the source's scored ids, in float64 on the host
+    windows: Optional[List[List[tuple]]] = None   # the long form: per source (source_start, source_len, carry, scored ids) of every window
+    logits: Optional[List[torch.Tensor]] = None   # return_logits: float32 [the same count, V], the logits each id was scored on
+
+
+MAX_SCORE_SOURCES = 4096   # of one score_acoustic call
+MAX_SCORE_ROWS = 65536     # of one at_gpt_score call
+
+
+def acoustic_stream(codes, config: HubertDecoderConfig) -> np.ndarray:
+    """Integer ``[K >= 2, T]`` codes -> the ``2 T`` model ids of the stream the GPT writes: ``c0[0] + ACOUSTIC_OFFSET, c1[0] + ACOUSTIC_OFFSET + 1024,
+    c0[1] + ...``, rows 0 and 1 only. The inverse of ``coarse_codes`` (which takes the ids minus the offset)."""
+    c = torch.as_tensor(np.asarray(codes.cpu() if isinstance(codes, torch.Tensor) else codes))
+    if c.dim() != 2 or c.shape[0] < 2 or c.is_floating_point() or c.dtype == torch.bool:
+        raise ValueError(f"score_acoustic: codes must be integer [K >= 2, T], got {tuple(c.shape)} {c.dtype}")
+    c = c[:2].to(torch.int64)
+    if c.numel() and (int(c.min()) < 0 or int(c.max()) >= config.codebook_size):
+        raise ValueError(f"score_acoustic: codes must lie in [0, {config.codebook_size})")
+    return (c + torch.tensor([[0], [config.codebook_size]]) + config.ACOUSTIC_OFFSET).t().reshape(-1).numpy()
+
+
+def refuse_long_source(n: int, config: HubertDecoderConfig) -> None:
+    """The short form's limit on a source of ``n`` ids: generation cuts a longer one, and a cut here would score the wrong pairing."""
+    if n > config.max_source_tokens:
+        raise ValueError(f"score_acoustic: a source of {n} ids exceeds max_source_tokens ({config.max_source_tokens}); long_form=True scores it in windows")
+
+
+def score_row(tokens, stream, config: HubertDecoderConfig, block: int, include_stop: bool = True):
+    """The short form's row of one source: ``(sequence, score_from)``, the prompt ``to_acoustic`` builds (ids + SEMANTIC_OFFSET, INFER), then the stream's
+    ids, then STOP with ``include_stop``; ``score_from`` is the first acoustic position. A source longer than ``max_source_tokens`` is refused (generation
+    cuts it; a cut here would score the wrong pairing), and so is a sequence longer than the block."""
+    src = source_ids(tokens, config)
+    refuse_long_source(int(src.numel()), config)
+    stream = np.asarray(stream, dtype=np.int64).reshape(-1)
+    if stream.size % 2:
+        raise ValueError(f"score_acoustic: an odd id count ({stream.size}): the stream holds whole frames of two ids")
+    tail = [config.STOP_TOKEN] if include_stop else []
+    seq = np.concatenate([src.numpy() + config.SEMANTIC_OFFSET, [config.INFER_TOKEN], stream, tail]).astype(np.int32)
+    if seq.size > block:
+        raise ValueError(f"score_acoustic: the sequence ({src.numel()} + 1 + {stream.size + len(tail)} ids) is longer than the model's block ({block})")
+    if stream.size + len(tail) == 0:
+        raise ValueError("score_acoustic: nothing to score: no codes and no STOP")
+    return seq, int(src.numel()) + 1
+
+
+def long_score_rows(tokens, stream, S: int, H: int, config: HubertDecoderConfig, block: int, include_stop: bool = True):
+    """The long form's rows of one source: one per window of ``acoustic_windows``, as ``(sequence, score_from, stream position of the
+    first target)``, and the schedule with the counts scored. Window k: its source ids + the offset, INFER, the ``carry`` ids the given stream holds at
+    ``[r k H, r k H + carry)``, then its targets: the ``new_ids`` stream ids from ``r k H + carry`` on, for the final window everything that is left, then
+    STOP with ``include_stop``. A final window with nothing to score has no row."""
+    r = int(config.ids_per_source_token)
+    src = source_ids(tokens, config).numpy()
+    stream = np.asarray(stream, dtype=np.int64).reshape(-1)
+    plan = acoustic_windows(int(src.size), S, H, r, block)
+    if stream.size % 2:
+        raise ValueError(f"score_acoustic: an odd id count ({stream.size}): the stream holds whole frames of two ids")
+    start, n_src, carry, _ = plan[-1]
+    first = r * start + carry
+    P, budget = window_steps(plan, 1024, block)[-1]
+    if stream.size < first:
+        raise ValueError(f"score_acoustic: a stream of {stream.size} ids is shorter than the final window's first step ({first}) for a source of {src.size} ids")
+    if stream.size > first + budget:
+        raise ValueError(f"score_acoustic: a stream of {stream.size} ids is longer than the final window's first step plus its budget ({first} + {budget})")
+    rows, windows = [], []
+    for k, (start, n_src, carry, new) in enumerate(plan):
+        base = r * start + carry
+        final = new is None
+        targets = stream[base:] if final else stream[base:base + new]
+        tail = [config.STOP_TOKEN] if final and include_stop else []
+        windows.append((start, n_src, carry, int(targets.size)))
+        if targets.size + len(tail) == 0:
+            continue
+        seq = np.concatenate([src[start:start + n_src] + config.SEMANTIC_OFFSET, [config.INFER_TOKEN], stream[r * start:base], targets, tail]).astype(np.int32)
+        if seq.size > block:
+            raise ValueError(f"score_acoustic: the final window's sequence ({seq.size} ids with STOP) is longer than the model's block ({block}); "
+                             "a stream that fills its budget did not stop: include_stop=False")
+        rows.append((seq, n_src + 1 + carry, base))
+    return rows, windows
+
+
+def constrained_allow(config: HubertDecoderConfig):
+    """The allow sets ``to_acoustic(constrain=True)`` draws under: even steps code book 0 or STOP, odd steps code book 1."""
+    a, n = config.ACOUSTIC_OFFSET, config.codebook_size
+    return [[a, a + n, config.STOP_TOKEN, config.STOP_TOKEN + 1], [a + n, a + 2 * n, 0, 0]]
+
+
 def seeded_uniforms(seed: int, batch: int, max_new_tokens: int) -> np.ndarray:
     return np.random.Generator(np.random.Philox(seed)).random((batch, max_new_tokens), dtype=np.float32)
 
@@ -441,6 +532,111 @@ class SemanticToAcoustic(LibHandle):
         out = self._generation(ids, [FINISH[f] for f in fin], logits, windows)
         out.ticks, out.placement = queue.get("ticks"), queue.get("placement")
         return out
+
+    def score_rows(self, seqs: Sequence[np.ndarray], score_from: Sequence[int], temperature: float = 1.0, allow=None, rows: int = MAX_SLOTS,
+                   pass_tokens: Optional[int] = None, head_rows: int = 1024, max_len: Optional[int] = None, return_logits: bool = False):
+        """``at_gpt_score`` as it is (include/audiotoken_hip.h): ``seqs`` 1 to 65536 int id arrays over the model's own vocabulary, row b
+        scored from position ``score_from[b]`` on. ``allow``: None or int ``[2][4]``. ``rows`` / ``pass_tokens`` / ``head_rows`` / ``max_len``: the cache
+        rows and the tokens of one pass, the scored positions of one head chunk, the positions of a cache row (default: the longest row). Returns
+        ``(logprob, rank, logits)``: per row float32 / int32 ``[len - score_from]`` on the CPU and (``return_logits``) float32 ``[len - score_from, V]``."""
+        n = len(seqs)
+        if not 1 <= n <= MAX_SCORE_ROWS or len(score_from) != n:
+            raise ValueError(f"score_rows: 1 to {MAX_SCORE_ROWS} rows with one score_from each, got {n} and {len(score_from)}")
+        lens = [int(len(s)) for s in seqs]
+        froms = [int(f) for f in score_from]
+        stride = max(lens + [2])
+        max_len = max(2, min(self.block_size, stride)) if max_len is None else int(max_len)
+        rows = int(rows)
+        if pass_tokens is None:   # every cache row full, or the whole call when that is less
+            pass_tokens = max(max_len, min(max(rows, 1) * max_len, sum(lens) - n))   # a row's last id takes no room in the list
+        out_stride = max([l - f for l, f in zip(lens, froms)] + [1])
+        host = np.zeros((n, stride), dtype=np.int32)
+        for b, s in enumerate(seqs):
+            host[b, :lens[b]] = np.asarray(s, dtype=np.int32)
+        c_allow = None if allow is None else (C.c_int32 * 8)(*[int(v) for v in np.asarray(allow).reshape(8)])
+        dev = self.device
+        with torch.cuda.device(dev):
+            nbytes = int(self._fn("score_state_bytes")(self.handle, rows, max_len, int(pass_tokens), int(head_rows)))
+            if nbytes == 0:
+                raise ValueError(_cabi.last_error())
+            d_seq = torch.from_numpy(host).to(dev)
+            d_lp = torch.full((n, out_stride), float("nan"), dtype=torch.float32, device=dev)
+            d_rank = torch.full((n, out_stride), -1, dtype=torch.int32, device=dev)
+            d_logits = torch.empty((n, out_stride, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
+            state = self._workspace(nbytes)
+            self._status.zero_()
+            _cabi.check(self._fn("score")(self.handle, d_seq.data_ptr(), stride, (C.c_int32 * n)(*lens), (C.c_int32 * n)(*froms), n, float(temperature),
+                                          c_allow, d_lp.data_ptr(), d_rank.data_ptr(), out_stride, _cabi.ptr(d_logits), state.data_ptr(), state.numel(), rows,
+                                          max_len, int(pass_tokens), int(head_rows), _cabi.current_stream_handle(dev), self._status.data_ptr()), "at_gpt_score")
+            lp_all, rank_all = d_lp.cpu(), d_rank.cpu()   # synchronises
+        if self.last_status() & 1:
+            raise ValueError("at_gpt_score: an id lies outside the model's vocabulary")
+        self.last_raw_scores = (lp_all, rank_all)   # the whole [n, out_stride] buffers, NaN / -1 where nothing was written (tests)
+        count = [l - f for l, f in zip(lens, froms)]
+        logprob = [lp_all[b, :count[b]].clone() for b in range(n)]
+        rank = [rank_all[b, :count[b]].clone() for b in range(n)]
+        logits = None if d_logits is None else [d_logits[b, :count[b]].cpu() for b in range(n)]
+        return logprob, rank, logits
+
+    def score_acoustic(self, tokens, codes, temperature: float = 1.0, constrain: bool = False, include_stop: bool = True, long_form: bool = False,
+                       window: Optional[int] = None, hop: Optional[int] = None, return_logits: bool = False, **passes) -> AcousticScore:
+        """The log-probability of given coarse codes under the model, teacher-forced (``AudioToken.score_acoustic``). ``passes``: ``rows``,
+        ``pass_tokens`` and ``head_rows`` of ``score_rows``."""
+        cfg = self.config
+        batch = tokens if isinstance(tokens, (list, tuple)) else [tokens]
+        code_list = codes if isinstance(codes, (list, tuple)) else [codes]
+        if not 1 <= len(batch) <= MAX_SCORE_SOURCES:
+            raise ValueError(f"score_acoustic: 1 to {MAX_SCORE_SOURCES} sources per call, got {len(batch)}")
+        if len(code_list) != len(batch):
+            raise ValueError(f"score_acoustic: {len(batch)} sources with {len(code_list)} code arrays")
+        if not long_form and (window is not None or hop is not None):
+            raise ValueError("score_acoustic: window= and hop= belong to long_form=True")
+        streams = [acoustic_stream(c, cfg) for c in code_list]
+        block = self.block_size
+        seqs, froms, owner, place, windows = [], [], [], [], None
+        if long_form:   # every window of every source is a row of one call: given the codes, the windows do not depend on each other
+            S = default_window(cfg, block)[0] if window is None else int(window)
+            H = (S // 2) // 2 * 2 if hop is None else int(hop)
+            windows = []
+            for b, (t, s) in enumerate(zip(batch, streams)):
+                rows_b, plan = long_score_rows(t, s, S, H, cfg, block, include_stop)
+                windows.append(plan)
+                for seq, score_from, base in rows_b:
+                    seqs.append(seq); froms.append(score_from); owner.append(b); place.append(base)
+            if len(seqs) > MAX_SCORE_ROWS:
+                raise ValueError(f"score_acoustic: the sources have {len(seqs)} windows, one call takes {MAX_SCORE_ROWS}")
+        else:
+            for b, (t, s) in enumerate(zip(batch, streams)):
+                seq, score_from = score_row(t, s, cfg, block, include_stop)
+                seqs.append(seq); froms.append(score_from); owner.append(b); place.append(0)
+        allow = constrained_allow(cfg) if constrain or long_form else None
+        lp, rank, logits = self.score_rows(seqs, froms, temperature, allow, return_logits=return_logits, **passes) if seqs else ([], [], [] if return_logits else None)
+        out_lp, out_rank, out_logits = [], [], []
+        for b, s in enumerate(streams):
+            n = s.size + (1 if include_stop else 0)
+            mine = [i for i, o in enumerate(owner) if o == b]   # in stream order, and they tile [0, n)
+            assert sum(len(lp[i]) for i in mine) == n and all(place[i] == sum(len(lp[j]) for j in mine[:q]) for q, i in enumerate(mine))
+            out_lp.append(torch.cat([lp[i] for i in mine]) if mine else torch.empty(0))
+            out_rank.append(torch.cat([rank[i] for i in mine]) if mine else torch.empty(0, dtype=torch.int32))
+            if return_logits:
+                out_logits.append(torch.cat([logits[i] for i in mine]) if mine else torch.empty(0, self.vocab))
+        nll = [float(-(x.to(torch.float64)).mean()) if x.numel() else float("nan") for x in out_lp]
+        return AcousticScore(logprob=out_lp, rank=out_rank, nll=nll, windows=windows, logits=out_logits if return_logits else None)
+
+
+def score_logits(logits: torch.Tensor, targets: torch.Tensor, temperature: float = 1.0, allow=None):
+    """``at_op_score_rows`` on device tensors: logits float32 ``[R, V]``, targets int32 ``[R]`` -> (logprob float32 ``[R]``, rank int32 ``[R]``): the
+    scoring rule alone."""
+    lib = _cabi.load()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+    assert targets.is_cuda and targets.dtype == torch.int32 and targets.is_contiguous() and targets.numel() == logits.shape[0]
+    logprob = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
+    rank = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    c_allow = None if allow is None else (C.c_int32 * 4)(*[int(v) for v in allow])
+    with torch.cuda.device(logits.device):
+        _cabi.check(lib.at_op_score_rows(logits.data_ptr(), logits.shape[0], logits.shape[1], targets.data_ptr(), float(temperature), c_allow, logprob.data_ptr(),
+                                         rank.data_ptr(), _cabi.current_stream_handle(logits.device)), "at_op_score_rows")
+    return logprob, rank
 
 
 def topk_sample(logits: torch.Tensor, temperature: float, top_k: int, uniforms: torch.Tensor, allow=None) -> torch.Tensor:

@@ -730,6 +730,33 @@ int at_gpt_generate_queue_prompted(at_gpt_t* h, const int32_t* src_dev, int src_
  * running sum in ascending id order exceeds u * S; if rounding leaves none, the highest kept id whose zt is not -inf. */
 int at_op_topk_sample(const float* logits_dev, int B, int V, float temperature, int top_k, const float* uniforms_dev, const int32_t* allow, int32_t* out_dev,
                       at_stream_t stream);
+/* Teacher-forced scoring (csrc/gpt_score.hip): the log-probability and the rank of GIVEN ids under the model, where the calls above draw ids.
+ * Row b of seq_dev (device int32 [n_rows][seq_stride], n_rows 1 to 65536) holds seq_len[b] ids of the model's own vocabulary, 2 <= seq_len[b] <= max_len <=
+ * block; seq_len and score_from are HOST arrays, 1 <= score_from[b] < seq_len[b]. For every p in [score_from[b], seq_len[b]) the logits at position p - 1
+ * (causal, positions from 0) are scored against the target seq[b][p] by the rule of at_op_score_rows (below) with `allow` = NULL or a HOST array int32
+ * [2][4], the set of a position being allow[(p - score_from[b]) % 2], and the result goes to logprob_out_dev / rank_out_dev [b][p - score_from[b]] (device
+ * float32 / int32 [n_rows][out_stride], out_stride >= every row's seq_len - score_from, n_rows * out_stride < 2^31; entries past a row's count are left as
+ * they were). logits_out_dev NULL or device float32 [n_rows][out_stride][V]: the logits each target was scored on. The rows are taken in the caller's order
+ * into passes of at most `rows` cache rows (1 to 64) and at most pass_tokens tokens (max_len to 65600, so one row always fits). A row puts its first
+ * seq_len - 1 ids into the list: nothing is scored on the logits of its last id, which is a target only. A pass is one prefill of its token list through
+ * the model at_gpt_generate runs (a list of more than 64 tokens on the GEMM route, a shorter one on the streaming linear kernel), then the
+ * head for the pass's scored positions, head_rows (a multiple of 16, 16 to 4096) at a time: the final LayerNorm, the logits on the fp32 GEMM, the row rule.
+ * The logits exist one chunk at a time. state_dev: at_gpt_score_state_bytes(h, rows, max_len, pass_tokens, head_rows) bytes (K / V for rows x max_len
+ * positions, activations for pass_tokens tokens, one chunk of logits; nothing per row of the call or per scored position; 0 = error). Everything is
+ * enqueued on `stream`; the host waits for nothing and nothing is allocated. status_dev NULL or a device word: bit 0 = an id outside [0, V) was clamped.
+ * Every argument is checked before the device is touched. Not re-entrant per handle. */
+size_t at_gpt_score_state_bytes(const at_gpt_t* h, int rows, int max_len, int pass_tokens, int head_rows);
+int at_gpt_score(at_gpt_t* h, const int32_t* seq_dev, int seq_stride, const int32_t* seq_len, const int32_t* score_from, int n_rows, float temperature,
+                 const int32_t* allow, float* logprob_out_dev, int32_t* rank_out_dev, int out_stride, float* logits_out_dev, void* state_dev, size_t state_bytes,
+                 int rows, int max_len, int pass_tokens, int head_rows, at_stream_t stream, int32_t* status_dev);
+/* The scoring rule alone, one workgroup per row, no float atomics (the same call twice gives the same bits). logits_dev device float32 [R][V], R 1 to 65536,
+ * 1 <= V <= 65536; targets_dev device int32 [R]; allow NULL or a HOST array int32 [4] = two half-open id ranges; logprob_out_dev device float32 [R],
+ * rank_out_dev device int32 [R]. The rule, for a row z with target t: 1. zt_i = z_i / temperature (one IEEE fp32 division; exact at 1). 2. ids outside the
+ * allow ranges become -inf. 3. m = max zt, S = sum exp(zt_i - m) in one fixed order of additions, logprob = (zt_t - m) - log(S).
+ * 4. rank = the number of ids with zt_i > zt_t (ties not counted): at_op_topk_sample's top_k = k keeps the target exactly when rank < k. A target that is
+ * not allowed, or outside [0, V), gets logprob = -inf and rank = V. */
+int at_op_score_rows(const float* logits_dev, int R, int V, const int32_t* targets_dev, float temperature, const int32_t* allow, float* logprob_out_dev,
+                     int32_t* rank_out_dev, at_stream_t stream);
 
 /* ---- the fine stage: coarse code books -> all eight (csrc/fine.hip) -----------------------------------------------------------
  * bark's non-causal fine transformer: 8 embedding tables wtes[i] [1056][E] and learned positions wpe [W][E]; n_layer pre-LN blocks (LayerNorm with gain
