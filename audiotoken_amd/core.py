@@ -319,7 +319,8 @@ class AudioToken:
 
     def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0, uniforms=None,
                     constrain: bool = False, return_logits: bool = False, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None,
-                    slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None):
+                    slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None, top_p: Optional[float] = None,
+                    min_p: Optional[float] = None):
         """Semantic ids -> the two coarse EnCodec code books: stage 1 of the reference's semantic decoder (its GPT, ``decoder.py:210-239``) on the
         KV-cached HIP decoder (semantic_decoder.py). Semantic tokenizers only. ``tokens``: a tensor / array / path of semantic ids (any
         shape, flattened), or a list of up to 64 of them, generated as one batch. Returns an ``AcousticGeneration``: ``codes`` (a list of int64
@@ -335,7 +336,9 @@ class AudioToken:
         long form takes 1 to 4096 sources and runs them through that many cache rows, each source starting when a row is free and finishing on its own
         (DESIGN.md §20); ``tick_tokens`` bounds the tokens of one model pass. A source's result does not depend on its neighbours.
         ``voice=`` (``long_form=True`` only): a ``VoicePrompt`` that every source continues, or a list with one (or None) per source. The
-        prompt's ids stand in front of the source's and its coarse codes are the first window's carry; the result covers the generated ids only."""
+        prompt's ids stand in front of the source's and its coarse codes are the first window's carry; the result covers the generated ids only.
+        ``top_p`` / ``min_p``: after the top-k, keep the ids whose mass strictly above them is below ``top_p`` of the top-k set's, and
+        the ids whose probability is at least ``min_p`` times the largest; None (or 1 / 0) is off and draws exactly what the call drew without them."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_acoustic maps semantic ids to acoustic code books; {self.tokenizer_name} has no semantic ids")
         if not long_form and (window is not None or hop is not None):
@@ -348,9 +351,9 @@ class AudioToken:
         if long_form:
             return self.semantic_decoder.to_acoustic_long(tokens, window=window, hop=hop, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
                                                           seed=seed, uniforms=uniforms, return_logits=return_logits, slots=slots, tick_tokens=tick_tokens,
-                                                          voice=voice)
+                                                          voice=voice, top_p=top_p, min_p=min_p)
         return self.semantic_decoder.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms,
-                                                 constrain=constrain, return_logits=return_logits)
+                                                 constrain=constrain, return_logits=return_logits, top_p=top_p, min_p=min_p)
 
     def score_acoustic(self, tokens, codes, temperature: float = 1.0, constrain: bool = False, include_stop: bool = True, long_form: bool = False,
                        window: Optional[int] = None, hop: Optional[int] = None, return_logits: bool = False):
@@ -462,7 +465,7 @@ class AudioToken:
 
     def to_audio(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, fine_temperature: Optional[float] = 0.5,
                  seed: int = 0, uniforms=None, fine_uniforms=None, long_form: bool = False, window: Optional[int] = None, hop: Optional[int] = None,
-                 slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None):
+                 slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None, top_p: Optional[float] = None, min_p: Optional[float] = None):
         """Semantic ids -> audio, this project's form of the reference's semantic ``decode`` (``decoder.py:210-243``): ``to_acoustic(constrain=True)``, then
         ``to_fine``, then the acoustic decoder at 8 code books (bandwidth 6). Semantic tokenizers only. ``tokens`` as ``to_acoustic`` takes them. Returns
         ``(audio, coarse, fine)``: a list of one float32 ``(1, 320 * T_b)`` CPU tensor per source, the ``AcousticGeneration`` and the ``FineGeneration``.
@@ -473,7 +476,7 @@ class AudioToken:
         its longest member needs), and the returned ``FineGeneration`` holds every source's codes.
         ``voice=`` (``long_form=True`` only): a ``VoicePrompt`` with all 8 code books that every source continues, or a list with one (or
         None) per source: its ids and code books 0 and 1 prompt stage 1, all 8 are ``to_fine``'s ``history``. The audio and both generations cover the
-        generated frames only."""
+        generated frames only. ``top_p`` / ``min_p`` are stage 1's (``to_acoustic``); the fine stage has no truncation."""
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_audio maps semantic ids to audio; {self.tokenizer_name} has no semantic ids (its own decode is the way back)")
         history = None
@@ -487,7 +490,7 @@ class AudioToken:
                 raise ValueError("to_audio: a voice prompt needs all 8 code books (the fine stage continues them)")
             history = voice.codes if not isinstance(voice, (list, tuple)) else [None if v is None else v.codes for v in rows]
         coarse = self.to_acoustic(tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, seed=seed, uniforms=uniforms, constrain=True,
-                                  long_form=long_form, window=window, hop=hop, slots=slots, tick_tokens=tick_tokens, voice=voice)
+                                  long_form=long_form, window=window, hop=hop, slots=slots, tick_tokens=tick_tokens, voice=voice, top_p=top_p, min_p=min_p)
         for b, c in enumerate(coarse.codes):
             if c is None or c.shape[1] < 1:
                 raise ValueError(f"to_audio: source {b} produced no whole frame of coarse codes (finish: {coarse.finish[b]})")
@@ -503,7 +506,8 @@ class AudioToken:
                              audio_format: str = "wav", rescale: bool = False, stream: bool = False, seed: int = 0, temperature: float = 0.8,
                              top_k: int = 100, fine_temperature: Optional[float] = 0.5, max_new_tokens: int = 1024, window: Optional[int] = None,
                              hop: Optional[int] = None, slots: int = 64, fine_slots: int = 64, round_files: int = 1024,
-                             codes_dir: Optional[os.PathLike] = None, voice=None, **kwargs) -> None:
+                             codes_dir: Optional[os.PathLike] = None, voice=None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                             **kwargs) -> None:
         """The way back from a semantic ``encode_batch_files``: ``.npy`` files of semantic ids -> audio files (semantic_files.py). Semantic
         tokenizers only (``decode_batch_files`` stays the acoustic tokenizer's, and keeps raising here). Inputs, output names, overwriting, the skipping of
         a second input that maps to one output name, sharding under ``torch.distributed``, ``audio_format`` ("wav" / "flac", checked before any model is
@@ -520,11 +524,14 @@ class AudioToken:
         ``[n, 6, W]`` fine draws, so they do not depend on the other files, the round size or the ranks. ``run_summary`` gains ``rounds``, ``gpt_ticks``,
         ``fine_passes`` and ``generated_frames``; ``run_timings`` gains ``gpt_s`` and ``fine_s`` (both inside ``stage_s``).
         ``voice=``: one ``VoicePrompt`` with all 8 code books that every file continues, as ``to_audio(long_form=True, voice=)`` does; a
-        file's ids and the prompt's may have 65536 together, and a file's fine draws count the windows of a row after the prompt's history."""
+        file's ids and the prompt's may have 65536 together, and a file's fine draws count the windows of a row after the prompt's history.
+        ``top_p`` / ``min_p``: stage 1's truncation after the top-k, checked before any model is built; None: off."""
         from . import semantic_files as SF
         from . import writer as Wr
+        from .semantic_decoder import check_truncation
         if audio_format not in Wr.AUDIO_FORMATS:
             raise ValueError(f"audio_format must be one of {Wr.AUDIO_FORMATS}, got {audio_format!r}")
+        check_truncation(top_p, min_p)
         if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
             raise ValueError(f"to_audio_batch_files maps files of semantic ids to audio files; {self.tokenizer_name} has no semantic ids "
                              "(decode_batch_files is its way back)")
@@ -535,7 +542,7 @@ class AudioToken:
                 raise ValueError(f"to_audio_batch_files: {name} must be 1 to {most}, got {value!r}")
         known = {"shard_across_ranks", "device_writer", "max_held_bytes"}
         decoder_kwargs = {k: v for k, v in kwargs.items() if k not in known}
-        stages = SF.Stages(self, seed, temperature, top_k, fine_temperature, max_new_tokens, window, hop, slots, fine_slots, voice=voice)
+        stages = SF.Stages(self, seed, temperature, top_k, fine_temperature, max_new_tokens, window, hop, slots, fine_slots, voice=voice, top_p=top_p, min_p=min_p)
         acoustic = self._fine_audio()
         acoustic.load_decoder(**decoder_kwargs)
         self.skipped_files = []

@@ -192,4 +192,6 @@ struct at_gpt {
     const float *wte = nullptr, *wpe = nullptr, *ln_f = nullptr;
     std::vector<at::GptLayer> layers;
     int32_t* flags_host = nullptr;    // pinned: the rows' finish flags as the host last saw them (GPT_MAX_B words)
+    // truncation of the generators' sampler (at_gpt_set_truncation): the nucleus' mass (1: off) and float32(log(min_p)) (-inf: off)
+    float top_p = 1.0f, lmin = -__builtin_huge_valf();
 };

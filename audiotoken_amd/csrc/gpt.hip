@@ -183,6 +183,7 @@ SampleArgs generation_args(const at_gpt* h, const GptState& s, float temperature
     sa.logits = s.logits; sa.V = h->vocab; sa.top_k = top_k; sa.temperature = temperature; sa.uniforms = uniforms; sa.u_stride = u_stride;
     sa.len = s.len; sa.done = s.done; sa.cur = s.cur; sa.step_ctr = s.step_ctr; sa.rows = s.rows; sa.samp_slot = s.samp_slot;
     sa.out_ids = out_ids; sa.out_len = out_len; sa.finish = finish; sa.logits_out = logits_out; sa.max_new = max_new; sa.block = h->block; sa.out_stride = out_stride;
+    sa.top_p = h->top_p; sa.lmin = h->lmin;
     return sa;
 }
 
@@ -375,6 +376,15 @@ void at_gpt_destroy(at_gpt_t* h) {
 int at_gpt_num_layers(const at_gpt_t* h) { return h && h->finalized ? h->n_layer : 0; }
 int at_gpt_vocab(const at_gpt_t* h) { return h && h->finalized ? h->vocab : 0; }
 int at_gpt_block_size(const at_gpt_t* h) { return h && h->finalized ? h->block : 0; }
+
+int at_gpt_set_truncation(at_gpt_t* h, float top_p, float min_p) {
+    AT_REQUIRE(h != nullptr, "null handle");
+    float lmin;
+    if (int rc = check_truncation(top_p, min_p, &lmin)) return rc;   // a refused call leaves the handle as it was
+    h->top_p = top_p;
+    h->lmin = lmin;
+    return 0;
+}
 
 size_t at_gpt_state_bytes(const at_gpt_t* h, int B, int max_len) {
     if (!(h && h->finalized)) { set_error("at_gpt_state_bytes: the model is not finalized"); return 0; }

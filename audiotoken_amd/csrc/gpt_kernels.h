@@ -50,10 +50,18 @@ struct SampleArgs {
     int *out_ids, *out_len, *finish;
     float* logits_out;        // nullable [caller's rows][out_stride][V]
     int max_new, block, out_stride;
+    // truncation: the nucleus' mass (1: off) and log(min_p) rounded to fp32 (-inf: off). With both off and no kept_out / thresh_out the
+    // launch is the sampler as it was before truncation existed.
+    float top_p = 1.0f, lmin = -__builtin_huge_valf();
+    // the op alone (at_op_nucleus_sample): the final kept count and threshold value of row b
+    int* kept_out = nullptr;
+    float* thresh_out = nullptr;
 };
 
 int check_allow(const int32_t* r, int V, Allow* out);
 int check_sampling(float temperature, int top_k);
+// top_p in (0, 1] and min_p in [0, 1), neither NaN; *lmin = float32(log(min_p)) computed in double and rounded once, -inf for 0
+int check_truncation(float top_p, float min_p, float* lmin);
 
 // One pass of the model over the R tokens of the state's list: the `steps.n` step tokens, which the embedding resolves, then the prompt tokens the begin
 // kernel wrote; then the head for the `ns` sampling rows that s.last_row names. An id outside [0, V) is clamped and reported in bit 0 of *status.

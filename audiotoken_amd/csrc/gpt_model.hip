@@ -291,6 +291,18 @@ __device__ __forceinline__ float tempered(const float* z, int i, float temperatu
     return v;
 }
 
+// ---- truncation: the pieces gpt_sample_kernel<true> adds between the radix select and the walk
+constexpr int NUCLEUS_LIST = 1024;   // a top-k set of at most this many values is compacted into LDS and finished there
+// the integer mass of one id: floor(p 2^40), p = expf(v - m) in [0, 1] (the product is exact: a power of two scales it)
+__device__ __forceinline__ unsigned long long mass_of(float v, float m) { return (unsigned long long)(expf(v - m) * 1099511627776.0f); }
+// an id stays in the nucleus iff the integer mass strictly above it is below this: ceil(top_p total), at least 1 (the maximum always stays)
+__device__ __forceinline__ unsigned long long cut_mass(float top_p, unsigned long long total) {
+    const unsigned long long t = (unsigned long long)ceil((double)top_p * (double)total);
+    return t < 1 ? 1 : (t > total ? total : t);
+}
+
+// TRUNC = false is the sampler of 17 alone. TRUNC = true adds min_p, the nucleus and the op's kept / thresh outputs; its extra LDS exists in that instance only.
+template <bool TRUNC>
 __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a) {
     __shared__ unsigned hist[256];
     __shared__ unsigned sel_prefix, sel_k;
@@ -339,7 +351,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
         }
         __syncthreads();
     }
-    const float thresh = key_value(sel_prefix);
+    float thresh = key_value(sel_prefix);
     // ---- m = the largest kept value (the largest of all: it is always kept)
     mx = wave_max(mx);
     if (lane == 0) wave_part[wave] = mx;
@@ -348,6 +360,91 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
 #pragma unroll
     for (int wv = 1; wv < SAMPLE_THREADS / 64; ++wv) m = fmaxf(m, wave_part[wv]);
     __syncthreads();
+    if constexpr (TRUNC) {
+        // ---- steps 3a and 3b on K = {zt >= thresh}: both are value thresholds, found as order keys (of v + 0, so that -0 and +0 are one value as they are
+        // for >=). Every sum is of integers through integer atomics, so nothing depends on the order in which threads arrive.
+        __shared__ unsigned long long mhist[256], list_q[NUCLEUS_LIST];
+        __shared__ unsigned list_key[NUCLEUS_LIST];
+        __shared__ unsigned long long nuc_above;
+        __shared__ unsigned nuc_prefix, nuc_key, minp_key, n_list;
+        __shared__ int n_kept;
+        const bool nucleus = a.top_p < 1.0f, min_p = a.lmin > -INFINITY;
+        const bool compact = nucleus && min(a.top_k, V) <= NUCLEUS_LIST;   // K has at least that many values; ties can still overflow the list
+        if (tid == 0) { nuc_above = 0; nuc_prefix = 0; nuc_key = minp_key = 0xffffffffu; n_list = 0; n_kept = 0; }
+        __syncthreads();
+        if (compact || min_p) {   // one walk: the lowest value of K that passes min_p, and K's (key, mass) pairs into the list
+            unsigned lo = 0xffffffffu;
+            for (int i = tid; i < V; i += SAMPLE_THREADS) {
+                const float v = tempered(z, i, a.temperature, allow);
+                if (!(v >= thresh)) continue;
+                const unsigned k = order_key(v + 0.0f);
+                if (v - m >= a.lmin) lo = min(lo, k);
+                if (compact) {
+                    const unsigned at = atomicAdd(&n_list, 1u);
+                    if (at < (unsigned)NUCLEUS_LIST) { list_key[at] = k; list_q[at] = mass_of(v, m); }
+                }
+            }
+            if (min_p && lo != 0xffffffffu) atomicMin(&minp_key, lo);
+            __syncthreads();
+        }
+        const unsigned n = n_list;   // uniform over the workgroup
+        if (compact && n <= (unsigned)NUCLEUS_LIST) {
+            // thread t owns list entry t: the mass of the entries strictly above it, and the total, in one loop over the list (LDS broadcast reads)
+            const unsigned mine = tid < (int)n ? list_key[tid] : 0u;
+            unsigned long long total = 0, above = 0;
+            for (unsigned j = 0; j < n; ++j) {
+                const unsigned long long q = list_q[j];
+                total += q;
+                if (list_key[j] > mine) above += q;
+            }
+            if (tid < (int)n && above < cut_mass(a.top_p, total)) atomicMin(&nuc_key, mine);
+            __syncthreads();
+        } else if (nucleus) {
+            // the radix descent of the select above, on masses: in every pass the one bin with (mass above it) < cut <= (mass above it) + (its own)
+            unsigned long long cut = 0;
+            for (int pass = 0; pass < 4; ++pass) {
+                const int shift = 24 - 8 * pass;
+                if (tid < 256) mhist[tid] = 0;
+                __syncthreads();
+                const unsigned prefix = nuc_prefix, mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+                const unsigned long long base = nuc_above;
+                for (int i = tid; i < V; i += SAMPLE_THREADS) {
+                    const float v = tempered(z, i, a.temperature, allow);
+                    if (!(v >= thresh)) continue;
+                    const unsigned k = order_key(v + 0.0f);
+                    if ((k & mask) == prefix) atomicAdd(&mhist[(k >> shift) & 255u], mass_of(v, m));
+                }
+                __syncthreads();
+                if (tid < 256) {
+                    unsigned long long above = base;
+                    for (int bin = 255; bin > tid; --bin) above += mhist[bin];
+                    if (pass == 0) {   // the total is every bin of the first pass
+                        unsigned long long total = above;
+                        for (int bin = tid; bin >= 0; --bin) total += mhist[bin];
+                        cut = cut_mass(a.top_p, total);
+                    }
+                    if (above < cut && cut <= above + mhist[tid]) {
+                        nuc_above = above;
+                        nuc_prefix = prefix | ((unsigned)tid << shift);
+                        if (pass == 3) nuc_key = prefix | (unsigned)tid;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        unsigned final_key = order_key(thresh + 0.0f);
+        if (minp_key != 0xffffffffu) final_key = max(final_key, minp_key);
+        if (nuc_key != 0xffffffffu) final_key = max(final_key, nuc_key);
+        thresh = key_value(final_key);
+        if (a.kept_out) {   // the op alone: the size of the final set
+            int c = 0;
+            for (int i = tid; i < V; i += SAMPLE_THREADS) c += tempered(z, i, a.temperature, allow) >= thresh ? 1 : 0;
+            if (c) atomicAdd(&n_kept, c);
+            __syncthreads();
+            if (tid == 0) a.kept_out[b] = n_kept;
+        }
+        if (a.thresh_out && tid == 0) a.thresh_out[b] = thresh;
+    }
     // ---- S and the running sums in ascending id order. A wave owns a contiguous run of ids and walks it 64 at a time (coalesced): within a group the lanes'
     // weights are scanned (shuffle scan), the groups chain through a carry, the waves' totals are added in wave order. The first walk gives the waves' totals and S,
     // the second the running sums, its carry starting from the total of the waves before.
@@ -503,8 +600,19 @@ int gpt_final_ln(const at_gpt* h, const float* x, const int* gather, float* y, i
     return 0;
 }
 
+int check_truncation(float top_p, float min_p, float* lmin) {
+    AT_REQUIRE(top_p > 0.0f && top_p <= 1.0f, "top_p must lie in (0, 1] (1: off) and not be NaN");
+    AT_REQUIRE(min_p >= 0.0f && min_p < 1.0f, "min_p must lie in [0, 1) (0: off) and not be NaN");
+    *lmin = min_p > 0.0f ? (float)std::log((double)min_p) : -INFINITY;
+    return 0;
+}
+
 int gpt_sample(const SampleArgs& a, int rows, hipStream_t stream) {
-    hipLaunchKernelGGL(gpt_sample_kernel, dim3(rows), dim3(SAMPLE_THREADS), 0, stream, a);
+    // both cuts off and nothing but the token asked for: the instance without truncation, the launch of 17
+    if (a.top_p < 1.0f || a.lmin > -INFINITY || a.kept_out || a.thresh_out)
+        hipLaunchKernelGGL(gpt_sample_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), 0, stream, a);
+    else
+        hipLaunchKernelGGL(gpt_sample_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, stream, a);
     AT_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -523,6 +631,21 @@ int at_op_topk_sample(const float* logits_dev, int B, int V, float temperature, 
     if (int rc = check_allow(allow, V, &sa.allow)) return rc;
     sa.logits = logits_dev; sa.V = V; sa.top_k = top_k; sa.temperature = temperature; sa.uniforms = uniforms_dev; sa.u_stride = 1;
     sa.out = out_dev;
+    return gpt_sample(sa, B, (hipStream_t)stream);
+}
+
+int at_op_nucleus_sample(const float* logits_dev, int B, int V, float temperature, int top_k, float top_p, float min_p, const float* uniforms_dev,
+                         const int32_t* allow, int32_t* out_dev, int32_t* kept_out_dev, float* thresh_out_dev, at_stream_t stream) {
+    AT_REQUIRE(logits_dev && uniforms_dev && out_dev, "null pointer");
+    AT_REQUIRE(B >= 1 && B <= 65535, "B must be 1 to 65535");
+    AT_REQUIRE(V >= 1 && V <= GPT_MAX_VOCAB, "V must be 1 to 65536");
+    if (int rc = check_sampling(temperature, top_k)) return rc;
+    SampleArgs sa{};
+    if (int rc = check_truncation(top_p, min_p, &sa.lmin)) return rc;
+    if (int rc = check_allow(allow, V, &sa.allow)) return rc;
+    sa.logits = logits_dev; sa.V = V; sa.top_k = top_k; sa.temperature = temperature; sa.uniforms = uniforms_dev; sa.u_stride = 1;
+    sa.top_p = top_p;
+    sa.out = out_dev; sa.kept_out = kept_out_dev; sa.thresh_out = thresh_out_dev;
     return gpt_sample(sa, B, (hipStream_t)stream);
 }
 

@@ -8,6 +8,7 @@ Stated deviations from the reference: the draws come from a cal
 reaches the model's block finishes with ``"block_size"`` instead of having its context cropped; bias-free checkpoints only."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -320,6 +321,18 @@ def seeded_uniforms(seed: int, batch: int, max_new_tokens: int) -> np.ndarray:
     return np.random.Generator(np.random.Philox(seed)).random((batch, max_new_tokens), dtype=np.float32)
 
 
+def check_truncation(top_p=None, min_p=None):
+    """``(top_p, min_p)`` as the library takes them: ``top_p`` None or 1 is off (1.0), ``min_p`` None or 0 is off (0.0). NaN, ``top_p``
+    outside (0, 1] and ``min_p`` outside [0, 1) raise ``ValueError`` before anything reaches the device."""
+    p = 1.0 if top_p is None else float(top_p)
+    q = 0.0 if min_p is None else float(min_p)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"top_p must lie in (0, 1] (None or 1: off), got {top_p!r}")
+    if not 0.0 <= q < 1.0:
+        raise ValueError(f"min_p must lie in [0, 1) (None or 0: off), got {min_p!r}")
+    return p, q
+
+
 class SemanticToAcoustic(LibHandle):
     """Owner of one ``at_gpt`` handle. ``weights``: a checkpoint path, a ``{name: array}`` dict, or None for the seeded synthetic model."""
 
@@ -350,10 +363,13 @@ class SemanticToAcoustic(LibHandle):
         return self
 
     def generate(self, prompts: Sequence[np.ndarray], max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100,
-                 stop_token: int = -1, uniforms: Optional[np.ndarray] = None, seed: int = 0, allow=None, return_logits: bool = False):
+                 stop_token: int = -1, uniforms: Optional[np.ndarray] = None, seed: int = 0, allow=None, return_logits: bool = False,
+                 top_p: Optional[float] = None, min_p: Optional[float] = None):
         """Raw generation over the model's own vocabulary: ``prompts`` a list of int id arrays (1 to 64 rows of their own lengths). Returns
         ``(ids, finish, logits)``: per row the int64 ids on the CPU, the finish reason's name and (``return_logits``) the float32 logits
-        ``[n + stopped, V]``. ``allow``: None or int ``[2][4]``, the id ranges even / odd steps may produce (include/audiotoken_hip.h)."""
+        ``[n + stopped, V]``. ``allow``: None or int ``[2][4]``, the id ranges even / odd steps may produce (include/audiotoken_hip.h).
+        ``top_p`` / ``min_p``: the nucleus and the min-p cut after the top-k; None: off."""
+        truncation = check_truncation(top_p, min_p)
         B = len(prompts)
         max_new = int(max_new_tokens)
         lens = [int(len(p)) for p in prompts]
@@ -379,9 +395,19 @@ class SemanticToAcoustic(LibHandle):
                                              state.data_ptr(), state.numel(), max_len, _cabi.current_stream_handle(dev), self._status.data_ptr()),
                         "at_gpt_generate")
 
-        ids, _, fin, logits = self._run(call, host, uniforms, B, max_new, return_logits and B >= 1 and max_new >= 1,
-                                        "at_gpt_generate: a prompt id lies outside the model's vocabulary")
+        with self._truncated(*truncation):
+            ids, _, fin, logits = self._run(call, host, uniforms, B, max_new, return_logits and B >= 1 and max_new >= 1,
+                                            "at_gpt_generate: a prompt id lies outside the model's vocabulary")
         return ids, [FINISH[f] for f in fin], logits
+
+    @contextlib.contextmanager
+    def _truncated(self, top_p: float, min_p: float):
+        """The handle's truncation (``at_gpt_set_truncation``) is ``(top_p, min_p)`` inside the block and off after it, also when the block raises."""
+        _cabi.check(self._fn("set_truncation")(self.handle, float(top_p), float(min_p)), "at_gpt_set_truncation")
+        try:
+            yield
+        finally:
+            _cabi.check(self._fn("set_truncation")(self.handle, 1.0, 0.0), "at_gpt_set_truncation")
 
     def _run(self, call, host, uniforms, B, cap, return_logits, bad_id):
         """One library call around its buffers: uploads ``host`` (int32 ids) and ``uniforms``, allocates ``ids [B, cap]`` (-1), the lengths, the finish flags
@@ -411,7 +437,8 @@ class SemanticToAcoustic(LibHandle):
         return ids, n, fin, logits
 
     def to_acoustic(self, tokens, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, seed: int = 0,
-                    uniforms: Optional[np.ndarray] = None, constrain: bool = False, return_logits: bool = False) -> AcousticGeneration:
+                    uniforms: Optional[np.ndarray] = None, constrain: bool = False, return_logits: bool = False, top_p: Optional[float] = None,
+                    min_p: Optional[float] = None) -> AcousticGeneration:
         cfg = self.config
         batch = tokens if isinstance(tokens, (list, tuple)) else [tokens]
         prompts = [prepare_source(t, cfg) for t in batch]
@@ -419,7 +446,7 @@ class SemanticToAcoustic(LibHandle):
         if constrain:   # step s: the code book of its parity, and STOP where a whole frame has been written
             a, n = cfg.ACOUSTIC_OFFSET, cfg.codebook_size
             allow = [[a, a + n, cfg.STOP_TOKEN, cfg.STOP_TOKEN + 1], [a + n, a + 2 * n, 0, 0]]
-        ids, finish, logits = self.generate(prompts, max_new_tokens, temperature, top_k, cfg.STOP_TOKEN, uniforms, seed, allow, return_logits)
+        ids, finish, logits = self.generate(prompts, max_new_tokens, temperature, top_k, cfg.STOP_TOKEN, uniforms, seed, allow, return_logits, top_p, min_p)
         return self._generation(ids, finish, logits)
 
     def _generation(self, ids, finish, logits, windows=None) -> AcousticGeneration:
@@ -435,7 +462,8 @@ class SemanticToAcoustic(LibHandle):
 
     def to_acoustic_long(self, tokens, window: Optional[int] = None, hop: Optional[int] = None, max_new_tokens: int = 1024, temperature: float = 0.8,
                          top_k: int = 100, seed: int = 0, uniforms: Optional[np.ndarray] = None, return_logits: bool = False,
-                         slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None) -> AcousticGeneration:
+                         slots: Optional[int] = None, tick_tokens: Optional[int] = None, voice=None, top_p: Optional[float] = None,
+                         min_p: Optional[float] = None) -> AcousticGeneration:
         """``to_acoustic(constrain=True)`` for sources of any length up to 65536 ids: the source is walked in windows of ``window`` ids every
         ``hop`` ids (defaults: ``default_window``), each window prompted with the acoustic ids the window before produced for their overlap, all windows of up
         to 64 sources enqueued by one library call. Every window but a source's last produces exactly ``ids_per_source_token`` ids per source id and cannot
@@ -449,8 +477,10 @@ class SemanticToAcoustic(LibHandle):
         ``voice``: a ``VoicePrompt`` that every source continues, or a list with one (or None) per source. Such a source follows the schedule
         of the prompt's ids followed by its own, its first window carrying the prompt's coarse codes as if the row had produced them; ``ids``, ``codes``,
         ``logits`` and ``uniforms`` cover what was generated only, position 0 the first id after the prompt, while ``windows`` is the schedule of the
-        concatenated source. Prompts that are one object share one entry of the device's table."""
+        concatenated source. Prompts that are one object share one entry of the device's table.
+        ``top_p`` / ``min_p``: the nucleus and the min-p cut after the top-k, at every step of every window; None: off."""
         cfg = self.config
+        truncation = check_truncation(top_p, min_p)
         r, block = int(cfg.ids_per_source_token), self.block_size
         S = default_window(cfg, block)[0] if window is None else int(window)
         H = (S // 2) // 2 * 2 if hop is None else int(hop)
@@ -527,7 +557,8 @@ class SemanticToAcoustic(LibHandle):
             queue["ticks"] = [tuple(c_trace[4 * i:4 * i + 4]) for i in range(min(c_n.value, cap_ticks))]
             queue["placement"] = [tuple(c_place[3 * i:3 * i + 3]) for i in range(B)]
 
-        ids, n, fin, logits = self._run(call, host, uniforms, B, cap, return_logits, "at_gpt_generate_long: a source id lies outside the semantic vocabulary")
+        with self._truncated(*truncation):
+            ids, n, fin, logits = self._run(call, host, uniforms, B, cap, return_logits, "at_gpt_generate_long: a source id lies outside the semantic vocabulary")
         windows = [plan[:-1] + [plan[-1][:3] + (n[b] - base[b],)] for b, plan in enumerate(plans)]
         out = self._generation(ids, [FINISH[f] for f in fin], logits, windows)
         out.ticks, out.placement = queue.get("ticks"), queue.get("placement")
@@ -650,3 +681,22 @@ def topk_sample(logits: torch.Tensor, temperature: float, top_k: int, uniforms: 
         _cabi.check(lib.at_op_topk_sample(logits.data_ptr(), logits.shape[0], logits.shape[1], float(temperature), int(top_k), uniforms.data_ptr(), c_allow,
                                           out.data_ptr(), _cabi.current_stream_handle(logits.device)), "at_op_topk_sample")
     return out
+
+
+def nucleus_sample(logits: torch.Tensor, temperature: float, top_k: int, uniforms: torch.Tensor, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                   allow=None):
+    """``at_op_nucleus_sample`` on device tensors: ``topk_sample``'s arguments with the nucleus and the min-p cut (None: off) ->
+    ``(token, kept, thresh)``, int32 / int32 / float32 ``[B]``: the draw, the size of the final set and its lowest tempered value."""
+    lib = _cabi.load()
+    p, q = check_truncation(top_p, min_p)
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+    assert uniforms.is_cuda and uniforms.dtype == torch.float32 and uniforms.is_contiguous() and uniforms.numel() == logits.shape[0]
+    out = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    kept = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    thresh = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
+    c_allow = None if allow is None else (C.c_int32 * 4)(*[int(v) for v in allow])
+    with torch.cuda.device(logits.device):
+        _cabi.check(lib.at_op_nucleus_sample(logits.data_ptr(), logits.shape[0], logits.shape[1], float(temperature), int(top_k), p, q, uniforms.data_ptr(),
+                                             c_allow, out.data_ptr(), kept.data_ptr(), thresh.data_ptr(), _cabi.current_stream_handle(logits.device)),
+                    "at_op_nucleus_sample")
+    return out, kept, thresh

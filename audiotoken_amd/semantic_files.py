@@ -148,8 +148,9 @@ class Stages:
     stage's window queue, its rows handed over longest first to cut the tail (rows are independent of each other, so the order changes no result)."""
 
     def __init__(self, tok, seed: int, temperature: float, top_k: int, fine_temperature, max_new_tokens: int, window, hop, slots: int, fine_slots: int,
-                 voice=None):
+                 voice=None, top_p=None, min_p=None):
         self.voice = voice         # one VoicePrompt that every file continues (DESIGN.md §22), or None
+        self.top_p, self.min_p = top_p, min_p   # stage 1's truncation after the top-k (DESIGN.md §24), None: off
         self.tok, self.seed, self.temperature, self.top_k, self.fine_temperature = tok, int(seed), temperature, top_k, fine_temperature
         self.max_new, self.slots, self.fine_slots = int(max_new_tokens), int(slots), int(fine_slots)
         gpt = tok._gpt()
@@ -180,7 +181,7 @@ class Stages:
         t0 = time.perf_counter()
         u = stack_gpt_draws([file_draws(self.seed, stem, cap)[0] for stem, cap in zip(stems, caps)])
         coarse = tok.to_acoustic(list(sources), max_new_tokens=self.max_new, temperature=self.temperature, top_k=self.top_k, uniforms=u, long_form=True,
-                                 window=self.S, hop=self.H, slots=self.slots, voice=self.voice)
+                                 window=self.S, hop=self.H, slots=self.slots, voice=self.voice, top_p=self.top_p, min_p=self.min_p)
         self.last_coarse = coarse
         t1 = time.perf_counter()
         have = [b for b, c in enumerate(coarse.codes) if c is not None and c.shape[1] >= 1]

@@ -730,6 +730,21 @@ int at_gpt_generate_queue_prompted(at_gpt_t* h, const int32_t* src_dev, int src_
  * running sum in ascending id order exceeds u * S; if rounding leaves none, the highest kept id whose zt is not -inf. */
 int at_op_topk_sample(const float* logits_dev, int B, int V, float temperature, int top_k, const float* uniforms_dev, const int32_t* allow, int32_t* out_dev,
                       at_stream_t stream);
+/* Truncation after the top-k. K = the ids step 3 keeps, p and m as in step 4, S_K = the sum of p over K.
+ * 3a. min_p in (0, 1): lmin = float32(log(min_p)), the logarithm in double, rounded once; an id stays iff (zt_i - m) >= lmin, one fp32 subtraction. Exact.
+ * 3b. top_p in (0, 1): G(x) = the sum of p over the ids of K with zt > x; an id stays iff G(zt_i) < top_p * S_K: the mass strictly above it is below
+ *     top_p (Hugging Face's TopPLogitsWarper, applied to the top-k set). Equal values stay or go together, the maximum always stays. The device adds
+ *     floor(p_i * 2^40) as 64-bit integers (the order of additions does not matter) and compares with ceil(top_p * that total): the kept set is the rule's
+ *     wherever no |G(x) / S_K - top_p| is below 2^-21 + 2^-22.
+ * Both are evaluated on K and intersected; with v_min and v_p the lowest values that stay, steps 4 and 5 run on zt_i >= max(v, v_min, v_p).
+ * top_p = 1 and min_p = 0 are off; NaN, top_p outside (0, 1] and min_p outside [0, 1) are refused before any device work.
+ * at_gpt_set_truncation sets both on the handle (off at creation): at_gpt_generate, at_gpt_generate_long, at_gpt_generate_queue and their prompted forms
+ * read them; a refused call leaves the handle unchanged. With both off those calls launch what they launched before and give the same ids, bit for bit.
+ * at_op_nucleus_sample is the op alone: at_op_topk_sample's arguments and rule with the two cuts, and kept_out_dev / thresh_out_dev, each NULL or device
+ * int32 / float32 [B]: the size of row b's final set and its lowest value. */
+int at_gpt_set_truncation(at_gpt_t* h, float top_p, float min_p);
+int at_op_nucleus_sample(const float* logits_dev, int B, int V, float temperature, int top_k, float top_p, float min_p, const float* uniforms_dev,
+                         const int32_t* allow, int32_t* out_dev, int32_t* kept_out_dev, float* thresh_out_dev, at_stream_t stream);
 /* Teacher-forced scoring (csrc/gpt_score.hip): the log-probability and the rank of GIVEN ids under the model, where the calls above draw ids.
  * Row b of seq_dev (device int32 [n_rows][seq_stride], n_rows 1 to 65536) holds seq_len[b] ids of the model's own vocabulary, 2 <= seq_len[b] <= max_len <=
  * block; seq_len and score_from are HOST arrays, 1 <= score_from[b] < seq_len[b]. For every p in [score_from[b], seq_len[b]) the logits at position p - 1
