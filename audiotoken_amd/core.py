@@ -501,6 +501,28 @@ class AudioToken:
         audio = [self._fine_audio().decode(c.unsqueeze(0)) for c in fine.codes]
         return audio, coarse, fine
 
+    def audio_stream(self, window: Optional[int] = None, hop: Optional[int] = None, max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100,
+                     fine_temperature: Optional[float] = 0.5, seed: int = 0, uniforms=None, fine_uniforms=None, top_p: Optional[float] = None,
+                     min_p: Optional[float] = None, keep_codes: bool = False, voice=None):
+        """``to_audio(long_form=True)`` as a stream (``SemanticAudioStream``): ``push(ids)`` semantic ids as they arrive, each call returns
+        the audio that turned final (float32 ``(1, 320 * n)``, ``n`` possibly 0), ``flush()`` the rest. One source per stream (``reset()`` starts the next);
+        several streams may be alive at once. The coarse ids and the fine codes are those of ``to_acoustic(long_form=True)`` and ``to_fine`` on the whole
+        source with the same draws; the memory does not grow with the source. The first audio of a long source needs ``W`` coarse frames (the fine model is
+        non-causal over its window): 2048 GPT ids, 683 source ids at the product sizes; then audio arrives every ``W / 2`` frames (6.8 s). A source
+        shorter than ``W`` frames gets all its audio at ``flush()``. Semantic tokenizers only; ``voice=`` is not built for streams."""
+        if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
+            raise ValueError(f"to_audio maps semantic ids to audio; {self.tokenizer_name} has no semantic ids (its own decode is the way back)")
+        if voice is not None:
+            raise ValueError("audio_stream: voice= is not built for streams (the prompted schedule changes every window); use to_audio(long_form=True, voice=)")
+        from .semantic_decoder import check_truncation
+        from .semantic_stream import SemanticAudioStream
+        check_truncation(top_p, min_p)
+        acoustic = self._fine_audio()
+        acoustic.load_decoder()
+        return SemanticAudioStream(self._gpt(), self._fine(), acoustic.decoder, window=window, hop=hop, max_new_tokens=max_new_tokens, temperature=temperature,
+                                   top_k=top_k, fine_temperature=fine_temperature, seed=seed, uniforms=uniforms, fine_uniforms=fine_uniforms, top_p=top_p,
+                                   min_p=min_p, keep_codes=keep_codes)
+
     def to_audio_batch_files(self, batch_size: int, outdir: os.PathLike, token_files: Optional[List[os.PathLike]] = None,
                              token_dir: Optional[Union[os.PathLike, Path]] = None, chunk_size: Optional[int] = None, num_workers: int = 12,
                              audio_format: str = "wav", rescale: bool = False, stream: bool = False, seed: int = 0, temperature: float = 0.8,

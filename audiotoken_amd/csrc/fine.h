@@ -103,6 +103,62 @@ private:
     std::vector<int32_t> placement_;
 };
 
+// ---- the stream's scheduler: pure host code, shared by at_fine_stream_push and tools/semantic_stream_args.hip ---------------------------
+// One row whose coarse frames arrive in pushes, no history. With T frames there, window j has run at start = j H for every j with j H + W <= T; such a
+// window is the same whether or not it turns out to be the row's last. The state's work array holds FINE_STREAM_CELLS(W) = 2 W cells, from the start of
+// the last window run on (the row's last window, at start = T - W, reads down to there), so a push is absorbed in rounds: take what fits, run what became
+// runnable, emit what turned final, shift. After non-last window j frames [j H, (j + 1) H) are final; after the last everything up to T.
+inline int fine_stream_windows_run(int64_t T, int W) { return T >= W ? (int)((T - W) / (W / 2)) + 1 : 0; }
+inline int fine_stream_cells(int W) { return 2 * W; }
+struct FineStreamRound {
+    int take;                 // new frames handed over behind the held ones
+    long long first;          // the row's frame in cell 0 during this round
+    int held;                 // frames in the array before the hand-over
+    int j_first, n_win;       // windows j_first .. j_first + n_win - 1 run at start = j H, rel = 0
+    int pad;                  // final, T < W: cells [T, W) are filled with 1024 and the single window runs (counted in n_win)
+    bool last_window;         // final: one more window at start = T - W ...
+    int last_rel;             // ... predicting buffer positions >= last_rel > 0
+    long long emit_from, emit_to;   // the row's frames that turn final in this round
+    int shift;                // cells dropped from the front after the round
+};
+class FineStreamSchedule {
+  public:
+    FineStreamSchedule(long long T_before, int n_new, bool final, int W) : T_(T_before), left_(n_new), final_(final), W_(W), H_(W / 2) {
+        j_ = fine_stream_windows_run(T_before, W);
+    }
+    bool next(FineStreamRound* r) {
+        if (done_) return false;
+        *r = FineStreamRound{};
+        r->first = first_of(j_);
+        r->held = (int)(T_ - r->first);
+        const int room = fine_stream_cells(W_) - r->held;
+        r->take = left_ < room ? left_ : room;
+        T_ += r->take;
+        left_ -= r->take;
+        r->j_first = j_;
+        r->emit_from = r->emit_to = (long long)j_ * H_;
+        j_ = fine_stream_windows_run(T_, W_);
+        r->n_win = j_ - r->j_first;
+        r->emit_to = (long long)j_ * H_;
+        if (left_ == 0) {
+            done_ = true;
+            if (final_) {
+                if (T_ < W_) { r->pad = (int)(W_ - T_); r->n_win = 1; }
+                else if ((T_ - W_) % H_ != 0) { r->last_window = true; r->last_rel = (int)((long long)j_ * H_ - (T_ - W_)); }
+                r->emit_to = T_;
+            }
+        }
+        r->shift = done_ && final_ ? 0 : (int)(first_of(j_) - r->first);
+        return r->take > 0 || r->n_win > 0 || r->last_window || r->emit_to > r->emit_from;
+    }
+  private:
+    long long first_of(int j) const { return j > 0 ? (long long)(j - 1) * H_ : 0; }
+    long long T_;
+    int left_, j_ = 0;
+    bool final_, done_ = false;
+    int W_, H_;
+};
+
 }  // namespace at
 
 struct at_fine {

@@ -693,3 +693,192 @@ int at_fine_generate_queue_hist(at_fine_t* h, const int32_t* coarse_dev, const i
 }
 
 }  // extern "C"
+
+// ---- the stream: one row whose coarse frames arrive in pushes -----------------------------------------------------------------
+namespace {
+
+constexpr int HANDOVER_BAD_ID = 4;   // status bit 2
+
+// The GPT's new ids into the work array: thread t = cell t. A frame's two ids are one 8-byte load (interleaved; code book 0 carries `offset`, code book 1
+// offset + codebook_size), its cell two 16-byte stores: channels 0 and 1, and 1024 ("nothing yet") in channels 2 to 7. A frame with an id outside its code
+// book (or past the fine model's 1024 ids) is reported in bit 2 of *status and not written. Cells [n, n + n_pad) get 1024 in all 8 channels: the padding
+// of a row shorter than the window. ones: NULL, or the attention's key mask [W], written here by the call's first launch.
+__global__ __launch_bounds__(256) void fine_handover_kernel(const int2* ids, int n, int n_pad, int offset, int codebook_size, int* work, float* ones, int W, int* status) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ones && t < W) ones[t] = 1.0f;
+    if (t >= n + n_pad) return;
+    int4* cell = reinterpret_cast<int4*>(work + (size_t)t * FINE_CODES);
+    int c0 = FINE_VOCAB, c1 = FINE_VOCAB;
+    if (t < n) {
+        const int2 id = ids[t];
+        const int top = min(codebook_size, FINE_VOCAB);
+        c0 = id.x - offset;
+        c1 = id.y - offset - codebook_size;
+        if (c0 < 0 || c0 >= top || c1 < 0 || c1 >= top) {
+            if (status) atomicOr(status, HANDOVER_BAD_ID);
+            return;
+        }
+    }
+    cell[0] = make_int4(c0, c1, FINE_VOCAB, FINE_VOCAB);
+    cell[1] = make_int4(FINE_VOCAB, FINE_VOCAB, FINE_VOCAB, FINE_VOCAB);
+}
+
+// The frames that just turned final, cells [cell0, cell0 + n) of the work array, as columns [col0, col0 + n) of out, int64 [8][stride]: what
+// AcousticDecodeStream.push takes on the device. Thread t = frame t: two 16-byte loads, eight 8-byte stores that are contiguous across the wave.
+__global__ __launch_bounds__(256) void fine_emit_kernel(const int* work, int cell0, int n, long long* out, int stride, int col0) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)cell0 + t) * FINE_CODES);
+    const int4 lo = cell[0], hi = cell[1];
+    const int ids[FINE_CODES] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+    for (int ch = 0; ch < FINE_CODES; ++ch) out[(size_t)ch * stride + col0 + t] = ids[ch];
+}
+
+// work cells [0, n) = cells [shift, shift + n): one workgroup, every cell read before any is written (n is at most 2 W <= 2048: two cells a thread)
+__global__ __launch_bounds__(1024) void fine_stream_shift_kernel(int* work, int shift, int n) {
+    int4 v[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int t = threadIdx.x + 1024 * i;
+        if (t < n) {
+            const int4* src = reinterpret_cast<const int4*>(work + ((size_t)shift + t) * FINE_CODES);
+            v[i][0] = src[0]; v[i][1] = src[1];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int t = threadIdx.x + 1024 * i;
+        if (t < n) {
+            int4* dst = reinterpret_cast<int4*>(work + (size_t)t * FINE_CODES);
+            dst[0] = v[i][0]; dst[1] = v[i][1];
+        }
+    }
+}
+
+int launch_handover(const int32_t* ids, int n, int n_pad, int offset, int codebook_size, int* work, float* ones, int W, int32_t* status, hipStream_t stream) {
+    const int mask = ones ? W : 0, span = n + n_pad > mask ? n + n_pad : mask;
+    if (span <= 0) return 0;
+    hipLaunchKernelGGL(fine_handover_kernel, dim3((span + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const int2*>(ids), n, n_pad, offset, codebook_size, work,
+                       ones, W, status);
+    AT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int check_handover(const int32_t* ids_dev, int n_frames, int acoustic_offset, int codebook_size) {
+    AT_REQUIRE(n_frames >= 0 && (ids_dev != nullptr || n_frames == 0), "n_frames must not be negative, and frames need a pointer");
+    AT_REQUIRE((reinterpret_cast<uintptr_t>(ids_dev) & 7) == 0, "ids_dev must be 8-byte aligned: a frame is one load");
+    AT_REQUIRE(acoustic_offset >= 0 && codebook_size >= 1 && (int64_t)acoustic_offset + 2 * (int64_t)codebook_size <= INT32_MAX, "the two code books must be ranges of int32 ids");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t at_fine_stream_state_bytes(const at_fine_t* h) {
+    if (!(h && h->finalized)) { set_error("at_fine_stream_state_bytes: the model is not finalized"); return 0; }
+    return carve_state(nullptr, 1, fine_stream_cells(h->block), 0, h->block, h->embd).bytes;
+}
+
+int at_op_fine_handover(const int32_t* ids_dev, int n_frames, int n_pad, int acoustic_offset, int codebook_size, int32_t* work_dev, at_stream_t stream,
+                        int32_t* status_dev) {
+    if (int rc = check_handover(ids_dev, n_frames, acoustic_offset, codebook_size)) return rc;
+    AT_REQUIRE(work_dev != nullptr && n_pad >= 0 && (int64_t)n_frames + n_pad <= FINE_MAX_T, "a work array of n_frames + n_pad cells, at most 262144");
+    AT_REQUIRE((reinterpret_cast<uintptr_t>(work_dev) & 15) == 0, "work_dev must be 16-byte aligned");
+    return launch_handover(ids_dev, n_frames, n_pad, acoustic_offset, codebook_size, work_dev, nullptr, 0, status_dev, (hipStream_t)stream);
+}
+
+int at_fine_stream_push(at_fine_t* h, void* state_dev, size_t state_bytes, int64_t* pos, const int32_t* ids_dev, int n_frames, int final, int acoustic_offset,
+                        int codebook_size, float temperature, int greedy, const float* uniforms_dev, int u_win0, int u_windows, int64_t* emit_dev,
+                        int emit_stride, int32_t* n_emitted, int32_t* windows_run, at_stream_t stream_, int32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized, "the model is not finalized");
+    AT_REQUIRE(state_dev != nullptr, "null state");
+    AT_REQUIRE(pos && n_emitted, "null pointer");
+    AT_REQUIRE(final == 0 || final == 1, "final must be 0 or 1");
+    AT_REQUIRE(greedy == 0 || greedy == 1, "greedy must be 0 or 1");
+    AT_REQUIRE(greedy || (std::isfinite(temperature) && temperature > 0.0f), "temperature must be a positive finite number");
+    if (int rc = check_handover(ids_dev, n_frames, acoustic_offset, codebook_size)) return rc;
+    AT_REQUIRE(pos[1] == 0, "the stream is finished: a push after the final call");
+    AT_REQUIRE(pos[0] >= 0 && pos[0] + n_frames <= FINE_MAX_T, "a stream takes at most 262144 frames");
+    AT_REQUIRE(!final || pos[0] + n_frames >= 1, "a final call with nothing pushed");
+    AT_REQUIRE(u_win0 >= 0 && u_windows >= 0 && emit_stride >= 0, "u_win0, u_windows and emit_stride must not be negative");
+    const int W = h->block, H = W / 2;
+    // ---- a dry run of the schedule: the windows and the frames of this call against the caller's arrays
+    int n_win = 0, j_lo = -1, j_hi = -1;
+    long long emitted = 0;
+    {
+        FineStreamSchedule dry(pos[0], n_frames, final != 0, W);
+        FineStreamRound rd;
+        while (dry.next(&rd)) {
+            const int n = rd.n_win + (rd.last_window ? 1 : 0);
+            if (n > 0) { if (j_lo < 0) j_lo = rd.j_first; j_hi = rd.j_first + n; }
+            n_win += n;
+            emitted += rd.emit_to - rd.emit_from;
+        }
+    }
+    AT_REQUIRE(greedy || n_win == 0 || (uniforms_dev != nullptr && j_lo >= u_win0 && j_hi <= u_win0 + u_windows), "the uniforms do not cover the windows this call runs");
+    AT_REQUIRE(emitted == 0 || (emit_dev != nullptr && emitted <= emit_stride), "emit_dev must hold the frames that turn final in this call");
+    const FineState s = carve_state(state_dev, 1, fine_stream_cells(W), 0, W, h->embd);
+    AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_stream_state_bytes(h)");
+    // ---- nothing above touched the device
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    hipStream_t stream = (hipStream_t)stream_;
+    FineSampleArgs sa{};
+    sa.logits = s.logits; sa.W = W; sa.greedy = greedy; sa.temperature = greedy ? 1.0f : temperature;
+    sa.uniforms = uniforms_dev; sa.work = s.work;
+    auto run_window = [&](int cell, int j, int rel) -> int {
+        FinePass p{};
+        p.n = 1;
+        p.cell0[0] = cell;
+        p.draw[0] = j - u_win0;
+        p.rel[0] = rel;
+        p.head_off[1] = W - rel;
+        sa.total = W - rel;
+        for (int cb = FINE_COARSE; cb < FINE_CODES; ++cb) {
+            if (int rc = run_forward(h, s, p, cb, stream)) return rc;
+            sa.c = cb;
+            hipLaunchKernelGGL(fine_sample_kernel, dim3((sa.total + SAMPLE_WAVES - 1) / SAMPLE_WAVES), dim3(64 * SAMPLE_WAVES), 0, stream, p, sa);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+        return 0;
+    };
+    FineStreamSchedule schedule(pos[0], n_frames, final != 0, W);
+    FineStreamRound rd;
+    int taken = 0, col = 0;
+    bool first = true;
+    const long long T = pos[0] + n_frames;
+    while (schedule.next(&rd)) {
+        if (rd.take > 0 || rd.pad > 0 || (first && n_win > 0))
+            if (int rc = launch_handover(ids_dev + 2 * (size_t)taken, rd.take, rd.pad, acoustic_offset, codebook_size, s.work + (size_t)rd.held * FINE_CODES,
+                                         first ? s.ones : nullptr, W, status_dev, stream))
+                return rc;
+        first = false;
+        taken += rd.take;
+        const int plain = rd.pad ? 1 : rd.n_win;
+        for (int i = 0; i < plain; ++i)
+            if (int rc = run_window((int)((long long)(rd.j_first + i) * H - rd.first), rd.j_first + i, 0)) return rc;
+        if (rd.last_window)
+            if (int rc = run_window((int)(T - W - rd.first), rd.j_first + rd.n_win, rd.last_rel)) return rc;
+        const int n = (int)(rd.emit_to - rd.emit_from);
+        if (n > 0) {
+            hipLaunchKernelGGL(fine_emit_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, s.work, (int)(rd.emit_from - rd.first), n,
+                               reinterpret_cast<long long*>(emit_dev), emit_stride, col);
+            AT_CHECK_HIP(hipGetLastError());
+            col += n;
+        }
+        if (rd.shift > 0) {
+            hipLaunchKernelGGL(fine_stream_shift_kernel, dim3(1), dim3(1024), 0, stream, s.work, rd.shift, rd.held + rd.take - rd.shift);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+    }
+    pos[0] = T;
+    pos[1] = final;
+    *n_emitted = (int)emitted;
+    if (windows_run) *windows_run = n_win;
+    return 0;
+}
+
+}  // extern "C"

@@ -172,6 +172,46 @@ class GptQueueSchedule {
     std::vector<int32_t> placement_;
 };
 
+// ---- the stream's scheduler: pure host code, shared by at_gpt_stream_push and tools/semantic_stream_args.hip ------------------------------
+// One source whose ids arrive in pushes. With n ids there, window k has run (as a non-final window) for every k with n > k H + S: one id past the window
+// must exist, since with exactly k H + S ids the window may still be the final one. The state's source buffer holds 2 S ids, from id `k H` of the next
+// window to run on, so a push is absorbed in rounds: take what fits, run what became runnable, drop the (windows run) * H ids no window reads again.
+inline int gpt_stream_windows_run(int64_t n, int S, int H) { return n > S ? (int)((n - S - 1) / H) + 1 : 0; }
+struct GptStreamRound {
+    int take;            // new ids copied behind the held ones
+    int held;            // ids in the buffer before the copy; the buffer's first id is id k_first * H of the source
+    int k_first, n_win;  // non-final windows k_first .. k_first + n_win - 1 run in this round
+    bool final_window;   // then window k_first + n_win runs as the final one, on the ids that are left
+    int final_ids;       // its source ids
+};
+class GptStreamSchedule {
+  public:
+    GptStreamSchedule(int64_t n_before, int n_new, bool final, int S, int H) : n_(n_before), left_(n_new), final_(final), S_(S), H_(H) {
+        k_ = gpt_stream_windows_run(n_before, S, H);
+    }
+    bool next(GptStreamRound* r) {
+        if (done_) return false;
+        *r = GptStreamRound{};
+        r->held = (int)(n_ - (int64_t)k_ * H_);
+        r->take = left_ < 2 * S_ - r->held ? left_ : 2 * S_ - r->held;
+        n_ += r->take;
+        left_ -= r->take;
+        r->k_first = k_;
+        k_ = gpt_stream_windows_run(n_, S_, H_);
+        r->n_win = k_ - r->k_first;
+        if (left_ == 0) {
+            done_ = true;
+            if (final_) { r->final_window = true; r->final_ids = (int)(n_ - (int64_t)k_ * H_); }
+        }
+        return r->take > 0 || r->n_win > 0 || r->final_window;
+    }
+  private:
+    int64_t n_;
+    int left_, k_ = 0;
+    bool final_, done_ = false;
+    int S_, H_;
+};
+
 struct GptHostTensor {
     std::vector<int64_t> shape;
     std::vector<float> data;

@@ -651,3 +651,135 @@ int at_gpt_generate_queue_prompted(at_gpt_t* h, const int32_t* src_dev, int src_
 }
 
 }  // extern "C"
+
+// ---- the stream: one source whose ids arrive in pushes ------------------------------------------------------------------------
+namespace {
+
+// The stream's own buffers behind the one-row generation state: the source ids no window has left behind (2 S), and the last r (S - H) stream ids
+struct GptStreamState {
+    GptState g;
+    int *src, *carry;
+    size_t bytes;
+};
+GptStreamState carve_stream(void* base, const at_gpt* h, int S, int H, int r) {
+    GptStreamState st{};
+    st.g = carve_state(base, 1, h->block, h->block, h->vocab, h->n_layer);
+    char* p = static_cast<char*>(base);
+    size_t off = st.g.bytes;
+    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += round256(bytes); return q; };
+    st.src = (int*)take((size_t)2 * S * 4);
+    st.carry = (int*)take((size_t)r * (S - H) * 4 + 4);
+    st.bytes = off;
+    return st;
+}
+
+// buf[0 .. n) = buf[shift .. shift + n): one workgroup, every id read before any is written (n is at most 2 S <= 1024)
+__global__ __launch_bounds__(1024) void gpt_stream_shift_kernel(int* buf, int shift, int n) {
+    const int t = threadIdx.x;
+    const int v = t < n ? buf[shift + t] : 0;
+    __syncthreads();
+    if (t < n) buf[t] = v;
+}
+
+int check_stream_geometry(const at_gpt* h, int S, int H, int r) {
+    AT_REQUIRE(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0, "the window S and the hop H must be even, at least 2");
+    AT_REQUIRE(H <= S, "the hop H must not exceed the window S");
+    AT_REQUIRE(r >= 1 && r <= GPT_MAX_BLOCK, "r (acoustic ids per source id) must be 1 to 1024");
+    AT_REQUIRE((int64_t)S + 1 + (int64_t)r * S <= h->block, "a window does not fit: S + 1 + r S must not exceed the model's block size");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t at_gpt_stream_state_bytes(const at_gpt_t* h, int S, int H, int r) {
+    if (!(h && h->finalized)) { set_error("at_gpt_stream_state_bytes: the model is not finalized"); return 0; }
+    if (check_stream_geometry(h, S, H, r)) return 0;
+    return carve_stream(nullptr, h, S, H, r).bytes;
+}
+
+int at_gpt_stream_push(at_gpt_t* h, void* state_dev, size_t state_bytes, int64_t* pos, const int32_t* ids_dev, int n_new, int final, int S, int H, int r,
+                       int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
+                       float temperature, int top_k, const float* uniforms_dev, int64_t u_pos0, int64_t u_len, int32_t* out_ids_dev, int out_cap,
+                       int32_t* out_len_dev, int32_t* finish_dev, int32_t* windows_run, at_stream_t stream_, int32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized, "the model is not finalized");
+    AT_REQUIRE(state_dev != nullptr, "null state");
+    AT_REQUIRE(pos && uniforms_dev && out_ids_dev && out_len_dev && finish_dev, "null pointer");
+    AT_REQUIRE(final == 0 || final == 1, "final must be 0 or 1");
+    AT_REQUIRE(n_new >= 0 && (ids_dev != nullptr || n_new == 0), "n_new must not be negative, and ids need a pointer");
+    AT_REQUIRE(pos[1] == 0, "the stream is finished: a push after the final call");
+    AT_REQUIRE(pos[0] >= 0 && pos[0] + n_new <= GPT_MAX_SOURCE, "a stream takes at most 65536 ids");
+    AT_REQUIRE(!final || pos[0] + n_new >= 1, "a final call with nothing pushed");
+    const int block = h->block;
+    Rules q{};
+    if (int rc = check_long_rules(h, S, H, r, ids_dev, 1, semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token, max_new, temperature,
+                                  top_k, status_dev, &q))
+        return rc;
+    AT_REQUIRE(u_pos0 >= 0 && u_len >= 0 && out_cap >= 0, "u_pos0, u_len and out_cap must not be negative");
+    // ---- the windows this call runs and what they need of the caller's arrays
+    const int k0 = gpt_stream_windows_run(pos[0], S, H), k1 = gpt_stream_windows_run(pos[0] + n_new, S, H);
+    const int carry = r * (S - H);
+    const int64_t p_base = k0 > 0 ? (int64_t)r * k0 * H : 0;   // the stream position of out_ids_dev[0]
+    if (k1 > k0 || final) {
+        const int64_t N = pos[0] + n_new;
+        const GptWindow first = gpt_window((int)(final && k0 == k1 ? N : (int64_t)k0 * H + S + 1), k0, S, H, r, max_new, block);
+        const GptWindow last = gpt_window((int)(final ? N : (int64_t)(k1 - 1) * H + S + 1), final ? k1 : k1 - 1, S, H, r, max_new, block);
+        const int64_t end = (int64_t)last.stream_base + last.budget;
+        AT_REQUIRE(first.stream_base >= u_pos0 && end <= u_pos0 + u_len, "the uniforms do not cover the stream positions this call draws");
+        AT_REQUIRE(end - p_base <= out_cap, "out_cap must hold the carry and the ids this call can produce");
+    }
+    const GptStreamState st = carve_stream(state_dev, h, S, H, r);
+    AT_REQUIRE(state_bytes >= st.bytes, "state too small: at_gpt_stream_state_bytes(h, S, H, r)");
+    // ---- nothing above touched the device
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    hipStream_t stream = (hipStream_t)stream_;
+    // the sampler and the begin kernel index the stream by absolute position: the call's arrays are addressed from the position of their first element
+    int32_t* out_abs = reinterpret_cast<int32_t*>(reinterpret_cast<intptr_t>(out_ids_dev) - (intptr_t)p_base * 4);
+    const float* u_abs = reinterpret_cast<const float*>(reinterpret_cast<intptr_t>(uniforms_dev) - (intptr_t)u_pos0 * 4);
+    const SampleArgs sa = generation_args(h, st.g, temperature, top_k, u_abs, 0, out_abs, 0, out_len_dev, finish_dev, nullptr, max_new);
+    if ((k1 > k0 || final) && k0 > 0) AT_CHECK_HIP(hipMemcpyAsync(out_ids_dev, st.carry, (size_t)carry * 4, hipMemcpyDeviceToDevice, stream));
+    const TickPlan step_plan = lockstep_steps(1);
+    auto run_window = [&](int k, int n_src_ids, bool last) -> int {
+        const GptWindow w = gpt_window(last ? k * H + n_src_ids : k * H + S + 1, k, S, H, r, max_new, block);
+        TickPlan begin{};
+        begin.start(0, 0, k, w.P, last);
+        for (int step = 0; step < w.budget; ++step) {
+            if (int rc = run_tick(h, st.g, step == 0 ? begin : step_plan, q, sa, stream)) return rc;
+            if (last && (step + 1) % GPT_CHECK_EVERY == 0 && step + 1 < w.budget) {   // the host's only look at the device: the final window's flag
+                bool all;
+                if (int rc = all_done(h, st.g, 1, stream, &all)) return rc;
+                if (all) break;
+            }
+        }
+        return 0;
+    };
+    GptStreamSchedule schedule(pos[0], n_new, final != 0, S, H);
+    GptStreamRound rd;
+    int taken = 0, ran = 0;
+    while (schedule.next(&rd)) {
+        if (rd.take > 0) AT_CHECK_HIP(hipMemcpyAsync(st.src + rd.held, ids_dev + taken, (size_t)rd.take * 4, hipMemcpyDeviceToDevice, stream));
+        taken += rd.take;
+        // the begin kernel reads source id k H + i of window k: the buffer is addressed from the source position of its first id
+        q.src = reinterpret_cast<const int*>(reinterpret_cast<intptr_t>(st.src) - (intptr_t)rd.k_first * H * 4);
+        for (int k = rd.k_first; k < rd.k_first + rd.n_win; ++k)
+            if (int rc = run_window(k, S, false)) return rc;
+        if (rd.final_window)
+            if (int rc = run_window(rd.k_first + rd.n_win, rd.final_ids, true)) return rc;
+        ran += rd.n_win + (rd.final_window ? 1 : 0);
+        if (rd.n_win > 0 && !rd.final_window) {
+            hipLaunchKernelGGL(gpt_stream_shift_kernel, dim3(1), dim3(1024), 0, stream, st.src, rd.n_win * H, rd.held + rd.take - rd.n_win * H);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+    }
+    // the carry of the next call's first window: the last r (S - H) ids of what has been produced
+    if (k1 > k0 && !final && carry > 0)
+        AT_CHECK_HIP(hipMemcpyAsync(st.carry, out_abs + (int64_t)r * k1 * H, (size_t)carry * 4, hipMemcpyDeviceToDevice, stream));
+    pos[0] += n_new;
+    pos[1] = final;
+    if (windows_run) *windows_run = ran;
+    return 0;
+}
+
+}  // extern "C"

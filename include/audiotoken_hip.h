@@ -855,6 +855,45 @@ int at_fine_generate_queue_hist(at_fine_t* h, const int32_t* coarse_dev, const i
                                 int max_T, int slots, int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream,
                                 int32_t* status_dev);
 
+/* ---- the semantic-to-audio stream: one source, pushed as its ids arrive -------------------------------------------------------
+ * Both stages run the windows of the calls above as soon as their inputs exist; ids, logits and codes are those of at_gpt_generate_long and
+ * at_fine_generate on the whole source at one row. The device state of each stage is caller-owned and its size does not depend on the stream's
+ * length. `pos` is the stream's HOST record, int64 [2] = {items pushed so far, 1 after the final call}, zeroed by the caller to start a stream and
+ * updated by a call that succeeds. Every argument, the geometry, the state's size, a push after the final call and a final call with nothing pushed
+ * are refused before the device is touched. All launches go on `stream`; neither call is re-entrant per handle.
+ *
+ * at_gpt_stream_push: n_new (>= 0) source ids, device int32. Window k of at_gpt_generate_long's schedule runs as a NON-final window as soon as
+ * more than k H + S ids exist; final = 1 runs the one remaining window as the final one (STOP on even steps, budget min(max_new, block - prompt)).
+ * The state (at_gpt_stream_state_bytes: the K / V cache and activations of one row, 2 S source ids, the last r (S - H) stream ids) keeps the ids no
+ * window has left behind yet; a long push is absorbed 2 S ids at a time. out_ids_dev: device int32 [out_cap], this call's piece of the stream: with k0
+ * windows run before the call it starts at stream position r k0 H, so for k0 > 0 its first r (S - H) entries are the carry and the ids this call
+ * produced follow; for k0 = 0 they start at entry 0. out_cap must hold them (the final window: its budget). The draw of stream position p is
+ * uniforms_dev[p - u_pos0]; the call refuses when a window it will run needs a position outside [u_pos0, u_pos0 + u_len). out_len_dev / finish_dev: one
+ * device word each, as row 0 of at_gpt_generate_long has them (the length counts the whole stream). windows_run: NULL or HOST, the windows this call
+ * ran. The host looks at the device only while the final window runs (its flag, every 16 steps). at_gpt_set_truncation applies. */
+size_t at_gpt_stream_state_bytes(const at_gpt_t* h, int S, int H, int r);
+int at_gpt_stream_push(at_gpt_t* h, void* state_dev, size_t state_bytes, int64_t* pos, const int32_t* ids_dev, int n_new, int final, int S, int H, int r,
+                       int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
+                       float temperature, int top_k, const float* uniforms_dev, int64_t u_pos0, int64_t u_len, int32_t* out_ids_dev, int out_cap,
+                       int32_t* out_len_dev, int32_t* finish_dev, int32_t* windows_run, at_stream_t stream, int32_t* status_dev);
+/* at_fine_stream_push: n_frames (>= 0) new coarse frames as the GPT wrote them: ids_dev device int32 [2 n_frames], interleaved, code book 0 carrying
+ * acoustic_offset and code book 1 acoustic_offset + codebook_size (8-byte aligned). The state (at_fine_stream_state_bytes) holds a window onto the
+ * row's work array: 2 W cells, from the start of the last window run on; a long push is absorbed as far as that leaves room. Window j of
+ * at_fine_generate's schedule runs at start = j W/2 as soon as j W/2 + W frames exist; final = 1 (T = the frames pushed in all) runs the padded single
+ * window when T < W, or the last window at start = T - W with rel > 0 when the windows run do not cover T. After non-last window j frames
+ * [j W/2, (j + 1) W/2) are final, after the last window everything up to T: they are written to emit_dev, device int64 [8][emit_stride], in order from
+ * column 0 (what AcousticDecodeStream.push takes); n_emitted (HOST, not NULL) is their count, and emit_stride must hold it. The draw of window j, code
+ * book 2 + c, buffer position t is uniforms_dev[((j - u_win0) * 6 + c) * W + t]; a window outside [u_win0, u_win0 + u_windows) is refused. An id
+ * outside its code book sets bit 2 of *status_dev and its frame is left as it was. greedy / temperature as at_fine_generate. */
+size_t at_fine_stream_state_bytes(const at_fine_t* h);
+int at_fine_stream_push(at_fine_t* h, void* state_dev, size_t state_bytes, int64_t* pos, const int32_t* ids_dev, int n_frames, int final, int acoustic_offset,
+                        int codebook_size, float temperature, int greedy, const float* uniforms_dev, int u_win0, int u_windows, int64_t* emit_dev,
+                        int emit_stride, int32_t* n_emitted, int32_t* windows_run, at_stream_t stream, int32_t* status_dev);
+/* The hand-over kernel alone: frames 0 .. n_frames - 1 of ids_dev (as above) into channels 0 and 1 of work_dev (device int32 [n_frames + n_pad][8]),
+ * 1024 into channels 2 to 7; cells [n_frames, n_frames + n_pad) get 1024 in all 8. Status bit 2 as above. */
+int at_op_fine_handover(const int32_t* ids_dev, int n_frames, int n_pad, int acoustic_offset, int codebook_size, int32_t* work_dev, at_stream_t stream,
+                        int32_t* status_dev);
+
 #ifdef __cplusplus
 }
 #endif
