@@ -1,12 +1,8 @@
-// The handle of the fine stage (fine.hip), declared apart from its code so that the stand-alone argument check (tools/fine_args.hip) can
-// build a finalized handle with no device behind it: every entry point validates against the handle's dimensions alone before it touches one.
+// The handle of the fine stage (fine.hip) and the pure host arithmetic of its schedules, declared apart from the code so that the stand-alone
+// argument checks (tools/fine_*args.hip) can build a finalized handle with no device behind it: every entry point validates against the handle's dimensions
+// alone before it touches one. The handle's plumbing (staging, upload, allocations) and the state carver are model_handle.h's, shared with the GPT.
 #pragma once
-#include <cstdint>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "at_common.h"
+#include "model_handle.h"
 
 namespace at {
 
@@ -18,11 +14,6 @@ constexpr int FINE_TABLE = 1056;       // rows of an embedding table and of a he
 constexpr int FINE_VOCAB = 1024;       // the ids a head may produce; 1024 itself is the "nothing yet" id of a cell
 constexpr int FINE_MAX_B = 64, FINE_MAX_BLOCK = 1024, FINE_MAX_LAYERS = 48;
 constexpr int FINE_MAX_T = 1 << 18;    // frames of one row (58 minutes at 75 frames a second)
-
-struct FineHostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
 
 struct FineLayer {
     const float *ln1_g = nullptr, *ln1_b = nullptr, *qkv = nullptr, *proj = nullptr, *ln2_g = nullptr, *ln2_b = nullptr, *fc = nullptr, *fc_proj = nullptr;
@@ -161,13 +152,9 @@ class FineStreamSchedule {
 
 }  // namespace at
 
-struct at_fine {
-    int device = 0;
-    bool finalized = false;
-    std::map<std::string, at::FineHostTensor> staged;
+struct at_fine : at::ModelHandle {  // device, finalized, staged, allocs
     int n_layer = 0, embd = 0, block = 0;
     bool bias = false;                // the four linears of every block carry a bias
-    std::vector<void*> allocs;        // every device allocation of finalize()
     const float* wtes[at::FINE_CODES] = {};
     const float* heads[at::FINE_HEADS] = {};
     const float *wpe = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;

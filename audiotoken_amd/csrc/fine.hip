@@ -9,7 +9,9 @@
 //   fine_sample_kernel   one wave per position over its 1024 logits: the argmax or the inverse-CDF draw, written straight into the work array
 //   fine_finish_kernel   the T cells after the history of the rows that leave a slot, as [8][T]
 // A call enqueues every window of every row without looking at the device: the host knows the schedule from the lengths. No float is added atomically.
-// Both generators are one loop (run_passes) over the passes of FineQueueSchedule (fine.h): at_fine_generate is the queue with a slot per row.
+// Both generators are one function (generate) and one loop (run_passes) over the passes of FineQueueSchedule (fine.h): at_fine_generate is
+// the queue with a slot per row. A pass's six code books are run_codebooks, which the stream's windows use as well. The handle's plumbing
+// and the state carver are model_handle.h's, shared with the GPT.
 #include <cmath>
 #include <cstring>
 
@@ -31,24 +33,20 @@ struct FineState {
     size_t bytes;
 };
 
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
 // max_hist: the longest history of the call (0 = none); a work array then holds min(H, max_hist) + max_T cells
 FineState carve_state(void* base, int B, int max_T, int max_hist, int W, int E) {
     FineState s{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += round256(bytes); return r; };
+    StateCarver c(base);
     const size_t R = (size_t)B * W;
     s.Lmax = fine_cells(max_T, W, fine_history(max_hist, W));
-    s.work = (int*)take((size_t)B * s.Lmax * FINE_CODES * 4);
-    s.ones = (float*)take(R * 4);
-    s.x = (float*)take(R * E * 4);
-    s.xn = (float*)take(R * E * 4);
-    s.qkv = (float*)take(R * 3 * E * 4);
-    s.h = (float*)take(R * 4 * E * 4);       // the MLP's hidden rows; before the head, the gathered rows
-    s.logits = (float*)take(R * FINE_VOCAB * 4);
-    s.bytes = off;
+    s.work = c.take<int>((size_t)B * s.Lmax * FINE_CODES);
+    s.ones = c.take<float>(R);
+    s.x = c.take<float>(R * E);
+    s.xn = c.take<float>(R * E);
+    s.qkv = c.take<float>(R * 3 * E);
+    s.h = c.take<float>(R * 4 * E);          // the MLP's hidden rows; before the head, the gathered rows
+    s.logits = c.take<float>(R * FINE_VOCAB);
+    s.bytes = c.off;
     return s;
 }
 
@@ -284,26 +282,30 @@ int run_forward(const at_fine* h, const FineState& s, const FinePass& p, int c, 
     return dense(s.xn, total, E, h->heads[c - 1], nullptr, FINE_VOCAB, s.logits, nullptr, EPI_NONE);
 }
 
-const FineHostTensor* staged(const at_fine* h, const std::string& name) {
-    auto it = h->staged.find(name);
-    return it == h->staged.end() ? nullptr : &it->second;
-}
-
-int upload(at_fine* h, const std::string& name, std::vector<int64_t> shape, const float** dst) {
-    const FineHostTensor* t = staged(h, name);
-    if (!t) { set_error("at_fine_finalize: missing tensor " + name); return -1; }
-    if (t->shape != shape) { set_error("at_fine_finalize: tensor " + name + " has an unexpected shape"); return -1; }
-    void* d = nullptr;
-    AT_CHECK_HIP(hipMalloc(&d, t->data.size() * sizeof(float)));
-    h->allocs.push_back(d);
-    AT_CHECK_HIP(hipMemcpy(d, t->data.data(), t->data.size() * sizeof(float), hipMemcpyHostToDevice));
-    *dst = static_cast<const float*>(d);
+// the six code books of one pass: for each the forward, then the sampler, which writes the code book's ids into the work arrays the next forward reads
+int run_codebooks(const at_fine* h, const FineState& s, const FinePass& p, FineSampleArgs sa, hipStream_t stream) {
+    sa.total = p.head_off[p.n];
+    for (int cb = FINE_COARSE; cb < FINE_CODES; ++cb) {
+        if (int rc = run_forward(h, s, p, cb, stream)) return rc;
+        sa.c = cb;
+        hipLaunchKernelGGL(fine_sample_kernel, dim3((sa.total + SAMPLE_WAVES - 1) / SAMPLE_WAVES), dim3(64 * SAMPLE_WAVES), 0, stream, p, sa);
+        AT_CHECK_HIP(hipGetLastError());
+    }
     return 0;
 }
 
+// what a call fixes of the sampler's arguments; run_codebooks adds the pass's head rows and the code book
+FineSampleArgs sample_args(const FineState& s, int W, int greedy, float temperature, const float* uniforms, float* logits_out, int32_t* ids_out) {
+    FineSampleArgs sa{};
+    sa.logits = s.logits; sa.W = W; sa.greedy = greedy; sa.temperature = greedy ? 1.0f : temperature;
+    sa.uniforms = uniforms; sa.work = s.work; sa.logits_out = logits_out; sa.ids_out = ids_out;
+    return sa;
+}
+
+int upload(at_fine* h, const std::string& name, std::vector<int64_t> shape, const float** dst) { return upload_staged(h, "at_fine_finalize", name, shape, dst); }
+
 void release(at_fine* h) {
-    for (void* p : h->allocs) (void)hipFree(p);
-    h->allocs.clear();
+    free_allocs(h);
     h->layers.clear();
     for (auto& t : h->wtes) t = nullptr;
     for (auto& t : h->heads) t = nullptr;
@@ -322,17 +324,18 @@ struct FineRowMap {
 };
 struct FineCall {
     const int32_t* coarse;
-    const int32_t* hist;   // the history table; null where no row has a history
-    int hstride;
     int32_t* out;
     float temperature;
     int greedy;
     const float* uniforms;
     float* logits_out;
     int32_t* window_ids;
-    int32_t *trace, *n_passes, *placement;   // nullable HOST arrays
-    int trace_cap;
     int32_t* status;
+    int32_t* trace;        // the queue alone: nullable HOST arrays
+    int trace_cap;
+    int32_t *n_passes, *placement;
+    const int32_t* hist;   // the history table; null where no row has a history
+    int hstride;
 };
 
 int launch_rows(bool init, const FineRows& rows, int span, int W, const FineState& s, const FineCall& c, bool first, hipStream_t stream) {
@@ -347,9 +350,7 @@ int launch_rows(bool init, const FineRows& rows, int span, int W, const FineStat
 // lens and map are indexed by row; everything has been checked. Slot j's work array is cells [j Lmax, (j + 1) Lmax) of the state.
 int run_passes(const at_fine* h, const FineState& s, const int32_t* lens, int n_rows, int slots, const FineRowMap* map, const FineCall& c, hipStream_t stream) {
     const int W = h->block;
-    FineSampleArgs sa{};
-    sa.logits = s.logits; sa.W = W; sa.greedy = c.greedy; sa.temperature = c.greedy ? 1.0f : c.temperature;
-    sa.uniforms = c.uniforms; sa.work = s.work; sa.logits_out = c.logits_out; sa.ids_out = c.window_ids;
+    const FineSampleArgs sa = sample_args(s, W, c.greedy, c.temperature, c.uniforms, c.logits_out, c.window_ids);
     std::vector<int32_t> hcells((size_t)n_rows);
     for (int b = 0; b < n_rows; ++b) hcells[b] = map[b].h;
     FineQueueSchedule schedule(lens, n_rows, W, slots, hcells.data());
@@ -388,13 +389,7 @@ int run_passes(const at_fine* h, const FineState& s, const int32_t* lens, int n_
         }
         p.n = q.n;
         if (int rc = launch_rows(true, in, span_in, W, s, c, at == 0, stream)) return rc;
-        sa.total = p.head_off[p.n];
-        for (int cb = FINE_COARSE; cb < FINE_CODES; ++cb) {
-            if (int rc = run_forward(h, s, p, cb, stream)) return rc;
-            sa.c = cb;
-            hipLaunchKernelGGL(fine_sample_kernel, dim3((sa.total + SAMPLE_WAVES - 1) / SAMPLE_WAVES), dim3(64 * SAMPLE_WAVES), 0, stream, p, sa);
-            AT_CHECK_HIP(hipGetLastError());
-        }
+        if (int rc = run_codebooks(h, s, p, sa, stream)) return rc;
         if (int rc = launch_rows(false, outr, span_out, W, s, c, false, stream)) return rc;
     }
     if (c.n_passes) *c.n_passes = schedule.passes();
@@ -407,45 +402,30 @@ int run_passes(const at_fine* h, const FineState& s, const int32_t* lens, int n_
 extern "C" {
 
 at_fine_t* at_fine_create(int device_id) {
-    int n = 0;
-    if (!host_only_test() && (hipGetDeviceCount(&n) != hipSuccess || device_id < 0 || device_id >= n)) {
-        set_error("at_fine_create: no such HIP device " + std::to_string(device_id));
-        return nullptr;
-    }
+    if (!device_exists("at_fine_create", device_id)) return nullptr;
     at_fine* h = new at_fine();
     h->device = device_id;
     return h;
 }
 
 int at_fine_set_tensor(at_fine_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-    AT_REQUIRE(h && name && host_data && shape && ndim >= 1 && ndim <= 4, "bad arguments");
-    AT_REQUIRE(!h->finalized, "model already finalized");
-    FineHostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) {
-        AT_REQUIRE(shape[i] >= 1 && shape[i] <= (int64_t)1 << 32, "bad dimension");
-        t.shape.push_back(shape[i]);
-        n *= (size_t)shape[i];
-    }
-    t.data.assign(host_data, host_data + n);
-    h->staged[name] = std::move(t);
-    return 0;
+    return stage_model_tensor(h, name, host_data, shape, ndim);
 }
 
 int at_fine_finalize(at_fine_t* h) {
     AT_REQUIRE(h != nullptr, "null handle");
     AT_REQUIRE(!h->finalized, "model already finalized");
-    const FineHostTensor* wpe = staged(h, "transformer.wpe.weight");
+    const HostTensor* wpe = staged_tensor(h, "transformer.wpe.weight");
     AT_REQUIRE(wpe && wpe->shape.size() == 2, "transformer.wpe.weight [block][n_embd] is needed");
     const int64_t W = wpe->shape[0], E = wpe->shape[1];
     AT_REQUIRE(E == 768 || E == 1024, "n_embd must be 768 or 1024 (heads of 64): what the kernels implement");
     AT_REQUIRE(W >= 128 && W % 128 == 0 && W <= FINE_MAX_BLOCK, "the block size must be a multiple of 128, from 128 to 1024");
     int n_layer = 0;
-    while (staged(h, "transformer.h." + std::to_string(n_layer) + ".ln_1.weight")) ++n_layer;
+    while (staged_tensor(h, "transformer.h." + std::to_string(n_layer) + ".ln_1.weight")) ++n_layer;
     AT_REQUIRE(n_layer >= 1 && n_layer <= FINE_MAX_LAYERS, "1 to 48 layers (transformer.h.<i>.ln_1.weight, ...)");
     int biases = 0;
     for (int l = 0; l < n_layer; ++l)
-        for (const char* lin : kLinears) biases += staged(h, "transformer.h." + std::to_string(l) + lin + ".bias") ? 1 : 0;
+        for (const char* lin : kLinears) biases += staged_tensor(h, "transformer.h." + std::to_string(l) + lin + ".bias") ? 1 : 0;
     AT_REQUIRE(biases == 0 || biases == 4 * n_layer, "the linears carry a bias in every block or in none");
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
@@ -564,93 +544,58 @@ int place_history(const char* who, const FineHistory& hi, int n_rows, int W, Fin
     return 0;
 }
 
-int generate_lockstep(const char* who, at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
-                      const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev,
-                      size_t state_bytes, int max_T, const FineHistory& hi, at_stream_t stream_, int32_t* status_dev) {
+// The one generator behind the four entry points. `c` holds the caller's arrays; the history table is added here. The lockstep form (queue = false) is the
+// queue with a slot per row (slots = n_rows = B) over rows t_stride apart with n_max draw cells each; the queue's rows are packed and may be traced.
+int generate(const char* who, bool queue, at_fine_t* h, FineCall c, const FineHistory& hi, const int32_t* lens, int n_rows, int slots, int t_stride, int n_max,
+             void* state_dev, size_t state_bytes, int max_T, at_stream_t stream_) {
     AT_REQUIRE(h && h->finalized, "the model is not finalized");
-    AT_REQUIRE(B >= 1 && B <= FINE_MAX_B, "B must be 1 to 64");
-    AT_REQUIRE(coarse_dev && lens && out_dev, "null pointer");
-    AT_REQUIRE(greedy == 0 || greedy == 1, "greedy must be 0 or 1");
-    AT_REQUIRE(greedy || uniforms_dev, "null pointer: sampling needs the uniforms");
-    AT_REQUIRE(greedy || (std::isfinite(temperature) && temperature > 0.0f), "temperature must be a positive finite number");
+    if (queue) {
+        AT_REQUIRE(n_rows >= 1 && n_rows <= FINE_MAX_QUEUE, "n_rows must be 1 to 4096");
+        AT_REQUIRE(slots >= 1 && slots <= FINE_MAX_B, "slots must be 1 to 64");
+    } else {
+        AT_REQUIRE(n_rows >= 1 && n_rows <= FINE_MAX_B, "B must be 1 to 64");
+    }
+    AT_REQUIRE(c.coarse && lens && c.out, "null pointer");
+    AT_REQUIRE(c.greedy == 0 || c.greedy == 1, "greedy must be 0 or 1");
+    AT_REQUIRE(c.greedy || c.uniforms, "null pointer: sampling needs the uniforms");
+    AT_REQUIRE(c.greedy || (std::isfinite(c.temperature) && c.temperature > 0.0f), "temperature must be a positive finite number");
     AT_REQUIRE(state_dev != nullptr, "null state");
     AT_REQUIRE(max_T >= 1 && max_T <= FINE_MAX_T, "max_T must be 1 to 262144");
-    AT_REQUIRE(t_stride >= 1 && t_stride <= FINE_MAX_T, "t_stride must be 1 to 262144");
+    if (queue) AT_REQUIRE(c.trace_cap >= 0 && (c.trace != nullptr || c.trace_cap == 0), "trace_cap must be 0 without a trace, and never negative");
+    else AT_REQUIRE(t_stride >= 1 && t_stride <= FINE_MAX_T, "t_stride must be 1 to 262144");
     const int W = h->block;
-    FineRowMap map[FINE_MAX_B];
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < 1 || lens[b] > t_stride || lens[b] > max_T) {
-            set_error(std::string(who) + ": the length of row " + std::to_string(b) + " must be 1 to min(t_stride, max_T)");
+    for (int b = 0; b < n_rows; ++b)
+        if (lens[b] < 1 || lens[b] > max_T || (!queue && lens[b] > t_stride)) {
+            set_error(std::string(who) + ": the length of row " + std::to_string(b) + " must be 1 to " + (queue ? "max_T" : "min(t_stride, max_T)"));
             return -1;
         }
-    }
-    if (int rc = place_history(who, hi, B, W, map)) return rc;
+    std::vector<FineRowMap> map((size_t)n_rows);
+    if (int rc = place_history(who, hi, n_rows, W, map.data())) return rc;
+    long long off = 0, woff = 0;   // the queue: frames and windows of the rows before
     int n_most = 0;
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < n_rows; ++b) {
         const int n = fine_windows(lens[b], W, map[b].h);
+        map[b].src = queue ? 2 * off : (long long)b * 2 * t_stride;
+        map[b].dst = queue ? FINE_CODES * off : (long long)b * FINE_CODES * t_stride;
+        map[b].stride = queue ? lens[b] : t_stride;
+        map[b].draw0 = queue ? (int)woff : (int)((long long)b * n_max);
+        off += lens[b];
+        woff += n;
         n_most = n > n_most ? n : n_most;
     }
-    AT_REQUIRE(n_max >= n_most, "n_max must hold the windows of the longest row: at_fine_num_windows(h, T)");
-    AT_REQUIRE((long long)B * n_max <= INT32_MAX, "B * n_max must fit 31 bits");
-    for (int b = 0; b < B; ++b) {
-        map[b].src = (long long)b * 2 * t_stride;
-        map[b].dst = (long long)b * FINE_CODES * t_stride;
-        map[b].stride = t_stride;
-        map[b].draw0 = b * n_max;
+    if (queue) {
+        AT_REQUIRE(woff <= INT32_MAX, "the rows' windows must number fewer than 2^31");
+    } else {
+        AT_REQUIRE(n_max >= n_most, "n_max must hold the windows of the longest row: at_fine_num_windows(h, T)");
+        AT_REQUIRE((long long)n_rows * n_max <= INT32_MAX, "B * n_max must fit 31 bits");
     }
-    const FineState s = carve_state(state_dev, B, max_T, hi.max_hist, W, h->embd);
-    AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_state_bytes(h, B, max_T)");
-    // ---- nothing above touched the device
-    DeviceGuard guard(h->device);
-    AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    FineCall c{};
-    c.coarse = coarse_dev; c.hist = hi.dev; c.hstride = hi.stride; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
-    c.logits_out = logits_out_dev; c.window_ids = window_ids_dev; c.status = status_dev;
-    return run_passes(h, s, lens, B, B, map, c, (hipStream_t)stream_);
-}
-
-int generate_queue(const char* who, at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy,
-                   const float* uniforms_dev, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T,
-                   int slots, const FineHistory& hi, int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_,
-                   int32_t* status_dev) {
-    AT_REQUIRE(h && h->finalized, "the model is not finalized");
-    AT_REQUIRE(n_rows >= 1 && n_rows <= FINE_MAX_QUEUE, "n_rows must be 1 to 4096");
-    AT_REQUIRE(slots >= 1 && slots <= FINE_MAX_B, "slots must be 1 to 64");
-    AT_REQUIRE(coarse_dev && lens && out_dev, "null pointer");
-    AT_REQUIRE(greedy == 0 || greedy == 1, "greedy must be 0 or 1");
-    AT_REQUIRE(greedy || uniforms_dev, "null pointer: sampling needs the uniforms");
-    AT_REQUIRE(greedy || (std::isfinite(temperature) && temperature > 0.0f), "temperature must be a positive finite number");
-    AT_REQUIRE(state_dev != nullptr, "null state");
-    AT_REQUIRE(max_T >= 1 && max_T <= FINE_MAX_T, "max_T must be 1 to 262144");
-    AT_REQUIRE(trace_cap >= 0 && (trace != nullptr || trace_cap == 0), "trace_cap must be 0 without a trace, and never negative");
-    const int W = h->block;
-    std::vector<FineRowMap> map((size_t)n_rows);
-    for (int b = 0; b < n_rows; ++b) {
-        if (lens[b] < 1 || lens[b] > max_T) {
-            set_error(std::string(who) + ": the length of row " + std::to_string(b) + " must be 1 to max_T");
-            return -1;
-        }
-    }
-    if (int rc = place_history(who, hi, n_rows, W, map.data())) return rc;
-    long long off = 0, woff = 0;   // frames and windows of the rows before
-    for (int b = 0; b < n_rows; ++b) {
-        map[b].src = 2 * off;
-        map[b].dst = FINE_CODES * off;
-        map[b].stride = lens[b];
-        map[b].draw0 = (int)woff;
-        off += lens[b];
-        woff += fine_windows(lens[b], W, map[b].h);
-    }
-    AT_REQUIRE(woff <= INT32_MAX, "the rows' windows must number fewer than 2^31");
     const FineState s = carve_state(state_dev, slots, max_T, hi.max_hist, W, h->embd);
-    AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_queue_state_bytes(h, slots, max_T)");
+    AT_REQUIRE(state_bytes >= s.bytes, queue ? "state too small: at_fine_queue_state_bytes(h, slots, max_T)" : "state too small: at_fine_state_bytes(h, B, max_T)");
     // ---- nothing above touched the device
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    FineCall c{};
-    c.coarse = coarse_dev; c.hist = hi.dev; c.hstride = hi.stride; c.out = out_dev; c.temperature = temperature; c.greedy = greedy; c.uniforms = uniforms_dev;
-    c.logits_out = logits_out_dev; c.window_ids = window_ids_dev; c.status = status_dev;
-    c.trace = trace; c.trace_cap = trace_cap; c.n_passes = n_passes; c.placement = placement;
+    c.hist = hi.dev;
+    c.hstride = hi.stride;
     return run_passes(h, s, lens, n_rows, slots, map.data(), c, (hipStream_t)stream_);
 }
 
@@ -662,24 +607,24 @@ extern "C" {
 int at_fine_generate(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, float temperature, int greedy,
                      const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
                      int max_T, at_stream_t stream_, int32_t* status_dev) {
-    return generate_lockstep("at_fine_generate", h, coarse_dev, t_stride, lens, B, temperature, greedy, uniforms_dev, n_max, out_dev, logits_out_dev,
-                             window_ids_dev, state_dev, state_bytes, max_T, FineHistory{}, stream_, status_dev);
+    return generate("at_fine_generate", false, h, FineCall{coarse_dev, out_dev, temperature, greedy, uniforms_dev, logits_out_dev, window_ids_dev, status_dev},
+                    FineHistory{}, lens, B, B, t_stride, n_max, state_dev, state_bytes, max_T, stream_);
 }
 
 int at_fine_generate_hist(at_fine_t* h, const int32_t* coarse_dev, int t_stride, const int32_t* lens, int B, const int32_t* hist_dev, int h_stride,
                           const int32_t* hist_lens, int n_hist, const int32_t* hist_of_row, int max_hist, float temperature, int greedy,
                           const float* uniforms_dev, int n_max, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev,
                           size_t state_bytes, int max_T, at_stream_t stream_, int32_t* status_dev) {
-    return generate_lockstep("at_fine_generate_hist", h, coarse_dev, t_stride, lens, B, temperature, greedy, uniforms_dev, n_max, out_dev, logits_out_dev,
-                             window_ids_dev, state_dev, state_bytes, max_T, FineHistory{hist_dev, h_stride, hist_lens, n_hist, hist_of_row, max_hist}, stream_,
-                             status_dev);
+    return generate("at_fine_generate_hist", false, h, FineCall{coarse_dev, out_dev, temperature, greedy, uniforms_dev, logits_out_dev, window_ids_dev, status_dev},
+                    FineHistory{hist_dev, h_stride, hist_lens, n_hist, hist_of_row, max_hist}, lens, B, B, t_stride, n_max, state_dev, state_bytes, max_T, stream_);
 }
 
 int at_fine_generate_queue(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, float temperature, int greedy, const float* uniforms_dev,
                            int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes, int max_T, int slots,
                            int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
-    return generate_queue("at_fine_generate_queue", h, coarse_dev, lens, n_rows, temperature, greedy, uniforms_dev, out_dev, logits_out_dev, window_ids_dev,
-                          state_dev, state_bytes, max_T, slots, FineHistory{}, trace, trace_cap, n_passes, placement, stream_, status_dev);
+    return generate("at_fine_generate_queue", true, h,
+                    FineCall{coarse_dev, out_dev, temperature, greedy, uniforms_dev, logits_out_dev, window_ids_dev, status_dev, trace, trace_cap, n_passes, placement},
+                    FineHistory{}, lens, n_rows, slots, 0, 0, state_dev, state_bytes, max_T, stream_);
 }
 
 int at_fine_generate_queue_hist(at_fine_t* h, const int32_t* coarse_dev, const int32_t* lens, int n_rows, const int32_t* hist_dev, int h_stride,
@@ -687,9 +632,9 @@ int at_fine_generate_queue_hist(at_fine_t* h, const int32_t* coarse_dev, const i
                                 const float* uniforms_dev, int32_t* out_dev, float* logits_out_dev, int32_t* window_ids_dev, void* state_dev, size_t state_bytes,
                                 int max_T, int slots, int32_t* trace, int trace_cap, int32_t* n_passes, int32_t* placement, at_stream_t stream_,
                                 int32_t* status_dev) {
-    return generate_queue("at_fine_generate_queue_hist", h, coarse_dev, lens, n_rows, temperature, greedy, uniforms_dev, out_dev, logits_out_dev,
-                          window_ids_dev, state_dev, state_bytes, max_T, slots, FineHistory{hist_dev, h_stride, hist_lens, n_hist, hist_of_row, max_hist},
-                          trace, trace_cap, n_passes, placement, stream_, status_dev);
+    return generate("at_fine_generate_queue_hist", true, h,
+                    FineCall{coarse_dev, out_dev, temperature, greedy, uniforms_dev, logits_out_dev, window_ids_dev, status_dev, trace, trace_cap, n_passes, placement},
+                    FineHistory{hist_dev, h_stride, hist_lens, n_hist, hist_of_row, max_hist}, lens, n_rows, slots, 0, 0, state_dev, state_bytes, max_T, stream_);
 }
 
 }  // extern "C"
@@ -826,9 +771,7 @@ int at_fine_stream_push(at_fine_t* h, void* state_dev, size_t state_bytes, int64
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
     hipStream_t stream = (hipStream_t)stream_;
-    FineSampleArgs sa{};
-    sa.logits = s.logits; sa.W = W; sa.greedy = greedy; sa.temperature = greedy ? 1.0f : temperature;
-    sa.uniforms = uniforms_dev; sa.work = s.work;
+    const FineSampleArgs sa = sample_args(s, W, greedy, temperature, uniforms_dev, nullptr, nullptr);
     auto run_window = [&](int cell, int j, int rel) -> int {
         FinePass p{};
         p.n = 1;
@@ -836,14 +779,7 @@ int at_fine_stream_push(at_fine_t* h, void* state_dev, size_t state_bytes, int64
         p.draw[0] = j - u_win0;
         p.rel[0] = rel;
         p.head_off[1] = W - rel;
-        sa.total = W - rel;
-        for (int cb = FINE_COARSE; cb < FINE_CODES; ++cb) {
-            if (int rc = run_forward(h, s, p, cb, stream)) return rc;
-            sa.c = cb;
-            hipLaunchKernelGGL(fine_sample_kernel, dim3((sa.total + SAMPLE_WAVES - 1) / SAMPLE_WAVES), dim3(64 * SAMPLE_WAVES), 0, stream, p, sa);
-            AT_CHECK_HIP(hipGetLastError());
-        }
-        return 0;
+        return run_codebooks(h, s, p, sa, stream);
     };
     FineStreamSchedule schedule(pos[0], n_frames, final != 0, W);
     FineStreamRound rd;

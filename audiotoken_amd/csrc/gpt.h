@@ -1,12 +1,9 @@
 // The handle of the semantic-to-acoustic GPT (gpt.hip, gpt_model.hip) and the pure host arithmetic of its schedules, declared apart from
 // the code so that the stand-alone argument checks (tools/gpt_*args.hip) can build a finalized handle with no device behind it: every entry point
-// validates against the handle's dimensions alone before it touches one.
+// validates against the handle's dimensions alone before it touches one. The handle's plumbing (staging, upload, allocations) and the state carver are
+// model_handle.h's, shared with the fine stage.
 #pragma once
-#include <map>
-#include <string>
-#include <vector>
-
-#include "at_common.h"
+#include "model_handle.h"
 
 namespace at {
 
@@ -212,23 +209,14 @@ class GptStreamSchedule {
     int S_, H_;
 };
 
-struct GptHostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
-
 struct GptLayer {
     const float *ln1 = nullptr, *qkv = nullptr, *proj = nullptr, *ln2 = nullptr, *fc = nullptr, *fc_proj = nullptr;
 };
 
 }  // namespace at
 
-struct at_gpt {
-    int device = 0;
-    bool finalized = false;
-    std::map<std::string, at::GptHostTensor> staged;
+struct at_gpt : at::ModelHandle {   // device, finalized, staged, allocs
     int n_layer = 0, vocab = 0, block = 0;
-    std::vector<void*> allocs;        // every device allocation of finalize()
     const float *wte = nullptr, *wpe = nullptr, *ln_f = nullptr;
     std::vector<at::GptLayer> layers;
     int32_t* flags_host = nullptr;    // pinned: the rows' finish flags as the host last saw them (GPT_MAX_B words)

@@ -5,7 +5,10 @@
 //   at_gpt_generate        the caller's prompts begin in tick 0, then every row steps; a look every 16 steps
 //   at_gpt_generate_long   lockstep passes: window k of every row that has one begins, then those rows step
 //   at_gpt_generate_queue  GptQueueSchedule's ticks: any mix of rows that step and windows that begin
+//   at_gpt_stream_push     one source whose ids arrive in pushes: GptStreamSchedule's rounds of windows
 // Nothing waits for the host between those looks: the rows' lengths, last tokens, step counters and finish flags live on the device.
+// The host side: the handle's plumbing and the state carver are model_handle.h's; the windowed entry points fill one GenRequest, which generate_long and
+// generate_queue take and check_request checks; the lockstep generators' step loop is run_steps (at_gpt_generate, a pass of the long form, a stream window).
 #include <cmath>
 #include <cstring>
 
@@ -18,34 +21,30 @@ namespace {
 
 constexpr int E = GPT_EMBD, HD = GPT_HEAD_DIM, NH = GPT_HEADS, FF = GPT_FF;
 
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
 GptState carve_state(void* base, int rows, int cap, int tokens, int vocab, int n_layer) {
     GptState s{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += round256(bytes); return r; };
+    StateCarver c(base);
     const size_t R = (size_t)tokens;
-    s.len = (int*)take(GPT_MAX_B * 4);
-    s.done = (int*)take(GPT_MAX_B * 4);
-    s.cur = (int*)take(GPT_MAX_B * 4);
-    s.step_ctr = (int*)take(GPT_MAX_B * 4);
-    s.last_row = (int*)take(GPT_MAX_B * 4);
-    s.samp_slot = (int*)take(GPT_MAX_B * 4);
-    s.rows = (SampleRow*)take(rows * sizeof(SampleRow));
-    s.tok_row = (int*)take(R * 4);
-    s.tok_pos = (int*)take(R * 4);
-    s.x = (float*)take(R * E * 4);
-    s.xn = (float*)take(R * E * 4);
-    s.q = (float*)take(R * 3 * E * 4);   // up to 64 tokens: q [R][768]; more, on the GEMM: q | k | v [R][2304]
-    s.h = (float*)take(R * FF * 4);
+    s.len = c.take<int>(GPT_MAX_B);
+    s.done = c.take<int>(GPT_MAX_B);
+    s.cur = c.take<int>(GPT_MAX_B);
+    s.step_ctr = c.take<int>(GPT_MAX_B);
+    s.last_row = c.take<int>(GPT_MAX_B);
+    s.samp_slot = c.take<int>(GPT_MAX_B);
+    s.rows = c.take<SampleRow>(rows);
+    s.tok_row = c.take<int>(R);
+    s.tok_pos = c.take<int>(R);
+    s.x = c.take<float>(R * E);
+    s.xn = c.take<float>(R * E);
+    s.q = c.take<float>(R * 3 * E);      // up to 64 tokens: q [R][768]; more, on the GEMM: q | k | v [R][2304]
+    s.h = c.take<float>(R * FF);
     s.tok_id = (int*)s.h;                // [R]: written by the begin kernel, read by the embedding, dead before the first layer's MLP writes h
-    s.logits = (float*)take((size_t)rows * vocab * 4);
+    s.logits = c.take<float>((size_t)rows * vocab);
     s.layer_stride = (size_t)rows * cap * NH * HD;
-    s.kc = (float*)take(s.layer_stride * n_layer * 4);
-    s.vc = (float*)take(s.layer_stride * n_layer * 4);
+    s.kc = c.take<float>(s.layer_stride * n_layer);
+    s.vc = c.take<float>(s.layer_stride * n_layer);
     s.cap = cap;
-    s.bytes = off;
+    s.bytes = c.off;
     return s;
 }
 
@@ -177,54 +176,108 @@ int all_done(at_gpt* h, const GptState& s, int n, hipStream_t stream, bool* all)
     return 0;
 }
 
-SampleArgs generation_args(const at_gpt* h, const GptState& s, float temperature, int top_k, const float* uniforms, int u_stride, int32_t* out_ids, int out_stride,
-                           int32_t* out_len, int32_t* finish, float* logits_out, int max_new) {
+// The step loop of the lockstep generators: the tick in which `begin`'s windows begin in cache rows 0 .. n_rows - 1, then step ticks of those rows, `steps`
+// ticks in all. After every GPT_CHECK_EVERY ticks, from tick poll_from on and not after the last, the host looks at the rows' flags and ends the loop when
+// none is running: its only look at the device. (poll_from = steps: never, which is right for windows that cannot end early.)
+int run_steps(at_gpt* h, const GptState& s, const TickPlan& begin, int n_rows, int steps, int poll_from, const Rules& q, const SampleArgs& sa, hipStream_t stream) {
+    const TickPlan step_plan = lockstep_steps(n_rows);
+    for (int step = 0; step < steps; ++step) {
+        if (int rc = run_tick(h, s, step == 0 ? begin : step_plan, q, sa, stream)) return rc;
+        if ((step + 1) % GPT_CHECK_EVERY == 0 && step + 1 < steps && step + 1 >= poll_from) {
+            bool all;
+            if (int rc = all_done(h, s, n_rows, stream, &all)) return rc;
+            if (all) break;
+        }
+    }
+    return 0;
+}
+
+// ---- a call of the windowed generators, as its entry point hands it over ------------------------------------------------------------------------
+struct Sources { const int32_t* dev; int stride; const int32_t* len; int n; };   // device ids [n][stride], HOST lengths
+struct Geometry { int S, H, r; };
+struct TokenSpace { int semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token; };
+struct Sampling { int max_new; float temperature; int top_k; const float* uniforms; int u_stride; };
+struct Outputs { int32_t* ids; int stride; int32_t *len, *finish; float* logits; };
+struct StateBuf { void* dev; size_t bytes; int max_len; };
+struct QueueExtras { int slots, tick_tokens; int32_t* trace; int trace_cap; int32_t *n_ticks, *placement; };
+// A call's voice prompts as the caller hands them over (DESIGN.md 22): the table on the device, the lengths and each source's entry (-1: none) on the host
+struct VoiceTable {
+    const int32_t* sem; int p_stride; const int32_t* codes; int f_stride; const int32_t* len; int n; const int32_t* of_src;
+    bool on;   // a prompted entry point was called
+};
+struct GenRequest {
+    const char* who;   // the entry point the caller called
+    at_gpt* h;
+    Sources src;
+    Geometry geo;
+    TokenSpace tok;
+    Sampling samp;
+    Outputs out;
+    StateBuf state;
+    at_stream_t stream;
+    int32_t* status;
+    VoiceTable voice;
+    QueueExtras queue;
+};
+
+SampleArgs generation_args(const at_gpt* h, const GptState& s, const Sampling& g, const Outputs& o) {
     SampleArgs sa{};
-    sa.logits = s.logits; sa.V = h->vocab; sa.top_k = top_k; sa.temperature = temperature; sa.uniforms = uniforms; sa.u_stride = u_stride;
+    sa.logits = s.logits; sa.V = h->vocab; sa.top_k = g.top_k; sa.temperature = g.temperature; sa.uniforms = g.uniforms; sa.u_stride = g.u_stride;
     sa.len = s.len; sa.done = s.done; sa.cur = s.cur; sa.step_ctr = s.step_ctr; sa.rows = s.rows; sa.samp_slot = s.samp_slot;
-    sa.out_ids = out_ids; sa.out_len = out_len; sa.finish = finish; sa.logits_out = logits_out; sa.max_new = max_new; sa.block = h->block; sa.out_stride = out_stride;
+    sa.out_ids = o.ids; sa.out_len = o.len; sa.finish = o.finish; sa.logits_out = o.logits; sa.max_new = g.max_new; sa.block = h->block; sa.out_stride = o.stride;
     sa.top_p = h->top_p; sa.lmin = h->lmin;
     return sa;
 }
 
-// What at_gpt_generate_long and at_gpt_generate_queue share: the checks of the geometry, the token space and the sampling arguments, and the rules they make
-int check_long_rules(const at_gpt* h, int S, int H, int r, const int32_t* src_dev, int src_stride, int semantic_offset, int semantic_vocab, int infer_token,
-                     int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k, int32_t* status_dev, Rules* out) {
-    const int V = h->vocab, block = h->block;
-    AT_REQUIRE(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0, "the window S and the hop H must be even, at least 2");
-    AT_REQUIRE(H <= S, "the hop H must not exceed the window S");
-    AT_REQUIRE(r >= 1 && r <= GPT_MAX_BLOCK, "r (acoustic ids per source id) must be 1 to 1024");
-    AT_REQUIRE((int64_t)S + 1 + (int64_t)r * S <= block, "a window does not fit: S + 1 + r S must not exceed the model's block size");
-    AT_REQUIRE(src_stride >= 1, "src_stride must be at least 1");
-    AT_REQUIRE(max_new >= 1 && max_new <= GPT_MAX_BLOCK, "max_new must be 1 to 1024");
-    if (int rc = check_sampling(temperature, top_k)) return rc;
-    AT_REQUIRE(semantic_offset >= 0 && semantic_vocab >= 1 && (int64_t)semantic_offset + semantic_vocab <= V, "the semantic ids must lie inside the vocabulary");
-    AT_REQUIRE(infer_token >= 0 && infer_token < V, "infer_token is not in the vocabulary");
-    AT_REQUIRE(acoustic_offset >= 0 && codebook_size >= 1 && (int64_t)acoustic_offset + 2 * (int64_t)codebook_size <= V,
+// the window geometry against the model's block size: what every windowed entry point and the stream's size query check first
+int check_geometry(const at_gpt* h, const Geometry& g) {
+    AT_REQUIRE(g.S >= 2 && g.S % 2 == 0 && g.H >= 2 && g.H % 2 == 0, "the window S and the hop H must be even, at least 2");
+    AT_REQUIRE(g.H <= g.S, "the hop H must not exceed the window S");
+    AT_REQUIRE(g.r >= 1 && g.r <= GPT_MAX_BLOCK, "r (acoustic ids per source id) must be 1 to 1024");
+    AT_REQUIRE((int64_t)g.S + 1 + (int64_t)g.r * g.S <= h->block, "a window does not fit: S + 1 + r S must not exceed the model's block size");
+    return 0;
+}
+
+// What the windowed generators and the stream share: the checks of the geometry, the token space and the sampling arguments, and the rules they make
+int check_long_rules(const GenRequest& rq, Rules* out) {
+    const int V = rq.h->vocab;
+    const TokenSpace& t = rq.tok;
+    if (int rc = check_geometry(rq.h, rq.geo)) return rc;
+    AT_REQUIRE(rq.src.stride >= 1, "src_stride must be at least 1");
+    AT_REQUIRE(rq.samp.max_new >= 1 && rq.samp.max_new <= GPT_MAX_BLOCK, "max_new must be 1 to 1024");
+    if (int rc = check_sampling(rq.samp.temperature, rq.samp.top_k)) return rc;
+    AT_REQUIRE(t.semantic_offset >= 0 && t.semantic_vocab >= 1 && (int64_t)t.semantic_offset + t.semantic_vocab <= V, "the semantic ids must lie inside the vocabulary");
+    AT_REQUIRE(t.infer_token >= 0 && t.infer_token < V, "infer_token is not in the vocabulary");
+    AT_REQUIRE(t.acoustic_offset >= 0 && t.codebook_size >= 1 && (int64_t)t.acoustic_offset + 2 * (int64_t)t.codebook_size <= V,
                "the two code books must lie inside the vocabulary");
-    AT_REQUIRE(stop_token < V, "stop_token is not in the vocabulary (negative: none)");
+    AT_REQUIRE(t.stop_token < V, "stop_token is not in the vocabulary (negative: none)");
     Rules q{};
-    q.src = src_dev; q.src_stride = src_stride; q.status = status_dev;
-    q.S = S; q.H = H; q.r = r; q.semantic_offset = semantic_offset; q.semantic_vocab = semantic_vocab; q.infer_token = infer_token;
-    q.stop_token = stop_token < 0 ? -1 : stop_token; q.max_new = max_new; q.block = block;
-    q.acoustic_offset = acoustic_offset; q.codebook_size = codebook_size;
-    q.mid[0] = Allow{1, acoustic_offset, acoustic_offset + codebook_size, 0, 0};
-    q.mid[1] = Allow{1, acoustic_offset + codebook_size, acoustic_offset + 2 * codebook_size, 0, 0};
+    q.src = rq.src.dev; q.src_stride = rq.src.stride; q.status = rq.status;
+    q.S = rq.geo.S; q.H = rq.geo.H; q.r = rq.geo.r; q.semantic_offset = t.semantic_offset; q.semantic_vocab = t.semantic_vocab; q.infer_token = t.infer_token;
+    q.stop_token = t.stop_token < 0 ? -1 : t.stop_token; q.max_new = rq.samp.max_new; q.block = rq.h->block;
+    q.acoustic_offset = t.acoustic_offset; q.codebook_size = t.codebook_size;
+    q.mid[0] = Allow{1, t.acoustic_offset, t.acoustic_offset + t.codebook_size, 0, 0};
+    q.mid[1] = Allow{1, t.acoustic_offset + t.codebook_size, t.acoustic_offset + 2 * t.codebook_size, 0, 0};
     q.last[0] = q.mid[0];
     q.last[1] = q.mid[1];
-    if (stop_token >= 0) { q.last[0].lo1 = stop_token; q.last[0].hi1 = stop_token + 1; }
+    if (t.stop_token >= 0) { q.last[0].lo1 = t.stop_token; q.last[0].hi1 = t.stop_token + 1; }
+    q.vp_sem = rq.voice.sem; q.vp_codes = rq.voice.codes; q.vp_stride = rq.voice.p_stride; q.vf_stride = rq.voice.f_stride;
     *out = q;
     return 0;
 }
 
-// A call's voice prompts as the caller hands them over (DESIGN.md 22): the table on the device, the lengths and each source's entry (-1: none) on the host
-struct VoiceTable {
-    const int32_t *sem = nullptr, *codes = nullptr, *len = nullptr, *of_src = nullptr;
-    int p_stride = 0, f_stride = 0, n = 0;
-    bool on = false;   // a prompted entry point was called
-};
-// The checks of a prompted call, and per source its prompt's length (0: none) and entry: pv and entry are left empty when no source has a prompt
-int check_voice(const char* who, const VoiceTable& vt, const int32_t* src_len, int n_src, int S, int H, int r, std::vector<int32_t>* pv, std::vector<int32_t>* entry) {
+// The sources' lengths (`unit`: what the entry point calls a source in its error texts), then the checks of a prompted call, and per source its prompt's
+// length (0: none) and entry: pv and entry are left empty when no source has a prompt
+int check_sources(const GenRequest& rq, const char* unit, std::vector<int32_t>* pv, std::vector<int32_t>* entry) {
+    const char* who = rq.who;
+    const VoiceTable& vt = rq.voice;
+    const int32_t* src_len = rq.src.len;
+    const int n_src = rq.src.n, S = rq.geo.S, H = rq.geo.H, r = rq.geo.r;
+    for (int i = 0; i < n_src; ++i)
+        if (src_len[i] < 1 || src_len[i] > rq.src.stride || src_len[i] > GPT_MAX_SOURCE) {
+            set_error(std::string(who) + ": src_len of " + unit + " " + std::to_string(i) + " must be 1 to min(src_stride, 65536)");
+            return -1;
+        }
     if (!vt.on) return 0;
     AT_REQUIRE(vt.n >= 0 && vt.n <= GPT_MAX_VOICE_PROMPTS, "n_prompts must be 0 to 4096");
     AT_REQUIRE(vt.of_src != nullptr, "null prompt_of_src");
@@ -262,26 +315,10 @@ int check_voice(const char* who, const VoiceTable& vt, const int32_t* src_len, i
     return 0;
 }
 
-const GptHostTensor* staged(const at_gpt* h, const std::string& name) {
-    auto it = h->staged.find(name);
-    return it == h->staged.end() ? nullptr : &it->second;
-}
-
-int upload(at_gpt* h, const std::string& name, std::vector<int64_t> shape, const float** dst) {
-    const GptHostTensor* t = staged(h, name);
-    if (!t) { set_error("at_gpt_finalize: missing tensor " + name); return -1; }
-    if (t->shape != shape) { set_error("at_gpt_finalize: tensor " + name + " has an unexpected shape"); return -1; }
-    void* d = nullptr;
-    AT_CHECK_HIP(hipMalloc(&d, t->data.size() * sizeof(float)));
-    h->allocs.push_back(d);
-    AT_CHECK_HIP(hipMemcpy(d, t->data.data(), t->data.size() * sizeof(float), hipMemcpyHostToDevice));
-    *dst = static_cast<const float*>(d);
-    return 0;
-}
+int upload(at_gpt* h, const std::string& name, std::vector<int64_t> shape, const float** dst) { return upload_staged(h, "at_gpt_finalize", name, shape, dst); }
 
 void release(at_gpt* h) {
-    for (void* p : h->allocs) (void)hipFree(p);
-    h->allocs.clear();
+    free_allocs(h);
     if (h->flags_host) { (void)hipHostFree(h->flags_host); h->flags_host = nullptr; }
     h->layers.clear();
     h->wte = h->wpe = h->ln_f = nullptr;
@@ -292,29 +329,14 @@ void release(at_gpt* h) {
 extern "C" {
 
 at_gpt_t* at_gpt_create(int device_id) {
-    int n = 0;
-    if (!host_only_test() && (hipGetDeviceCount(&n) != hipSuccess || device_id < 0 || device_id >= n)) {
-        set_error("at_gpt_create: no such HIP device " + std::to_string(device_id));
-        return nullptr;
-    }
+    if (!device_exists("at_gpt_create", device_id)) return nullptr;
     at_gpt* h = new at_gpt();
     h->device = device_id;
     return h;
 }
 
 int at_gpt_set_tensor(at_gpt_t* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-    AT_REQUIRE(h && name && host_data && shape && ndim >= 1 && ndim <= 4, "bad arguments");
-    AT_REQUIRE(!h->finalized, "model already finalized");
-    GptHostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) {
-        AT_REQUIRE(shape[i] >= 1 && shape[i] <= (int64_t)1 << 32, "bad dimension");
-        t.shape.push_back(shape[i]);
-        n *= (size_t)shape[i];
-    }
-    t.data.assign(host_data, host_data + n);
-    h->staged[name] = std::move(t);
-    return 0;
+    return stage_model_tensor(h, name, host_data, shape, ndim);
 }
 
 int at_gpt_finalize(at_gpt_t* h) {
@@ -325,15 +347,15 @@ int at_gpt_finalize(at_gpt_t* h) {
             set_error("at_gpt_finalize: " + kv.first + ": the kernels implement the bias-free model only");
             return -1;
         }
-    const GptHostTensor* wte = staged(h, "transformer.wte.weight");
-    const GptHostTensor* wpe = staged(h, "transformer.wpe.weight");
+    const HostTensor* wte = staged_tensor(h, "transformer.wte.weight");
+    const HostTensor* wpe = staged_tensor(h, "transformer.wpe.weight");
     AT_REQUIRE(wte && wpe, "transformer.wte.weight and transformer.wpe.weight are needed");
     AT_REQUIRE(wte->shape.size() == 2 && wpe->shape.size() == 2 && wte->shape[1] == E && wpe->shape[1] == E, "n_embd must be 768 (12 heads of 64): what the kernels implement");
     const int64_t V = wte->shape[0], block = wpe->shape[0];
     AT_REQUIRE(V >= 64 && V % 64 == 0 && V <= GPT_MAX_VOCAB, "the vocabulary must be a multiple of 64, at most 65536");
     AT_REQUIRE(block >= 64 && block % 64 == 0 && block <= GPT_MAX_BLOCK, "the block size must be a multiple of 64, at most 1024");
     int n_layer = 0;
-    while (staged(h, "transformer.h." + std::to_string(n_layer) + ".ln_1.weight")) ++n_layer;
+    while (staged_tensor(h, "transformer.h." + std::to_string(n_layer) + ".ln_1.weight")) ++n_layer;
     AT_REQUIRE(n_layer >= 1 && n_layer <= GPT_MAX_LAYERS, "1 to 48 layers (transformer.h.<i>.ln_1.weight, ...)");
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
@@ -386,12 +408,16 @@ int at_gpt_set_truncation(at_gpt_t* h, float top_p, float min_p) {
     return 0;
 }
 
-size_t at_gpt_state_bytes(const at_gpt_t* h, int B, int max_len) {
-    if (!(h && h->finalized)) { set_error("at_gpt_state_bytes: the model is not finalized"); return 0; }
-    if (!(B >= 1 && B <= GPT_MAX_B)) { set_error("at_gpt_state_bytes: B must be 1 to 64"); return 0; }
-    if (!(max_len >= 1 && max_len <= h->block)) { set_error("at_gpt_state_bytes: max_len must be 1 to the model's block size"); return 0; }
+// the size of a lockstep generator's state, behind its two names: `who` is the entry point the caller called
+static size_t lockstep_state_bytes(const char* who, const at_gpt_t* h, int B, int max_len) {
+    const std::string w(who);
+    if (!(h && h->finalized)) { set_error(w + ": the model is not finalized"); return 0; }
+    if (!(B >= 1 && B <= GPT_MAX_B)) { set_error(w + ": B must be 1 to 64"); return 0; }
+    if (!(max_len >= 1 && max_len <= h->block)) { set_error(w + ": max_len must be 1 to the model's block size"); return 0; }
     return carve_state(nullptr, B, max_len, B * max_len, h->vocab, h->n_layer).bytes;
 }
+size_t at_gpt_state_bytes(const at_gpt_t* h, int B, int max_len) { return lockstep_state_bytes("at_gpt_state_bytes", h, B, max_len); }
+size_t at_gpt_long_state_bytes(const at_gpt_t* h, int B, int max_len) { return lockstep_state_bytes("at_gpt_long_state_bytes", h, B, max_len); }
 
 int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, const int32_t* prompt_len, int B, int max_new, float temperature, int top_k,
                     int stop_token, const float* uniforms_dev, const int32_t* allow, int32_t* out_ids_dev, int32_t* out_len_dev, int32_t* finish_dev,
@@ -426,17 +452,8 @@ int at_gpt_generate(at_gpt_t* h, const int32_t* prompts_dev, int prompt_stride, 
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
     hipStream_t stream = (hipStream_t)stream_;
-    const SampleArgs sa = generation_args(h, s, temperature, top_k, uniforms_dev, max_new, out_ids_dev, max_new, out_len_dev, finish_dev, logits_out_dev, max_new);
-    const TickPlan steps = lockstep_steps(B);
-    for (int step = 0; step < max_new; ++step) {
-        if (int rc = run_tick(h, s, step == 0 ? begin : steps, q, sa, stream)) return rc;
-        if ((step + 1) % GPT_CHECK_EVERY == 0 && step + 1 < max_new) {   // the host's only look at the device during the call
-            bool all;
-            if (int rc = all_done(h, s, B, stream, &all)) return rc;
-            if (all) break;
-        }
-    }
-    return 0;
+    const SampleArgs sa = generation_args(h, s, Sampling{max_new, temperature, top_k, uniforms_dev, max_new}, Outputs{out_ids_dev, max_new, out_len_dev, finish_dev, logits_out_dev});
+    return run_steps(h, s, begin, B, max_new, 0, q, sa, stream);
 }
 
 int at_gpt_long_num_windows(int N, int S, int H) {
@@ -455,77 +472,60 @@ int at_gpt_long_num_windows_prompted(int P, int N, int S, int H) {
     return gpt_long_windows(N, S, H, P);
 }
 
-size_t at_gpt_long_state_bytes(const at_gpt_t* h, int B, int max_len) {
-    if (!(h && h->finalized)) { set_error("at_gpt_long_state_bytes: the model is not finalized"); return 0; }
-    if (!(B >= 1 && B <= GPT_MAX_B)) { set_error("at_gpt_long_state_bytes: B must be 1 to 64"); return 0; }
-    if (!(max_len >= 1 && max_len <= h->block)) { set_error("at_gpt_long_state_bytes: max_len must be 1 to the model's block size"); return 0; }
-    return carve_state(nullptr, B, max_len, B * max_len, h->vocab, h->n_layer).bytes;
+// What at_gpt_generate_long and at_gpt_generate_queue check alike once the counts are known to be in range, in this order: the pointers, the rules, the
+// sources with their voice prompts, and the caller's arrays against the sources' extent. `unit`: what the entry point calls a source in its error texts.
+static int check_request(const GenRequest& rq, const char* unit, Rules* q, std::vector<int32_t>* pv, std::vector<int32_t>* entry) {
+    AT_REQUIRE(rq.src.dev && rq.src.len && rq.samp.uniforms && rq.out.ids && rq.out.len && rq.out.finish, "null pointer");
+    AT_REQUIRE(rq.state.dev != nullptr, "null state");
+    AT_REQUIRE(rq.queue.trace_cap >= 0 && (rq.queue.trace != nullptr || rq.queue.trace_cap == 0), "trace_cap must be 0 without a trace and never negative");
+    if (int rc = check_long_rules(rq, q)) return rc;
+    if (int rc = check_sources(rq, unit, pv, entry)) return rc;
+    const auto [need_len, need_stride] = gpt_extent(rq.src.len, rq.src.n, rq.geo.S, rq.geo.H, rq.geo.r, rq.samp.max_new, rq.h->block, pv->empty() ? nullptr : pv->data());
+    AT_REQUIRE(rq.out.stride >= need_stride && rq.samp.u_stride >= need_stride, std::string("out_stride and u_stride must hold the longest ") + unit + "'s stream");
+    AT_REQUIRE(rq.state.max_len >= need_len && rq.state.max_len <= rq.h->block, "max_len must hold the longest window with its new ids and not exceed the block size");
+    return 0;
 }
 
-static int generate_long(const char* who, const VoiceTable& vt, at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, int S, int H, int r,
-                         int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature,
-                         int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
-                         float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream_, int32_t* status_dev) {
+static int generate_long(const GenRequest& rq) {
+    at_gpt* h = rq.h;
+    const int B = rq.src.n, S = rq.geo.S, H = rq.geo.H, r = rq.geo.r, max_new = rq.samp.max_new;
     AT_REQUIRE(h && h->finalized, "the model is not finalized");
     AT_REQUIRE(B >= 1 && B <= GPT_MAX_B, "B must be 1 to 64");
-    AT_REQUIRE(src_dev && src_len && uniforms_dev && out_ids_dev && out_len_dev && finish_dev, "null pointer");
-    AT_REQUIRE(state_dev != nullptr, "null state");
-    const int V = h->vocab, block = h->block;
     Rules q{};
-    if (int rc = check_long_rules(h, S, H, r, src_dev, src_stride, semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token, max_new,
-                                  temperature, top_k, status_dev, &q))
-        return rc;
+    std::vector<int32_t> pv, entry;
+    if (int rc = check_request(rq, "row", &q, &pv, &entry)) return rc;
+    const bool voiced = !pv.empty();
     // ---- the schedule: rows in descending order of their window counts, so that the rows of pass k are the first Bk of them
     int n_win[GPT_MAX_B], order[GPT_MAX_B];
     int n_max = 0;
-    for (int b = 0; b < B; ++b)
-        if (src_len[b] < 1 || src_len[b] > src_stride || src_len[b] > GPT_MAX_SOURCE) {
-            set_error(std::string(who) + ": src_len of row " + std::to_string(b) + " must be 1 to min(src_stride, 65536)");
-            return -1;
-        }
-    std::vector<int32_t> pv, entry;
-    if (int rc = check_voice(who, vt, src_len, B, S, H, r, &pv, &entry)) return rc;
-    const bool voiced = !pv.empty();
-    q.vp_sem = vt.sem; q.vp_codes = vt.codes; q.vp_stride = vt.p_stride; q.vf_stride = vt.f_stride;
     for (int b = 0; b < B; ++b) {
-        const int n = n_win[b] = gpt_long_windows(src_len[b], S, H, voiced ? pv[b] : 0);
+        const int n = n_win[b] = gpt_long_windows(rq.src.len[b], S, H, voiced ? pv[b] : 0);
         n_max = n > n_max ? n : n_max;
         int at = b;
         while (at > 0 && n_win[order[at - 1]] < n) { order[at] = order[at - 1]; --at; }
         order[at] = b;
     }
-    const auto [need_len, need_stride] = gpt_extent(src_len, B, S, H, r, max_new, block, voiced ? pv.data() : nullptr);
-    AT_REQUIRE(out_stride >= need_stride && u_stride >= need_stride, "out_stride and u_stride must hold the longest row's stream");
-    AT_REQUIRE(max_len >= need_len && max_len <= block, "max_len must hold the longest window with its new ids and not exceed the block size");
-    const GptState s = carve_state(state_dev, B, max_len, B * max_len, V, h->n_layer);
-    AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_gpt_long_state_bytes(h, B, max_len)");
+    const GptState s = carve_state(rq.state.dev, B, rq.state.max_len, B * rq.state.max_len, h->vocab, h->n_layer);
+    AT_REQUIRE(rq.state.bytes >= s.bytes, "state too small: at_gpt_long_state_bytes(h, B, max_len)");
     // ---- nothing above touched the device
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    hipStream_t stream = (hipStream_t)stream_;
-    const SampleArgs sa = generation_args(h, s, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev, max_new);
+    hipStream_t stream = (hipStream_t)rq.stream;
+    const SampleArgs sa = generation_args(h, s, rq.samp, rq.out);
     for (int k = 0; k < n_max; ++k) {
         // pass k: window k of every row that has one begins in cache row 0 .. Bk - 1, then those rows step up to the largest budget among them
         TickPlan begin{};
         int Bk = 0, steps = 0, mid_steps = 0;
         while (Bk < B && n_win[order[Bk]] > k) {
             const int b = order[Bk];
-            const GptWindow w = gpt_window(src_len[b], k, S, H, r, max_new, block, voiced ? pv[b] : 0);
+            const GptWindow w = gpt_window(rq.src.len[b], k, S, H, r, max_new, h->block, voiced ? pv[b] : 0);
             begin.start(Bk, b, k, w.P, w.final_window, voiced ? pv[b] : 0, voiced ? entry[b] : 0);
             if (!w.final_window) mid_steps = w.budget > mid_steps ? w.budget : mid_steps;
             steps = w.budget > steps ? w.budget : steps;
             ++Bk;
         }
-        const TickPlan step_plan = lockstep_steps(Bk);
-        for (int step = 0; step < steps; ++step) {
-            if (int rc = run_tick(h, s, step == 0 ? begin : step_plan, q, sa, stream)) return rc;
-            // the host's only look at the device; a non-final window never ends early, so there is nothing to see before the last of them is complete
-            if ((step + 1) % GPT_CHECK_EVERY == 0 && step + 1 < steps && step + 1 >= mid_steps) {
-                bool all;
-                if (int rc = all_done(h, s, Bk, stream, &all)) return rc;
-                if (all) break;
-            }
-        }
+        // a non-final window never ends early, so there is nothing to see before the last of them is complete
+        if (int rc = run_steps(h, s, begin, Bk, steps, mid_steps, q, sa, stream)) return rc;
     }
     return 0;
 }
@@ -534,9 +534,10 @@ int at_gpt_generate_long(at_gpt_t* h, const int32_t* src_dev, int src_stride, co
                          int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
                          const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
                          float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev) {
-    return generate_long("at_gpt_generate_long", VoiceTable{}, h, src_dev, src_stride, src_len, B, S, H, r, semantic_offset, semantic_vocab, infer_token, acoustic_offset,
-                         codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev, finish_dev,
-                         logits_out_dev, state_dev, state_bytes, max_len, stream, status_dev);
+    return generate_long(GenRequest{"at_gpt_generate_long", h, {src_dev, src_stride, src_len, B}, {S, H, r},
+                                    {semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token},
+                                    {max_new, temperature, top_k, uniforms_dev, u_stride}, {out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev},
+                                    {state_dev, state_bytes, max_len}, stream, status_dev});
 }
 
 int at_gpt_generate_long_prompted(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int B, const int32_t* prompt_sem_dev, int p_stride,
@@ -544,12 +545,11 @@ int at_gpt_generate_long_prompted(at_gpt_t* h, const int32_t* src_dev, int src_s
                                   int r, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
                                   float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
                                   int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, at_stream_t stream, int32_t* status_dev) {
-    VoiceTable vt;
-    vt.sem = prompt_sem_dev; vt.codes = prompt_codes_dev; vt.len = prompt_len; vt.of_src = prompt_of_src;
-    vt.p_stride = p_stride; vt.f_stride = f_stride; vt.n = n_prompts; vt.on = true;
-    return generate_long("at_gpt_generate_long_prompted", vt, h, src_dev, src_stride, src_len, B, S, H, r, semantic_offset, semantic_vocab, infer_token, acoustic_offset,
-                         codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev, finish_dev,
-                         logits_out_dev, state_dev, state_bytes, max_len, stream, status_dev);
+    return generate_long(GenRequest{"at_gpt_generate_long_prompted", h, {src_dev, src_stride, src_len, B}, {S, H, r},
+                                    {semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token},
+                                    {max_new, temperature, top_k, uniforms_dev, u_stride}, {out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev},
+                                    {state_dev, state_bytes, max_len}, stream, status_dev,
+                                    {prompt_sem_dev, p_stride, prompt_codes_dev, f_stride, prompt_len, n_prompts, prompt_of_src, true}});
 }
 
 size_t at_gpt_queue_state_bytes(const at_gpt_t* h, int slots, int max_len, int tick_tokens) {
@@ -563,43 +563,26 @@ size_t at_gpt_queue_state_bytes(const at_gpt_t* h, int slots, int max_len, int t
     return carve_state(nullptr, slots, max_len, tick_tokens, h->vocab, h->n_layer).bytes;
 }
 
-static int generate_queue(const char* who, const VoiceTable& vt, at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, int S, int H,
-                          int r, int semantic_offset, int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new,
-                          float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
-                          int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace,
-                          int trace_cap, int32_t* n_ticks, int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
+static int generate_queue(const GenRequest& rq) {
+    at_gpt* h = rq.h;
+    const QueueExtras& x = rq.queue;
+    const int n_src = rq.src.n, slots = x.slots, tick_tokens = x.tick_tokens, max_len = rq.state.max_len;
     AT_REQUIRE(h && h->finalized, "the model is not finalized");
     AT_REQUIRE(n_src >= 1 && n_src <= GPT_MAX_QUEUE, "n_src must be 1 to 4096");
     AT_REQUIRE(slots >= 1 && slots <= GPT_MAX_B, "slots must be 1 to 64");
-    AT_REQUIRE(src_dev && src_len && uniforms_dev && out_ids_dev && out_len_dev && finish_dev, "null pointer");
-    AT_REQUIRE(state_dev != nullptr, "null state");
-    AT_REQUIRE(trace_cap >= 0 && (trace != nullptr || trace_cap == 0), "trace_cap must be 0 without a trace and never negative");
-    const int V = h->vocab, block = h->block;
     Rules q{};
-    if (int rc = check_long_rules(h, S, H, r, src_dev, src_stride, semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token, max_new,
-                                  temperature, top_k, status_dev, &q))
-        return rc;
-    for (int i = 0; i < n_src; ++i)
-        if (src_len[i] < 1 || src_len[i] > src_stride || src_len[i] > GPT_MAX_SOURCE) {
-            set_error(std::string(who) + ": src_len of source " + std::to_string(i) + " must be 1 to min(src_stride, 65536)");
-            return -1;
-        }
     std::vector<int32_t> pv, entry;
-    if (int rc = check_voice(who, vt, src_len, n_src, S, H, r, &pv, &entry)) return rc;
+    if (int rc = check_request(rq, "source", &q, &pv, &entry)) return rc;
     const bool voiced = !pv.empty();
-    q.vp_sem = vt.sem; q.vp_codes = vt.codes; q.vp_stride = vt.p_stride; q.vf_stride = vt.f_stride;
-    const auto [need_len, need_stride] = gpt_extent(src_len, n_src, S, H, r, max_new, block, voiced ? pv.data() : nullptr);
-    AT_REQUIRE(out_stride >= need_stride && u_stride >= need_stride, "out_stride and u_stride must hold the longest source's stream");
-    AT_REQUIRE(max_len >= need_len && max_len <= block, "max_len must hold the longest window with its new ids and not exceed the block size");
     AT_REQUIRE(tick_tokens >= slots + max_len && tick_tokens <= GPT_MAX_TICK_TOKENS, "tick_tokens must be at least slots + max_len (one window always fits) and at most 65600");
-    const GptState s = carve_state(state_dev, slots, max_len, tick_tokens, V, h->n_layer);
-    AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_gpt_queue_state_bytes(h, slots, max_len, tick_tokens)");
+    const GptState s = carve_state(rq.state.dev, slots, max_len, tick_tokens, h->vocab, h->n_layer);
+    AT_REQUIRE(rq.state.bytes >= s.bytes, "state too small: at_gpt_queue_state_bytes(h, slots, max_len, tick_tokens)");
     // ---- nothing above touched the device
     DeviceGuard guard(h->device);
     AT_REQUIRE(guard.ok, "cannot select the handle's device");
-    hipStream_t stream = (hipStream_t)stream_;
-    const SampleArgs sa = generation_args(h, s, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev, max_new);
-    GptQueueSchedule schedule(src_len, n_src, S, H, r, max_new, block, slots, tick_tokens, voiced ? pv.data() : nullptr);
+    hipStream_t stream = (hipStream_t)rq.stream;
+    const SampleArgs sa = generation_args(h, s, rq.samp, rq.out);
+    GptQueueSchedule schedule(rq.src.len, n_src, rq.geo.S, rq.geo.H, rq.geo.r, rq.samp.max_new, h->block, slots, tick_tokens, voiced ? pv.data() : nullptr);
     GptQueueTick t;
     while (schedule.next(&t)) {
         TickPlan p{};
@@ -611,8 +594,8 @@ static int generate_queue(const char* who, const VoiceTable& vt, at_gpt_t* h, co
         }
         if (int rc = run_tick(h, s, p, q, sa, stream)) return rc;
         const int at = schedule.ticks() - 1;
-        if (at < trace_cap) {   // a trace too small loses its tail, the run goes on
-            int32_t* row = trace + 4 * (size_t)at;
+        if (at < x.trace_cap) {   // a trace too small loses its tail, the run goes on
+            int32_t* row = x.trace + 4 * (size_t)at;
             row[0] = t.n_step; row[1] = t.n_start; row[2] = t.prefill_tokens; row[3] = t.route();
         }
         if (t.poll) {   // the host's only look at the device: some slot is in a final window, and when that ends only the device knows
@@ -621,8 +604,8 @@ static int generate_queue(const char* who, const VoiceTable& vt, at_gpt_t* h, co
             schedule.seen(h->flags_host);
         }
     }
-    if (n_ticks) *n_ticks = schedule.ticks();
-    if (placement) std::memcpy(placement, schedule.placement().data(), (size_t)n_src * 3 * sizeof(int32_t));
+    if (x.n_ticks) *x.n_ticks = schedule.ticks();
+    if (x.placement) std::memcpy(x.placement, schedule.placement().data(), (size_t)n_src * 3 * sizeof(int32_t));
     return 0;
 }
 
@@ -631,9 +614,10 @@ int at_gpt_generate_queue(at_gpt_t* h, const int32_t* src_dev, int src_stride, c
                           const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev, int32_t* finish_dev,
                           float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens, int32_t* trace, int trace_cap,
                           int32_t* n_ticks, int32_t* placement, at_stream_t stream, int32_t* status_dev) {
-    return generate_queue("at_gpt_generate_queue", VoiceTable{}, h, src_dev, src_stride, src_len, n_src, S, H, r, semantic_offset, semantic_vocab, infer_token,
-                          acoustic_offset, codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev,
-                          finish_dev, logits_out_dev, state_dev, state_bytes, max_len, slots, tick_tokens, trace, trace_cap, n_ticks, placement, stream, status_dev);
+    return generate_queue(GenRequest{"at_gpt_generate_queue", h, {src_dev, src_stride, src_len, n_src}, {S, H, r},
+                                     {semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token},
+                                     {max_new, temperature, top_k, uniforms_dev, u_stride}, {out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev},
+                                     {state_dev, state_bytes, max_len}, stream, status_dev, {}, {slots, tick_tokens, trace, trace_cap, n_ticks, placement}});
 }
 
 int at_gpt_generate_queue_prompted(at_gpt_t* h, const int32_t* src_dev, int src_stride, const int32_t* src_len, int n_src, const int32_t* prompt_sem_dev, int p_stride,
@@ -642,12 +626,12 @@ int at_gpt_generate_queue_prompted(at_gpt_t* h, const int32_t* src_dev, int src_
                                    float temperature, int top_k, const float* uniforms_dev, int u_stride, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
                                    int32_t* finish_dev, float* logits_out_dev, void* state_dev, size_t state_bytes, int max_len, int slots, int tick_tokens,
                                    int32_t* trace, int trace_cap, int32_t* n_ticks, int32_t* placement, at_stream_t stream, int32_t* status_dev) {
-    VoiceTable vt;
-    vt.sem = prompt_sem_dev; vt.codes = prompt_codes_dev; vt.len = prompt_len; vt.of_src = prompt_of_src;
-    vt.p_stride = p_stride; vt.f_stride = f_stride; vt.n = n_prompts; vt.on = true;
-    return generate_queue("at_gpt_generate_queue_prompted", vt, h, src_dev, src_stride, src_len, n_src, S, H, r, semantic_offset, semantic_vocab, infer_token,
-                          acoustic_offset, codebook_size, stop_token, max_new, temperature, top_k, uniforms_dev, u_stride, out_ids_dev, out_stride, out_len_dev,
-                          finish_dev, logits_out_dev, state_dev, state_bytes, max_len, slots, tick_tokens, trace, trace_cap, n_ticks, placement, stream, status_dev);
+    return generate_queue(GenRequest{"at_gpt_generate_queue_prompted", h, {src_dev, src_stride, src_len, n_src}, {S, H, r},
+                                     {semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token},
+                                     {max_new, temperature, top_k, uniforms_dev, u_stride}, {out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev},
+                                     {state_dev, state_bytes, max_len}, stream, status_dev,
+                                     {prompt_sem_dev, p_stride, prompt_codes_dev, f_stride, prompt_len, n_prompts, prompt_of_src, true},
+                                     {slots, tick_tokens, trace, trace_cap, n_ticks, placement}});
 }
 
 }  // extern "C"
@@ -664,12 +648,10 @@ struct GptStreamState {
 GptStreamState carve_stream(void* base, const at_gpt* h, int S, int H, int r) {
     GptStreamState st{};
     st.g = carve_state(base, 1, h->block, h->block, h->vocab, h->n_layer);
-    char* p = static_cast<char*>(base);
-    size_t off = st.g.bytes;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += round256(bytes); return q; };
-    st.src = (int*)take((size_t)2 * S * 4);
-    st.carry = (int*)take((size_t)r * (S - H) * 4 + 4);
-    st.bytes = off;
+    StateCarver c(base, st.g.bytes);
+    st.src = c.take<int>((size_t)2 * S);
+    st.carry = c.take<int>((size_t)r * (S - H) + 1);
+    st.bytes = c.off;
     return st;
 }
 
@@ -681,21 +663,13 @@ __global__ __launch_bounds__(1024) void gpt_stream_shift_kernel(int* buf, int sh
     if (t < n) buf[t] = v;
 }
 
-int check_stream_geometry(const at_gpt* h, int S, int H, int r) {
-    AT_REQUIRE(S >= 2 && S % 2 == 0 && H >= 2 && H % 2 == 0, "the window S and the hop H must be even, at least 2");
-    AT_REQUIRE(H <= S, "the hop H must not exceed the window S");
-    AT_REQUIRE(r >= 1 && r <= GPT_MAX_BLOCK, "r (acoustic ids per source id) must be 1 to 1024");
-    AT_REQUIRE((int64_t)S + 1 + (int64_t)r * S <= h->block, "a window does not fit: S + 1 + r S must not exceed the model's block size");
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t at_gpt_stream_state_bytes(const at_gpt_t* h, int S, int H, int r) {
     if (!(h && h->finalized)) { set_error("at_gpt_stream_state_bytes: the model is not finalized"); return 0; }
-    if (check_stream_geometry(h, S, H, r)) return 0;
+    if (check_geometry(h, Geometry{S, H, r})) return 0;
     return carve_stream(nullptr, h, S, H, r).bytes;
 }
 
@@ -713,9 +687,10 @@ int at_gpt_stream_push(at_gpt_t* h, void* state_dev, size_t state_bytes, int64_t
     AT_REQUIRE(!final || pos[0] + n_new >= 1, "a final call with nothing pushed");
     const int block = h->block;
     Rules q{};
-    if (int rc = check_long_rules(h, S, H, r, ids_dev, 1, semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token, max_new, temperature,
-                                  top_k, status_dev, &q))
-        return rc;
+    // one source of stride 1; the sampler's view of the caller's arrays replaces them below, once the geometry is known to be sound
+    GenRequest rq{"at_gpt_stream_push", h, {ids_dev, 1, nullptr, 1}, {S, H, r}, {semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token},
+                        {max_new, temperature, top_k, uniforms_dev, 0}, {out_ids_dev, 0, out_len_dev, finish_dev, nullptr}, {state_dev, state_bytes, block}, stream_, status_dev};
+    if (int rc = check_long_rules(rq, &q)) return rc;
     AT_REQUIRE(u_pos0 >= 0 && u_len >= 0 && out_cap >= 0, "u_pos0, u_len and out_cap must not be negative");
     // ---- the windows this call runs and what they need of the caller's arrays
     const int k0 = gpt_stream_windows_run(pos[0], S, H), k1 = gpt_stream_windows_run(pos[0] + n_new, S, H);
@@ -738,22 +713,15 @@ int at_gpt_stream_push(at_gpt_t* h, void* state_dev, size_t state_bytes, int64_t
     // the sampler and the begin kernel index the stream by absolute position: the call's arrays are addressed from the position of their first element
     int32_t* out_abs = reinterpret_cast<int32_t*>(reinterpret_cast<intptr_t>(out_ids_dev) - (intptr_t)p_base * 4);
     const float* u_abs = reinterpret_cast<const float*>(reinterpret_cast<intptr_t>(uniforms_dev) - (intptr_t)u_pos0 * 4);
-    const SampleArgs sa = generation_args(h, st.g, temperature, top_k, u_abs, 0, out_abs, 0, out_len_dev, finish_dev, nullptr, max_new);
+    rq.samp.uniforms = u_abs;
+    rq.out.ids = out_abs;
+    const SampleArgs sa = generation_args(h, st.g, rq.samp, rq.out);
     if ((k1 > k0 || final) && k0 > 0) AT_CHECK_HIP(hipMemcpyAsync(out_ids_dev, st.carry, (size_t)carry * 4, hipMemcpyDeviceToDevice, stream));
-    const TickPlan step_plan = lockstep_steps(1);
     auto run_window = [&](int k, int n_src_ids, bool last) -> int {
         const GptWindow w = gpt_window(last ? k * H + n_src_ids : k * H + S + 1, k, S, H, r, max_new, block);
         TickPlan begin{};
         begin.start(0, 0, k, w.P, last);
-        for (int step = 0; step < w.budget; ++step) {
-            if (int rc = run_tick(h, st.g, step == 0 ? begin : step_plan, q, sa, stream)) return rc;
-            if (last && (step + 1) % GPT_CHECK_EVERY == 0 && step + 1 < w.budget) {   // the host's only look at the device: the final window's flag
-                bool all;
-                if (int rc = all_done(h, st.g, 1, stream, &all)) return rc;
-                if (all) break;
-            }
-        }
-        return 0;
+        return run_steps(h, st.g, begin, 1, w.budget, last ? 0 : w.budget, q, sa, stream);   // only the final window's flag is worth a look
     };
     GptStreamSchedule schedule(pos[0], n_new, final != 0, S, H);
     GptStreamRound rd;

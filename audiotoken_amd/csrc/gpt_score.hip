@@ -110,32 +110,28 @@ struct ScoreState {
     int *gather, *target, *parity, *out_index;   // per scored position of a pass
 };
 
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
 ScoreState carve_score_state(void* base, int rows, int cap, int tokens, int head_rows, int vocab, int n_layer) {
     ScoreState s{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += round256(bytes); return r; };
+    StateCarver c(base);
     const size_t R = (size_t)tokens;
-    s.g.done = (int*)take(GPT_MAX_B * 4);
-    s.g.tok_row = (int*)take(R * 4);
-    s.g.tok_pos = (int*)take(R * 4);
-    s.gather = (int*)take(R * 4);
-    s.target = (int*)take(R * 4);
-    s.parity = (int*)take(R * 4);
-    s.out_index = (int*)take(R * 4);
-    s.g.x = (float*)take(R * E * 4);
-    s.g.xn = (float*)take(R * E * 4);
-    s.g.q = (float*)take(R * 3 * E * 4);
-    s.g.h = (float*)take(R * FF * 4);
+    s.g.done = c.take<int>(GPT_MAX_B);
+    s.g.tok_row = c.take<int>(R);
+    s.g.tok_pos = c.take<int>(R);
+    s.gather = c.take<int>(R);
+    s.target = c.take<int>(R);
+    s.parity = c.take<int>(R);
+    s.out_index = c.take<int>(R);
+    s.g.x = c.take<float>(R * E);
+    s.g.xn = c.take<float>(R * E);
+    s.g.q = c.take<float>(R * 3 * E);
+    s.g.h = c.take<float>(R * FF);
     s.g.tok_id = (int*)s.g.h;   // as in carve_state: read by the embedding before the first layer's MLP writes h
-    s.g.logits = (float*)take((size_t)head_rows * vocab * 4);
+    s.g.logits = c.take<float>((size_t)head_rows * vocab);
     s.g.layer_stride = (size_t)rows * cap * NH * HD;
-    s.g.kc = (float*)take(s.g.layer_stride * n_layer * 4);
-    s.g.vc = (float*)take(s.g.layer_stride * n_layer * 4);
+    s.g.kc = c.take<float>(s.g.layer_stride * n_layer);
+    s.g.vc = c.take<float>(s.g.layer_stride * n_layer);
     s.g.cap = cap;
-    s.g.bytes = off;
+    s.g.bytes = c.off;
     return s;
 }
 

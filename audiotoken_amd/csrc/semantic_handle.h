@@ -1,7 +1,7 @@
 // What the handles of the two semantic tokenizers (at_hubert in hubert.hip, at_w2vbert in w2vbert.hip) have in common, stated once: tensor staging, the
 // device arena and its packed export / import replay (packed_model.h), the lazy weight splits per scheme, the range table, the common options, the
 // reports, the split-GEMM helper that owns the f16x2 scale rule (split_gemm_args) and the finalize helpers. A model file keeps what is its own: weight
-// pointers, LayerW, Plan, the site names, the model part of finalize, the list of weights it splits and the encode stages. HostTensor, stage_tensor and device_exists also serve the acoustic handle (encodec_handle.h).
+// pointers, LayerW, Plan, the site names, the model part of finalize, the list of weights it splits and the encode stages. stage_tensor also serves the acoustic handle (encodec_handle.h); HostTensor and device_exists come from model_handle.h.
 #pragma once
 #include <map>
 #include <string>
@@ -9,17 +9,10 @@
 
 #include "at_common.h"
 #include "gemm_bf16x3.h"
+#include "model_handle.h"   // HostTensor, device_exists
 #include "packed_model.h"
 
 namespace at {
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
-
-// at_*_create: whether `device_id` names a HIP device; if not, the error is set in the name of the exported function `fn`
-bool device_exists(const char* fn, int device_id);
 
 // at_*_set_tensor of every handle: one host tensor copied into h->staged until finalize()
 template <class H>

@@ -7,15 +7,6 @@
 
 namespace at {
 
-bool device_exists(const char* fn, int device_id) {
-    int n = 0;
-    if (!host_only_test() && (hipGetDeviceCount(&n) != hipSuccess || device_id < 0 || device_id >= n)) {
-        set_error(std::string(fn) + ": no such HIP device " + std::to_string(device_id));
-        return false;
-    }
-    return true;
-}
-
 // ---- range table ----------------------------------------------------------------------------------------------------------------------------
 int RangeTable::alloc() {
     if (dev) return 0;

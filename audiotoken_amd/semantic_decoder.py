@@ -442,10 +442,7 @@ class SemanticToAcoustic(LibHandle):
         cfg = self.config
         batch = tokens if isinstance(tokens, (list, tuple)) else [tokens]
         prompts = [prepare_source(t, cfg) for t in batch]
-        allow = None
-        if constrain:   # step s: the code book of its parity, and STOP where a whole frame has been written
-            a, n = cfg.ACOUSTIC_OFFSET, cfg.codebook_size
-            allow = [[a, a + n, cfg.STOP_TOKEN, cfg.STOP_TOKEN + 1], [a + n, a + 2 * n, 0, 0]]
+        allow = constrained_allow(cfg) if constrain else None   # step s: the code book of its parity, and STOP where a whole frame has been written
         ids, finish, logits = self.generate(prompts, max_new_tokens, temperature, top_k, cfg.STOP_TOKEN, uniforms, seed, allow, return_logits, top_p, min_p)
         return self._generation(ids, finish, logits)
 

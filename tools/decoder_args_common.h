@@ -1,20 +1,31 @@
-// What the three stand-alone argument checks of the GPT decoder share (tools/gpt_args.hip, gpt_long_args.hip, gpt_queue_args.hip): the error sink, the
-// case bookkeeping, stand-ins for device pointers and a finalized handle built by hand (csrc/gpt.h) with dimensions and no device memory behind it.
+// What the ten stand-alone argument checks of the semantic decoder share (tools/gpt_*args.hip, fine_*args.hip, semantic_stream_args.hip): the error sink, the
+// case bookkeeping, stand-ins for device pointers, exact-size copies of host arrays, finalized handles of both stages built by hand (csrc/gpt.h, csrc/fine.h)
+// with dimensions and no device memory behind them, and stand-ins for the launchers the fine forward calls, which count their calls: a program that links
+// fine.hip ends by showing that none was reached. A program that does not link gemm_f32.hip defines ARGS_STAND_IN_GEMM before it includes this header.
 #pragma once
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "../audiotoken_amd/csrc/fine.h"
 #include "../audiotoken_amd/csrc/gpt.h"
+#include "../audiotoken_amd/csrc/w2vbert_kernels.h"
 #include "../include/audiotoken_hip.h"
 
 namespace at {
 static std::string g_error;
+static int g_launches = 0;
 void set_error(const std::string& msg) { g_error = msg; }   // the library's lives in encodec.hip, which these programs do not link
+#ifdef ARGS_STAND_IN_GEMM
+int launch_gemm(const GemmArgs&, hipStream_t) { ++g_launches; return -1; }
+#endif
+int launch_relpos_attention(const AttnArgs&, hipStream_t) { ++g_launches; return -1; }
+int launch_layernorm(const float*, const float*, const float*, const float*, float*, long long, int, hipStream_t) { ++g_launches; return -1; }
 }  // namespace at
 
 static int failures = 0;
@@ -47,11 +58,19 @@ static std::unique_ptr<int32_t[]> exact_copy(const std::vector<int32_t>& v) {
     return p;
 }
 
-// a 2-layer model of 128 positions, finalized by hand
+// a 2-layer GPT of 128 positions, finalized by hand
 static void finalize_by_hand(at_gpt* model, int vocab) {
     model->finalized = true;
     model->n_layer = 2;
     model->vocab = vocab;
+    model->block = 128;
+    model->layers.resize(2);
+}
+// a 2-layer fine model of 768 channels and a window of 128, finalized by hand
+static void finalize_by_hand(at_fine* model) {
+    model->finalized = true;
+    model->n_layer = 2;
+    model->embd = 768;
     model->block = 128;
     model->layers.resize(2);
 }

@@ -3,42 +3,10 @@
 // device: the handle is a finalized at_fine built here by hand (fine.h), with dimensions and no device memory behind it. Built and run by
 // `make -C audiotoken_amd/csrc fine_asan`:
 //   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined tools/fine_args.hip audiotoken_amd/csrc/fine.hip
-// The three launchers fine.hip's forward calls (GEMM, attention, LayerNorm) are stand-ins here that count their calls: the program ends by showing that
-// none was reached. The host array (the rows' lengths) lives in a heap block of exactly the size the call may read, so a read past it is a sanitizer report.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "../audiotoken_amd/csrc/fine.h"
-#include "../audiotoken_amd/csrc/w2vbert_kernels.h"
-#include "../include/audiotoken_hip.h"
-
-namespace at {
-static std::string g_error;
-static int g_launches = 0;
-void set_error(const std::string& msg) { g_error = msg; }   // the library's lives in encodec.hip, which this program does not link
-int launch_gemm(const GemmArgs&, hipStream_t) { ++g_launches; return -1; }
-int launch_relpos_attention(const AttnArgs&, hipStream_t) { ++g_launches; return -1; }
-int launch_layernorm(const float*, const float*, const float*, const float*, float*, long long, int, hipStream_t) { ++g_launches; return -1; }
-}  // namespace at
-
-static int failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        std::printf("FAILED: %s (last error: %s)\n", what, at::g_error.c_str());
-        ++failures;
-    }
-}
-static bool refused(int rc, const char* text) { return rc != 0 && at::g_error.find(text) != std::string::npos; }
-
-// stand-ins for device pointers: never dereferenced by a call that is refused
-static int32_t fake_i[4];
-static float fake_f[4];
+// The three launchers fine.hip's forward calls (GEMM, attention, LayerNorm) are stand-ins that count their calls (decoder_args_common.h): the program ends by
+// showing that none was reached. The host array (the rows' lengths) lives in a heap block of exactly the size the call may read.
+#define ARGS_STAND_IN_GEMM
+#include "decoder_args_common.h"
 
 struct Call {
     at_fine* h;
@@ -56,21 +24,16 @@ struct Call {
     int max_T = 300;
 
     int run() const {
-        std::unique_ptr<int32_t[]> l(new int32_t[lens.size() ? lens.size() : 1]);
-        if (!lens.empty()) std::memcpy(l.get(), lens.data(), lens.size() * sizeof(int32_t));
+        const auto l = exact_copy(lens);
         at::g_error.clear();
-        return at_fine_generate(h, coarse, stride, lens.empty() ? nullptr : l.get(), B, temperature, greedy, uniforms, n_max, out, nullptr, nullptr, state,
+        return at_fine_generate(h, coarse, stride, l.get(), B, temperature, greedy, uniforms, n_max, out, nullptr, nullptr, state,
                                 state_bytes, max_T, nullptr, nullptr);
     }
 };
 
 int main() {
     at_fine model;
-    model.finalized = true;
-    model.n_layer = 2;
-    model.embd = 768;
-    model.block = 128;
-    model.layers.resize(2);
+    finalize_by_hand(&model);
     at_fine raw;   // never finalized
 
     // ---- the window count: n = max(0, ceil((T - W) / H)) + 1
@@ -138,10 +101,5 @@ int main() {
     { Call c = ok; c.n_max = 0; expect(refused(c.run(), "n_max"), "n_max = 0"); }
     { Call c = ok; c.n_max = 9; expect(refused(c.run(), "state too small"), "an n_max larger than needed"); }
     expect(at::g_launches == 0, "no case reached a launch");
-    if (failures) {
-        std::printf("%d case(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("fine argument checks: ok\n");
-    return 0;
+    return verdict("fine argument checks");
 }

@@ -6,47 +6,8 @@
 // Built and run by `make -C audiotoken_amd/csrc fine_hist_asan` (FINE_HIST_ARGS="sched ..." for the second mode). The handle is a finalized at_fine built
 // by hand, the three launchers fine.hip's forward calls are stand-ins that count their calls, and the host arrays live in heap blocks of exactly the size
 // a call may read, so a read past one is a sanitizer report.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "../audiotoken_amd/csrc/fine.h"
-#include "../audiotoken_amd/csrc/w2vbert_kernels.h"
-#include "../include/audiotoken_hip.h"
-
-namespace at {
-static std::string g_error;
-static int g_launches = 0;
-void set_error(const std::string& msg) { g_error = msg; }   // the library's lives in encodec.hip, which this program does not link
-int launch_gemm(const GemmArgs&, hipStream_t) { ++g_launches; return -1; }
-int launch_relpos_attention(const AttnArgs&, hipStream_t) { ++g_launches; return -1; }
-int launch_layernorm(const float*, const float*, const float*, const float*, float*, long long, int, hipStream_t) { ++g_launches; return -1; }
-}  // namespace at
-
-static int failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        std::printf("FAILED: %s (last error: %s)\n", what, at::g_error.c_str());
-        ++failures;
-    }
-}
-static bool refused(int rc, const char* text) { return rc != 0 && at::g_error.find(text) != std::string::npos; }
-
-// stand-ins for device pointers: never dereferenced by a call that is refused
-static int32_t fake_i[4];
-static float fake_f[4];
-
-static std::unique_ptr<int32_t[]> exact(const std::vector<int32_t>& v) {
-    std::unique_ptr<int32_t[]> p(new int32_t[v.size() ? v.size() : 1]);
-    if (!v.empty()) std::memcpy(p.get(), v.data(), v.size() * sizeof(int32_t));
-    return p;
-}
+#define ARGS_STAND_IN_GEMM
+#include "decoder_args_common.h"
 
 // W = 128, H = 64. Row 0 continues history 0 (70 frames: h = 64), row 1 has none. 300 frames after 64 history cells are 5 windows, without them 4.
 struct Call {
@@ -64,26 +25,22 @@ struct Call {
     int max_T = 300;
 
     int run() const {
-        auto l = exact(lens), hl = exact(hist_lens), of = exact(of_row);
+        const auto l = exact_copy(lens), hl = exact_copy(hist_lens), of = exact_copy(of_row);
         at::g_error.clear();
         const int B = (int)lens.size();
         if (queue)
-            return at_fine_generate_queue_hist(h, fake_i, l.get(), B, hist, h_stride, hist_lens.empty() ? nullptr : hl.get(), n_hist,
-                                               of_row.empty() ? nullptr : of.get(), max_hist, 0.5f, 0, fake_f, fake_i, nullptr, nullptr, fake_f, state_bytes,
+            return at_fine_generate_queue_hist(h, fake_i, l.get(), B, hist, h_stride, hl.get(), n_hist,
+                                               of.get(), max_hist, 0.5f, 0, fake_f, fake_i, nullptr, nullptr, fake_f, state_bytes,
                                                max_T, 2, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-        return at_fine_generate_hist(h, fake_i, 300, l.get(), B, hist, h_stride, hist_lens.empty() ? nullptr : hl.get(), n_hist,
-                                     of_row.empty() ? nullptr : of.get(), max_hist, 0.5f, 0, fake_f, n_max, fake_i, nullptr, nullptr, fake_f, state_bytes, max_T,
+        return at_fine_generate_hist(h, fake_i, 300, l.get(), B, hist, h_stride, hl.get(), n_hist,
+                                     of.get(), max_hist, 0.5f, 0, fake_f, n_max, fake_i, nullptr, nullptr, fake_f, state_bytes, max_T,
                                      nullptr, nullptr);
     }
 };
 
 static int refusals() {
     at_fine model;
-    model.finalized = true;
-    model.n_layer = 2;
-    model.embd = 768;
-    model.block = 128;
-    model.layers.resize(2);
+    finalize_by_hand(&model);
     at_fine raw;   // never finalized
     const int W = 128, H = 64, top = 1 << 18;
 
@@ -161,12 +118,7 @@ static int refusals() {
         }
     }
     expect(at::g_launches == 0, "no case reached a launch");
-    if (failures) {
-        std::printf("%d case(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("fine history argument checks: ok\n");
-    return 0;
+    return verdict("fine history argument checks");
 }
 
 static int sched(int argc, char** argv) {

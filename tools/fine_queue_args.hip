@@ -7,42 +7,8 @@
 // Built and run by `make -C audiotoken_amd/csrc fine_queue_asan` (FINE_QUEUE_ARGS="dry ..." for the second mode). The three launchers fine.hip's forward
 // calls are stand-ins that count their calls: the program ends by showing that none was reached. The host arrays live in heap blocks of exactly the size
 // the call may touch, so an access past them is a sanitizer report.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "../audiotoken_amd/csrc/fine.h"
-#include "../audiotoken_amd/csrc/w2vbert_kernels.h"
-#include "../include/audiotoken_hip.h"
-
-namespace at {
-static std::string g_error;
-static int g_launches = 0;
-void set_error(const std::string& msg) { g_error = msg; }   // the library's lives in encodec.hip, which this program does not link
-int launch_gemm(const GemmArgs&, hipStream_t) { ++g_launches; return -1; }
-int launch_relpos_attention(const AttnArgs&, hipStream_t) { ++g_launches; return -1; }
-int launch_layernorm(const float*, const float*, const float*, const float*, float*, long long, int, hipStream_t) { ++g_launches; return -1; }
-}  // namespace at
-
-static int failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        std::printf("FAILED: %s (last error: %s)\n", what, at::g_error.c_str());
-        ++failures;
-    }
-}
-static bool refused(int rc, const char* text) { return rc != 0 && at::g_error.find(text) != std::string::npos; }
-
-// stand-ins for device pointers: never dereferenced by a call that is refused
-static int32_t fake_i[4];
-static float fake_f[4];
-constexpr int INT_MAX_ = std::numeric_limits<int>::max(), INT_MIN_ = std::numeric_limits<int>::min();
+#define ARGS_STAND_IN_GEMM
+#include "decoder_args_common.h"
 
 // W = 128: rows of 300 frames (4 windows), 1 frame and 129 frames (2 windows) through 2 slots
 struct Call {
@@ -61,13 +27,12 @@ struct Call {
     int trace_cap = 0;
 
     int run() const {
-        std::unique_ptr<int32_t[]> l(new int32_t[lens.size() ? lens.size() : 1]);
-        if (!lens.empty()) std::memcpy(l.get(), lens.data(), lens.size() * sizeof(int32_t));
+        const auto l = exact_copy(lens);
         std::unique_ptr<int32_t[]> trace(new int32_t[trace_cap > 0 ? 3 * (size_t)trace_cap : 1]);
         std::unique_ptr<int32_t[]> place(new int32_t[n_rows > 0 && n_rows <= at::FINE_MAX_QUEUE ? 3 * (size_t)n_rows : 1]);
         int32_t passes = -7;
         at::g_error.clear();
-        const int rc = at_fine_generate_queue(h, coarse, lens.empty() ? nullptr : l.get(), n_rows, temperature, greedy, uniforms, out, nullptr, nullptr, state,
+        const int rc = at_fine_generate_queue(h, coarse, l.get(), n_rows, temperature, greedy, uniforms, out, nullptr, nullptr, state,
                                               state_bytes, max_T, slots, with_trace ? trace.get() : nullptr, trace_cap, &passes,
                                               with_placement ? place.get() : nullptr, nullptr, nullptr);
         if (rc != 0 && passes != -7) {
@@ -80,11 +45,7 @@ struct Call {
 
 static int refusals() {
     at_fine model;
-    model.finalized = true;
-    model.n_layer = 2;
-    model.embd = 768;
-    model.block = 128;
-    model.layers.resize(2);
+    finalize_by_hand(&model);
     at_fine raw;   // never finalized
 
     // ---- at_fine_queue_state_bytes: the layout of at_fine_state_bytes for (slots, max_T), nothing per row
@@ -134,12 +95,7 @@ static int refusals() {
     { Call c = ok; c.n_rows = 4096; c.lens.assign(4096, 300); c.lens[4095] = 1; expect(refused(c.run(), "state too small"), "4096 rows"); }
     { Call c = ok; c.max_T = 1 << 18; c.lens = {1 << 18, 1 << 18, 1}; expect(refused(c.run(), "state too small"), "rows of the largest length"); }
     expect(at::g_launches == 0, "no case reached a launch");
-    if (failures) {
-        std::printf("%d case(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("fine queue argument checks: ok\n");
-    return 0;
+    return verdict("fine queue argument checks");
 }
 
 static int dry_run(int argc, char** argv) {

@@ -1,9 +1,9 @@
 // The argument checks of the GPT decoder's entry points (audiotoken_amd/csrc/gpt.hip: at_gpt_generate, at_gpt_state_bytes; gpt_model.hip: at_op_topk_sample) under
 // AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program. Every case below is refused before anything is launched, so it needs no
-// device: the handle is a finalized at_gpt built by hand (gpt_args_common.h). Built and run by `make -C audiotoken_amd/csrc gpt_asan`:
+// device: the handle is a finalized at_gpt built by hand (decoder_args_common.h). Built and run by `make -C audiotoken_amd/csrc gpt_asan`:
 //   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined tools/gpt_args.hip audiotoken_amd/csrc/{gpt,gpt_model,gemm_f32}.hip
 // (gemm_f32.hip only because the model pass calls its launcher; nothing of it runs here).
-#include "gpt_args_common.h"
+#include "decoder_args_common.h"
 
 struct Call {
     at_gpt* h;

@@ -1,8 +1,8 @@
 // The argument and schedule checks of the long form's entry points (audiotoken_amd/csrc/gpt.hip: at_gpt_generate_long, at_gpt_long_state_bytes,
 // at_gpt_long_num_windows) under AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program, the way tools/gpt_args.hip checks at_gpt_generate:
-// the handle is a finalized at_gpt built by hand (gpt_args_common.h) and every case is refused before anything is launched. Built and run by
+// the handle is a finalized at_gpt built by hand (decoder_args_common.h) and every case is refused before anything is launched. Built and run by
 // `make -C audiotoken_amd/csrc gpt_long_asan`.
-#include "gpt_args_common.h"
+#include "decoder_args_common.h"
 
 // A model of 128 positions and 256 ids: semantic ids [0, 64), the two code books [64, 128) and [128, 192), INFER 200, STOP 201. S = 8, H = 4, r = 3:
 // a window holds 8 + 1 + 24 = 33 positions; rows of 30 ids (7 windows: the last reads 6 ids, starts at stream 84, carries 12) and 5 ids (one window).

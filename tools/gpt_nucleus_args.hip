@@ -1,8 +1,8 @@
 // The argument checks of the sampler's truncation (audiotoken_amd/csrc/gpt.hip: at_gpt_set_truncation; gpt_model.hip: at_op_nucleus_sample)
 // under AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program. Every refused case is refused before anything is launched and the accepted
-// ones only write the handle, so it needs no device: the handle is a finalized at_gpt built by hand (gpt_args_common.h). Built and run by
+// ones only write the handle, so it needs no device: the handle is a finalized at_gpt built by hand (decoder_args_common.h). Built and run by
 // `make -C audiotoken_amd/csrc gpt_nucleus_asan`.
-#include "gpt_args_common.h"
+#include "decoder_args_common.h"
 
 int main() {
     at_gpt model;

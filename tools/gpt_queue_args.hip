@@ -1,6 +1,6 @@
 // The generation queue's host side (audiotoken_amd/csrc/gpt.hip: at_gpt_generate_queue, at_gpt_queue_state_bytes; csrc/gpt.h: GptQueueSchedule) under
 // AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program, the way tools/gpt_long_args.hip checks the long form. Three modes:
-//   gpt_queue_args                                    every refusal path on a finalized at_gpt built by hand (gpt_args_common.h)
+//   gpt_queue_args                                    every refusal path on a finalized at_gpt built by hand (decoder_args_common.h)
 //   gpt_queue_args dry S H r block max_new slots tick_tokens N:e [N:e ...]
 //                                                     the scheduler alone: sources of N ids whose final window ends after e sampler launches; prints
 //                                                     "tick <steps> <starts> <prefill> <route>" per tick, then "source <slot> <first> <last>" per source
@@ -10,7 +10,7 @@
 // Built and run by `make -C audiotoken_amd/csrc gpt_queue_asan` (QUEUE_ARGS="dry ..." or "extent ..." for the other modes).
 #include <cstdlib>
 
-#include "gpt_args_common.h"
+#include "decoder_args_common.h"
 
 // The model and the token space of tools/gpt_long_args.hip: 128 positions, 256 ids, S = 8, H = 4, r = 3; sources of 30 ids (7 windows, the stream reaches
 // 84 + 16 = 100 positions, the final window 6 + 1 + 12 + 16 = 35 tokens) and 5 ids, through 2 slots.

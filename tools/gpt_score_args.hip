@@ -1,8 +1,8 @@
 // The argument checks of teacher-forced scoring (audiotoken_amd/csrc/gpt_score.hip: at_gpt_score, at_gpt_score_state_bytes, at_op_score_rows)
 // under AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program. Every case below is refused before anything is launched, so it needs no
-// device: the handle is a finalized at_gpt built by hand (gpt_args_common.h). Built and run by `make -C audiotoken_amd/csrc gpt_score_asan`:
+// device: the handle is a finalized at_gpt built by hand (decoder_args_common.h). Built and run by `make -C audiotoken_amd/csrc gpt_score_asan`:
 //   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined tools/gpt_score_args.hip audiotoken_amd/csrc/{gpt_score,gpt,gpt_model,gemm_f32}.hip
-#include "gpt_args_common.h"
+#include "decoder_args_common.h"
 
 struct Call {
     at_gpt* h;

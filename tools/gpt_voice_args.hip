@@ -7,7 +7,7 @@
 // Built and run by `make -C audiotoken_amd/csrc gpt_voice_asan` (VOICE_ARGS="extent ..." for the other mode).
 #include <cstdlib>
 
-#include "gpt_args_common.h"
+#include "decoder_args_common.h"
 
 // The model and the token space of tools/gpt_long_args.hip: 128 positions, 256 ids, S = 8, H = 4, r = 3. Row 0 has 30 ids after a prompt of 4 (8 windows
 // of the 34 concatenated ids: the last reads 6, carries 12 and starts at result position 84), row 1 has 5 ids and no prompt.

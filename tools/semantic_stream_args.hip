@@ -8,16 +8,7 @@
 // tests/test_semantic_stream_cpu.py compares the printed rounds with the Python twins' (semantic_stream.gpt_stream_rounds / fine_stream_rounds).
 #include <cstdlib>
 
-#include "gpt_args_common.h"
-
-#include "../audiotoken_amd/csrc/fine.h"
-#include "../audiotoken_amd/csrc/w2vbert_kernels.h"
-
-namespace at {
-static int g_launches = 0;   // the fine forward's launchers are stand-ins that count their calls: none may be reached
-int launch_relpos_attention(const AttnArgs&, hipStream_t) { ++g_launches; return -1; }
-int launch_layernorm(const float*, const float*, const float*, const float*, float*, long long, int, hipStream_t) { ++g_launches; return -1; }
-}  // namespace at
+#include "decoder_args_common.h"
 
 alignas(16) static int32_t fake_ids[4];
 
@@ -97,11 +88,7 @@ int main(int argc, char** argv) {
     finalize_by_hand(&model, 256);
     at_gpt raw;
     at_fine fine;
-    fine.finalized = true;
-    fine.n_layer = 2;
-    fine.embd = 768;
-    fine.block = 128;
-    fine.layers.resize(2);
+    finalize_by_hand(&fine);
     at_fine fraw;
 
     // ---- at_gpt_stream_state_bytes: fixed by the geometry
