@@ -194,6 +194,9 @@ SIGNATURES = {
     "at_kmeans_row_d2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "at_kmeans_relocations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "at_op_gemm": (C.c_int, [C.POINTER(GemmDesc), C.c_void_p]),
+    "at_op_gemm_dual": (C.c_int, [C.POINTER(GemmDesc), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "at_op_gemm_route": (C.c_int, [C.POINTER(GemmDesc), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "at_op_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "at_required_tensors": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "at_op_gemm_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -94,7 +94,7 @@ struct FastDivU {
 };
 
 // ---- the one dense contraction every layer maps onto ----------------------------------------
-// out[b][m][n] = epi( alpha * ( sum_kk A(b,m,kk) * W[n][kk] + bias[n] ) ) (+ R[b][m][n])
+// out[b][m][n] = alpha * epi( sum_kk A(b,m,kk) * W[n][kk] + bias[n] ) (+ R[b][m][n])     (EPI_GLU: no alpha, no residual)
 // where A(b,m,kk) = pro( X[b][ row(m, kk / Cin) ][ kk % Cin ] ),  row(m,tap) = m*stride + tap - pad_left,
 // rows outside [0,Tin) are reflected (pad_mode 1) or read as zero (pad_mode 0).
 // Activations are time-major / channels-last ([B][T][C], C contiguous), so a causal conv1d, a strided
@@ -133,6 +133,17 @@ struct GemmArgs {
 
 int launch_gemm(const GemmArgs& a, hipStream_t stream);
 int check_gemm_args(const GemmArgs& a);
+// The route of a launch (gemm_f32.hip): launch_gemm picks one tile configuration from the shape, and each workgroup one of three bodies
+// (gemm_core.h: gemm_body). gemm_route reports both without launching anything — pure host code, no device needed.
+enum GemmConfig {   // block tile BM x BN; K tile 32 unless named
+    GEMM_CFG_128x16 = 0, GEMM_CFG_128x32 = 1, GEMM_CFG_128x64 = 2, GEMM_CFG_128x64_K16 = 3, GEMM_CFG_64x64 = 4, GEMM_CFG_128x128_K16 = 5, GEMM_CFG_128x128 = 6
+};
+struct GemmRoute {
+    int config = -1;                    // GemmConfig; -1 = nothing is launched (M or N is 0)
+    long long workgroups[3] = {0, 0, 0};   // per GemmBody (general, FAST, TAP), over the whole grid including the batch
+};
+GemmConfig gemm_config(const GemmArgs& a);
+int gemm_route(const GemmArgs& a, GemmRoute& r);   // check_gemm_args' code when the arguments are refused
 
 // ---- optional per-group timing with HIP events on the launch stream (bench.py roofline) -------
 struct Profiler {

@@ -383,8 +383,7 @@ int at_encodec_decode_stream_scatter(at_encodec_t* h, const void* state_in, int 
     return stream_pool_copy(h, true, false, pool, S, state_in, B, slots_dev, slots_host, stream);
 }
 
-int at_op_gemm(const at_gemm_desc* d, at_stream_t stream) {
-    AT_REQUIRE(d != nullptr, "null descriptor");
+static GemmArgs gemm_args_of(const at_gemm_desc* d, const float* X2, int64_t x2_bstride, int ld2, int K1) {
     GemmArgs a;
     a.X = d->X; a.x_bstride = d->x_bstride; a.Tin = d->Tin; a.Cin = d->Cin; a.ldx = d->ldx;
     a.ktaps = d->ktaps; a.stride = d->stride; a.pad_left = d->pad_left; a.pad_mode = d->pad_mode;
@@ -392,7 +391,28 @@ int at_op_gemm(const at_gemm_desc* d, at_stream_t stream) {
     a.R = d->R; a.r_bstride = d->r_bstride; a.ldr = d->ldr;
     a.M = d->M; a.N = d->N; a.K = d->K; a.batch = d->batch; a.pro = d->pro; a.epi = d->epi; a.alpha = d->alpha;
     a.aux_off = d->aux_off; a.row_mask = d->row_mask;
-    return launch_gemm(a, (hipStream_t)stream);
+    if (X2) { a.X2 = X2; a.x2_bstride = x2_bstride; a.ld2 = ld2; a.K1 = K1; }
+    return a;
+}
+
+int at_op_gemm(const at_gemm_desc* d, at_stream_t stream) {
+    AT_REQUIRE(d != nullptr, "null descriptor");
+    return launch_gemm(gemm_args_of(d, nullptr, 0, 0, 0), (hipStream_t)stream);
+}
+
+int at_op_gemm_dual(const at_gemm_desc* d, const float* X2, int64_t x2_bstride, int ld2, int K1, at_stream_t stream) {
+    AT_REQUIRE(d != nullptr, "null descriptor");
+    AT_REQUIRE(X2 != nullptr, "at_op_gemm_dual: null second source (at_op_gemm is the single-source call)");
+    return launch_gemm(gemm_args_of(d, X2, x2_bstride, ld2, K1), (hipStream_t)stream);
+}
+
+int at_op_gemm_route(const at_gemm_desc* d, const float* X2, int64_t x2_bstride, int ld2, int K1, int32_t* out) {
+    AT_REQUIRE(d != nullptr && out != nullptr, "null descriptor or output");
+    GemmRoute r;
+    if (int rc = gemm_route(gemm_args_of(d, X2, x2_bstride, ld2, K1), r)) return rc;
+    out[0] = r.config;
+    for (int i = 0; i < 3; ++i) out[1 + i] = (int32_t)r.workgroups[i];
+    return 0;
 }
 
 int at_op_rvq_encode(const float* x, int64_t rows, int T, const float* codebooks, const float* e2, int n_q, int16_t* codes,

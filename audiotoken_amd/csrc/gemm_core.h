@@ -8,6 +8,30 @@ namespace at {
 typedef float f4 __attribute__((ext_vector_type(4)));
 constexpr int BK = 32;   // default K tile; GemmTile's BKT parameter may select 16 (see gemm_f32.hip)
 
+// The three bodies of GemmTile::run (see there) and the one predicate that picks a workgroup's body from the launch arguments and the tile's
+// origin. Host and device share it: the kernel branches on it, at_op_gemm_route counts it over the grid without launching anything.
+//   BM_, BN_, BK_: the configuration's block tile and K tile; RPP_ = 256 / (BK_ / 4): rows staged per pass of the 256 threads
+enum GemmBody { GEMM_BODY_GENERAL = 0, GEMM_BODY_FAST = 1, GEMM_BODY_TAP = 2 };
+struct GemmBodyChoice {
+    bool fast, tap_ok;   // FAST wins when both hold
+    __host__ __device__ __forceinline__ int body() const { return fast ? GEMM_BODY_FAST : (tap_ok ? GEMM_BODY_TAP : GEMM_BODY_GENERAL); }
+};
+template <int BM_, int BN_, int BK_, int RPP_>
+__host__ __device__ __forceinline__ GemmBodyChoice gemm_body(const GemmArgs& a, int m0, int n0) {
+    const int Tlast_ = a.Tin - 1;
+    // an M tail is fine for the FAST body: rows >= M are clamped to row M-1 when the pointers are set up and their
+    // results are dropped by the epilogue
+    const int m_hi = m0 + BM_ - 1 < a.M - 1 ? m0 + BM_ - 1 : a.M - 1;
+    const bool fast = BN_ >= RPP_ && a.X2 == nullptr && (a.K % BK_) == 0 && n0 + BN_ <= a.N &&
+                      (a.ktaps == 1 || a.ldx == a.Cin) && m0 * a.stride - a.pad_left >= 0 &&
+                      m_hi * a.stride - a.pad_left + a.ktaps - 1 <= Tlast_;
+    // TAP body: boundary tiles of windowed convs (reflect / zero padding at the clip ends, N tails, rows that are not
+    // contiguous windows such as grouped convs): a K tile lies inside one tap, so the row pointers are rebuilt only
+    // when the tap changes (every Cin / BK tiles) instead of per K step.
+    const bool tap_ok = BN_ >= RPP_ && (a.K % BK_) == 0 && (a.X2 != nullptr ? (a.K1 % BK_) == 0 : (a.ktaps == 1 || (a.Cin % BK_) == 0));
+    return GemmBodyChoice{fast, tap_ok};
+}
+
 // Accumulator ownership after gemm_tile(): lane (r16 = lane&15, q = lane>>4) of wave (wm, wn) holds
 //   acc[i][j] = out[m = m0 + wm*TM*16 + i*16 + r16][n = n0 + wn*TN*16 + j*16 + q*4 .. +3]
 template <int BM, int BN, int WM, int WN, int PRO = PRO_NONE, int BKT = 32>
@@ -32,20 +56,11 @@ struct GemmTile {
     //          XCH + WCH precomputed pointers and a tile fetch is "pointer + kt*32" — ~20 VALU instead of ~340 per
     //          K step (PMC: 2.66 VALU per MFMA and 72 % MFMA-pipe busy before this split).
     //  !FAST — boundary tiles: reflect / zero padding, N/K tails, dual-source K; clamped unconditional loads + masks.
+    __host__ __device__ static __forceinline__ GemmBodyChoice body(const GemmArgs& a, int m0, int n0) { return gemm_body<BM, BN, BK, RPP>(a, m0, n0); }
     __device__ static __forceinline__ void run(const GemmArgs& a, float* smem, int m0, int n0, int b, f4 (&acc)[TM][TN]) {
-        const int Tlast_ = a.Tin - 1;
-        // an M tail is fine for the FAST body: rows >= M are clamped to row M-1 when the pointers are set up and their
-        // results are dropped by the epilogue
-        const int m_hi = m0 + BM - 1 < a.M - 1 ? m0 + BM - 1 : a.M - 1;
-        const bool fast = BN >= RPP && a.X2 == nullptr && (a.K % BK) == 0 && n0 + BN <= a.N &&
-                          (a.ktaps == 1 || a.ldx == a.Cin) && m0 * a.stride - a.pad_left >= 0 &&
-                          m_hi * a.stride - a.pad_left + a.ktaps - 1 <= Tlast_;
-        // TAP body: boundary tiles of windowed convs (reflect / zero padding at the clip ends, N tails, rows that are not
-        // contiguous windows such as grouped convs): a K tile lies inside one tap, so the row pointers are rebuilt only
-        // when the tap changes (every Cin / BK tiles) instead of per K step.
-        const bool tap_ok = BN >= RPP && (a.K % BK) == 0 && (a.X2 != nullptr ? (a.K1 % BK) == 0 : (a.ktaps == 1 || (a.Cin % BK) == 0));
-        if (fast) run_impl<1>(a, smem, m0, n0, b, acc);
-        else if (tap_ok) run_impl<2>(a, smem, m0, n0, b, acc);
+        const GemmBodyChoice c = body(a, m0, n0);
+        if (c.fast) run_impl<1>(a, smem, m0, n0, b, acc);
+        else if (c.tap_ok) run_impl<2>(a, smem, m0, n0, b, acc);
         else run_impl<0>(a, smem, m0, n0, b, acc);
     }
 

@@ -101,6 +101,8 @@ static int launch_cfg(const GemmArgs& a, hipStream_t stream) {
 int check_gemm_args(const GemmArgs& a) {
     AT_REQUIRE(a.X2 ? (a.ktaps == 1 && a.K1 == a.Cin && a.K1 % 4 == 0 && a.K > a.K1 && a.ld2 % 4 == 0 && a.ld2 >= a.K - a.K1)
                     : a.K == a.ktaps * a.Cin, "K must equal ktaps*Cin (or K1 + width of the second source)");
+    // the general body fetches 16-byte chunks: a second source of, say, 6 columns would have its last chunk read past the X2 row and the weight row
+    AT_REQUIRE(a.X2 == nullptr || (a.K - a.K1) % 4 == 0, "width of the second source must be a multiple of 4");
     AT_REQUIRE(a.Cin % 4 == 0 && a.N % 4 == 0, "Cin and N must be multiples of 4");
     AT_REQUIRE(a.ldx % 4 == 0 && a.ldx >= 4, "ldx must be a positive multiple of 4");
     AT_REQUIRE((a.ldc % 4 == 0 || (a.epi == EPI_GLU && a.ldc % 2 == 0)) && (a.R == nullptr || a.ldr % 4 == 0), "ldc/ldr must be multiples of 4");
@@ -111,25 +113,66 @@ int check_gemm_args(const GemmArgs& a) {
     return 0;
 }
 
-int launch_gemm(const GemmArgs& a, hipStream_t stream) {
-    if (int rc = check_gemm_args(a)) return rc;
-    if (a.M <= 0 || a.N <= 0) return 0;
-    if (a.N <= 16) return launch_cfg<128, 16, 4, 1>(a, stream);
-    if (a.N <= 32) return launch_cfg<128, 32, 4, 1>(a, stream);
+// The tile configuration of a launch, from its shape alone (pure host code: launch_gemm switches on it, gemm_route reports it)
+GemmConfig gemm_config(const GemmArgs& a) {
+    if (a.N <= 16) return GEMM_CFG_128x16;
+    if (a.N <= 32) return GEMM_CFG_128x32;
     if (a.N <= 64) {
         // grouped convs (HuBERT positional conv: 48 channels per group): a K tile of 16 keeps every tile inside one tap (TAP body)
-        if (a.ktaps > 1 && a.Cin % 32 != 0 && a.Cin % 16 == 0 && a.K % 16 == 0) return launch_cfg<128, 64, 4, 1, 16>(a, stream);
-        return launch_cfg<128, 64, 4, 1>(a, stream);
+        if (a.ktaps > 1 && a.Cin % 32 != 0 && a.Cin % 16 == 0 && a.K % 16 == 0) return GEMM_CFG_128x64_K16;
+        return GEMM_CFG_128x64;
     }
     // a launch that cannot fill the 512 tile slots (2 per CU) with 128 x 128 tiles — single-clip latency paths such as
-    // ffn2 of one 30 s clip: 12 x 8 tiles with K = 4096 — runs 4x as many 64 x 64 tiles instead (same k order, same results)
+    // ffn2 of one 30 s clip: 12 x 8 tiles with K = 4096 — runs 4x as many 64 x 64 tiles instead (same k order, same results:
+    // tests/test_gemm_f32_routes_gpu.py holds every configuration and body to the bits of a plain Linear over the im2col rows)
     const long long tiles128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128) * a.batch;
-    if ((long long)a.M * a.batch <= 1024 || tiles128 < 256) return launch_cfg<64, 64, 2, 2>(a, stream);
+    if ((long long)a.M * a.batch <= 1024 || tiles128 < 256) return GEMM_CFG_64x64;
     // K tile of 16 for the big tiles: 32 KB of LDS per workgroup and a shorter barrier-to-barrier section measured
     // 4-5 % faster than K tile 32 on the conformer shapes (ffn2 133 -> 139 TFLOP/s); K % 16 != 0 keeps the 32 path
     static const int bk16 = getenv("AUDIOTOKEN_GEMM_BK16") ? atoi(getenv("AUDIOTOKEN_GEMM_BK16")) : 1;
-    if (bk16 && a.pro == PRO_NONE && a.K % 16 == 0) return launch_cfg<128, 128, 2, 2, 16>(a, stream);   // (neutral on the ELU-prologue conv shapes)
-    return launch_cfg<128, 128, 2, 2>(a, stream);
+    if (bk16 && a.pro == PRO_NONE && a.K % 16 == 0) return GEMM_CFG_128x128_K16;   // (neutral on the ELU-prologue conv shapes)
+    return GEMM_CFG_128x128;
+}
+
+int launch_gemm(const GemmArgs& a, hipStream_t stream) {
+    if (int rc = check_gemm_args(a)) return rc;
+    if (a.M <= 0 || a.N <= 0) return 0;
+    switch (gemm_config(a)) {
+        case GEMM_CFG_128x16: return launch_cfg<128, 16, 4, 1>(a, stream);
+        case GEMM_CFG_128x32: return launch_cfg<128, 32, 4, 1>(a, stream);
+        case GEMM_CFG_128x64_K16: return launch_cfg<128, 64, 4, 1, 16>(a, stream);
+        case GEMM_CFG_128x64: return launch_cfg<128, 64, 4, 1>(a, stream);
+        case GEMM_CFG_64x64: return launch_cfg<64, 64, 2, 2>(a, stream);
+        case GEMM_CFG_128x128_K16: return launch_cfg<128, 128, 2, 2, 16>(a, stream);
+        case GEMM_CFG_128x128: return launch_cfg<128, 128, 2, 2>(a, stream);
+    }
+    set_error("launch_gemm: no configuration");
+    return -1;
+}
+
+// Workgroups per body of one configuration: the kernel's own predicate (GemmTile::body) over the kernel's own grid (n-tile fastest, times batch)
+template <int BM, int BN, int WM, int WN, int BKT = 32>
+static void count_bodies(const GemmArgs& a, long long (&n)[3]) {
+    using Tile = GemmTile<BM, BN, WM, WN, PRO_NONE, BKT>;
+    for (int m0 = 0; m0 < a.M; m0 += BM)
+        for (int n0 = 0; n0 < a.N; n0 += BN) n[Tile::body(a, m0, n0).body()] += a.batch;
+}
+
+int gemm_route(const GemmArgs& a, GemmRoute& r) {
+    r = GemmRoute{};
+    if (int rc = check_gemm_args(a)) return rc;
+    if (a.M <= 0 || a.N <= 0) return 0;   // nothing is launched: config stays -1
+    r.config = gemm_config(a);
+    switch (r.config) {
+        case GEMM_CFG_128x16: count_bodies<128, 16, 4, 1>(a, r.workgroups); break;
+        case GEMM_CFG_128x32: count_bodies<128, 32, 4, 1>(a, r.workgroups); break;
+        case GEMM_CFG_128x64: count_bodies<128, 64, 4, 1>(a, r.workgroups); break;
+        case GEMM_CFG_128x64_K16: count_bodies<128, 64, 4, 1, 16>(a, r.workgroups); break;
+        case GEMM_CFG_64x64: count_bodies<64, 64, 2, 2>(a, r.workgroups); break;
+        case GEMM_CFG_128x128_K16: count_bodies<128, 128, 2, 2, 16>(a, r.workgroups); break;
+        case GEMM_CFG_128x128: count_bodies<128, 128, 2, 2>(a, r.workgroups); break;
+    }
+    return 0;
 }
 
 }  // namespace at

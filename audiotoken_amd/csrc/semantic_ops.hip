@@ -21,6 +21,13 @@ int at_op_relpos_attention(const float* qkv, const float* attn_mask, const float
     return launch_relpos_attention(a, (hipStream_t)stream);
 }
 
+int at_op_attention_f32(const float* qkv, const float* attn_mask, const float* dist_emb80, float* ctx, int B, int T, int heads, at_stream_t stream) {
+    AT_REQUIRE(qkv && attn_mask && ctx && B >= 1 && T >= 1 && heads >= 1 && heads <= 64, "bad arguments");
+    AttnArgs a;
+    a.qkv = qkv; a.amask = attn_mask; a.dist_emb = dist_emb80; a.ctx = ctx; a.B = B; a.T = T; a.heads = heads; a.arith = 0;
+    return launch_relpos_attention(a, (hipStream_t)stream);
+}
+
 int at_op_relpos_attention_kvp(const float* qkv, const float* attn_mask, const float* dist_emb80, float dist_max_abs, float* ctx, int B, int T, int heads, int w8,
                                void* kv_workspace, size_t kv_workspace_bytes, int32_t* status_dev, at_stream_t stream) {
     AT_REQUIRE(qkv && attn_mask && ctx && kv_workspace && B >= 1 && T >= 1 && heads >= 1 && heads <= 64, "bad arguments");

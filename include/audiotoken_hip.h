@@ -504,7 +504,7 @@ int at_w2vbert_layer_status(at_w2vbert_t* h, int32_t* flags, int cap);
  * at_hubert_set_option moves one transformer layer to bf16x3 / f16x2. */
 int at_hubert_layer_status(at_hubert_t* h, int32_t* flags, int cap);
 
-/* Windowed fp32 GEMM: out[b][m][n] = act(alpha*(sum_kk A(b,m,kk)*W[n][kk] + bias[n])) (+ R[b][m][n]) with
+/* Windowed fp32 GEMM: out[b][m][n] = alpha*act(sum_kk A(b,m,kk)*W[n][kk] + bias[n]) (+ R[b][m][n]) with
  * A(b,m,kk) = pro(X[b][m*stride + kk/Cin - pad_left][kk%Cin]); rows outside [0,Tin) reflect (pad_mode=1) or are
  * zero (pad_mode=0). Covers conv1d (ref: encodec SConv1d), Linear and ConvTranspose1d-as-phases. */
 typedef struct at_gemm_desc {
@@ -521,6 +521,14 @@ typedef struct at_gemm_desc {
     const float* row_mask; /* optional [batch*M]: rows with mask 0 are written as zeros */
 } at_gemm_desc;
 int at_op_gemm(const at_gemm_desc* d, at_stream_t stream);
+/* The same call with the second A source filled in (ktaps == 1, K1 == Cin): A(b,m,kk) = pro(X[b][m][kk]) for kk < K1 and X2[b][m][kk - K1] (row stride
+ * ld2, clip stride x2_bstride, no prologue) for K1 <= kk < K — the SEANet residual block's fused shortcut. K1 and K - K1 must be multiples of 4. */
+int at_op_gemm_dual(const at_gemm_desc* d, const float* X2, int64_t x2_bstride, int ld2, int K1, at_stream_t stream);
+/* The route at_op_gemm / at_op_gemm_dual (X2 NULL = single source) would take, without launching anything (pure host code, no device needed):
+ * out[0] = tile configuration (0 128x16, 1 128x32, 2 128x64, 3 128x64 with K tile 16, 4 64x64, 5 128x128 with K tile 16, 6 128x128; -1 = nothing to
+ * launch), out[1..3] = workgroups over the whole grid (batch included) that take the general, the FAST and the TAP body (csrc/gemm_core.h: gemm_body).
+ * Returns the argument check's error code when the call would be refused. */
+int at_op_gemm_route(const at_gemm_desc* d, const float* X2, int64_t x2_bstride, int ld2, int K1, int32_t* out);
 
 /* Residual VQ search (ref: encodec ResidualVectorQuantizer.encode; formula SURVEY.md Appendix A.1):
  * x device float32 [rows][128]; codebooks device [n_q][1024][128]; e2 device [n_q][1024];
@@ -559,6 +567,10 @@ int at_op_layernorm(const float* x, const float* gamma, const float* beta, const
  * attn_mask [B*T] (1 = valid key), dist_emb80 [80][64] (73 rows used, rest zero) -> ctx [B*T][1024]. */
 int at_op_relpos_attention(const float* qkv, const float* attn_mask, const float* dist_emb80, float* ctx, int B, int T,
                            at_stream_t stream);
+
+/* The same attention on the fp32 matrix-core kernel (csrc/w2vbert_kernels.hip: relpos_attention_kernel), whatever the default arithmetic: what the fine
+ * stage launches at every layer. heads 1..64: qkv [B*T][3 * heads * 64], ctx [B*T][heads * 64]; dist_emb80 NULL = no rel-pos bias. */
+int at_op_attention_f32(const float* qkv, const float* attn_mask, const float* dist_emb80, float* ctx, int B, int T, int heads, at_stream_t stream);
 
 /* The same attention on the path the product runs (ref audiotoken/modeling_wav2vec2_bert.py:46-73; HF HubertAttention with dist_emb80 = NULL): k / v are
  * first written as the row-major fp16 pieces the fused q / k / v projection's epilogue produces and the distance embeddings as the fp16 pieces finalize()

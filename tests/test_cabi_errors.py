@@ -30,6 +30,25 @@ def test_null_handles_are_rejected_with_a_message():
     assert lib.at_encodec_workspace_bytes(None, 0, 0) == 0
 
 
+def test_gemm_dual_second_source_width_must_be_a_multiple_of_4():
+    """The general body fetches 16-byte chunks: a second source of 6 columns would have its last chunk read past the X2 row and the weight row.
+    The argument check refuses the call before anything is launched (status -1, message set), so this runs without a device; the addresses
+    are never dereferenced."""
+    lib = _cabi.load()
+    d = _cabi.GemmDesc()
+    d.X, d.x_bstride, d.Tin, d.Cin, d.ldx = 4096, 0, 64, 16, 16
+    d.ktaps, d.stride, d.pad_left, d.pad_mode = 1, 1, 0, 0
+    d.W, d.bias, d.C, d.c_bstride, d.ldc = 8192, 0, 12288, 0, 32
+    d.R, d.r_bstride, d.ldr = 0, 0, 32
+    d.M, d.N, d.K, d.batch, d.pro, d.epi, d.alpha = 64, 32, 16 + 6, 1, 0, 0, 1.0
+    assert lib.at_op_gemm_dual(C.byref(d), 16384, 0, 8, 16, None) == -1
+    assert "width of the second source must be a multiple of 4" in _cabi.last_error()
+    assert lib.at_op_gemm_dual(C.byref(d), None, 0, 8, 16, None) == -1 and "second source" in _cabi.last_error()
+    assert lib.at_op_gemm_dual(None, 16384, 0, 8, 16, None) == -1 and "null" in _cabi.last_error().lower()
+    assert lib.at_op_attention_f32(None, None, None, None, 1, 1, 16, None) == -1 and "bad arguments" in _cabi.last_error()
+    assert lib.at_op_attention_f32(4096, 4096, None, 4096, 1, 1, 65, None) == -1 and "bad arguments" in _cabi.last_error()
+
+
 @pytest.mark.gpu
 def test_encode_argument_validation(cuda_device):
     from audiotoken_amd.configs import AcousticEncoderConfig
