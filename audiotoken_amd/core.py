@@ -523,6 +523,29 @@ class AudioToken:
                                    top_k=top_k, fine_temperature=fine_temperature, seed=seed, uniforms=uniforms, fine_uniforms=fine_uniforms, top_p=top_p,
                                    min_p=min_p, keep_codes=keep_codes)
 
+    def audio_stream_pool(self, streams: int = 64, slots: int = 16, fine_slots: int = 4, window: Optional[int] = None, hop: Optional[int] = None,
+                          max_new_tokens: int = 1024, temperature: float = 0.8, top_k: int = 100, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                          fine_temperature: Optional[float] = 0.5, tick_tokens: Optional[int] = None, keep_codes: bool = False, return_logits: bool = False,
+                          voice=None):
+        """Up to ``streams`` live ``audio_stream()``s on one device state (``SemanticAudioStreamPool``, DESIGN.md §26): ``a = pool.open(seed=0)``;
+        ``pool.push({a: ids_a, b: ids_b}, flush=[c])`` returns ``{sid: float32 (1, 320 n)}`` on the CPU for every stream named; ``pool.flush([a])``;
+        ``pool.close(a)``; ``pool.stream(a)`` is the stream's record. A stream opened with seed ``s`` has the windows and draws of ``audio_stream(seed=s)``.
+        The streams share ``slots`` (1 to 64) GPT cache rows tick by tick, fine passes of up to ``fine_slots`` windows, and one decode stream pool. One call
+        is checked whole before anything is launched. Semantic tokenizers only; ``voice=`` is not built for streams."""
+        if self.tokenizer_name not in (Tokenizers.semantic_s, Tokenizers.semantic_m):
+            raise ValueError(f"to_audio maps semantic ids to audio; {self.tokenizer_name} has no semantic ids (its own decode is the way back)")
+        if voice is not None:
+            raise ValueError("audio_stream: voice= is not built for streams (the prompted schedule changes every window); use to_audio(long_form=True, voice=)")
+        from .semantic_decoder import check_truncation
+        from .semantic_pool import MAX_POOL_STREAMS, SemanticAudioStreamPool
+        check_truncation(top_p, min_p)
+        if not 1 <= int(streams) <= MAX_POOL_STREAMS:
+            raise ValueError(f"audio_stream_pool: streams must be 1 to {MAX_POOL_STREAMS}, got {streams}")
+        decode_pool = self._fine_audio().decode_stream_pool(slots=int(streams))
+        return SemanticAudioStreamPool(self._gpt(), self._fine(), decode_pool, streams=streams, slots=slots, fine_slots=fine_slots, window=window, hop=hop,
+                                       max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                                       fine_temperature=fine_temperature, tick_tokens=tick_tokens, keep_codes=keep_codes, return_logits=return_logits)
+
     def to_audio_batch_files(self, batch_size: int, outdir: os.PathLike, token_files: Optional[List[os.PathLike]] = None,
                              token_dir: Optional[Union[os.PathLike, Path]] = None, chunk_size: Optional[int] = None, num_workers: int = 12,
                              audio_format: str = "wav", rescale: bool = False, stream: bool = False, seed: int = 0, temperature: float = 0.8,

@@ -150,6 +150,73 @@ class FineStreamSchedule {
     int W_, H_;
 };
 
+// ---- the stream pool's scheduler: pure host code, shared by at_fine_pool_push and tools/audio_stream_pool_args.hip ---------------------------
+// One call serves n streams, each with its own FineStreamSchedule. A round is global: round g of the call is round g of every stream that still has one
+// (hand-over, the runnable windows, emit, shift). A stream's runnable windows of a round form a chain (window j + 1 reads what window j wrote), so they run
+// in waves: wave i holds the i-th runnable window of every stream that has one, in the call's order, in passes of up to fine_slots windows. Two windows of
+// one stream never share a pass. Everything is known from the counts: nothing is polled.
+constexpr int FINE_MAX_POOL_STREAMS = 1024;
+struct FinePoolPass {
+    int n = 0, wave = 0;
+    int stream[FINE_MAX_B], j[FINE_MAX_B], cell[FINE_MAX_B], rel[FINE_MAX_B];   // per window: its stream of the call, its index, its first cell in the stream's array, rel
+};
+class FinePoolSchedule {
+  public:
+    // the arrays must outlive the schedule; the caller has checked every argument
+    FinePoolSchedule(const int64_t* T_before, const int32_t* n_new, const int32_t* final, int n, int W, int fine_slots)
+        : n_(n), W_(W), slots_(fine_slots), rd_(n), live_(n, 0), T_(n) {
+        sched_.reserve(n);
+        for (int i = 0; i < n; ++i) {
+            sched_.emplace_back(T_before[i], n_new[i], final[i] != 0, W);
+            T_[i] = T_before[i] + n_new[i];
+        }
+    }
+    bool next_round() {
+        bool any = false;
+        for (int i = 0; i < n_; ++i) {
+            live_[i] = sched_[i].next(&rd_[i]) ? 1 : 0;
+            any = any || live_[i];
+        }
+        wave_ = 0;
+        at_ = 0;
+        if (any) ++n_rounds_;
+        return any;
+    }
+    const FineStreamRound* round(int i) const { return live_[i] ? &rd_[i] : nullptr; }
+    // the next pass of the round, or false when every window of it has run
+    bool next(FinePoolPass* p) {
+        *p = FinePoolPass();
+        for (;;) {
+            for (; at_ < n_ && p->n < slots_; ++at_) {
+                if (chain(at_) <= wave_) continue;
+                const FineStreamRound& rd = rd_[at_];
+                const int plain = rd.pad ? 1 : rd.n_win, H = W_ / 2, i = p->n++;
+                const bool last = wave_ >= plain;
+                p->stream[i] = at_;
+                p->j[i] = rd.j_first + wave_;
+                p->cell[i] = last ? (int)(T_[at_] - W_ - rd.first) : (int)((long long)(rd.j_first + wave_) * H - rd.first);
+                p->rel[i] = last ? rd.last_rel : 0;
+            }
+            if (p->n > 0) { p->wave = wave_; ++n_passes_; return true; }
+            bool more = false;
+            for (int i = 0; i < n_; ++i) more = more || chain(i) > wave_ + 1;
+            if (!more) return false;
+            ++wave_;
+            at_ = 0;
+        }
+    }
+    int rounds() const { return n_rounds_; }
+    int passes() const { return n_passes_; }
+
+  private:
+    int chain(int i) const { return live_[i] ? (rd_[i].pad ? 1 : rd_[i].n_win) + (rd_[i].last_window ? 1 : 0) : 0; }
+    int n_, W_, slots_, wave_ = 0, at_ = 0, n_rounds_ = 0, n_passes_ = 0;
+    std::vector<FineStreamSchedule> sched_;
+    std::vector<FineStreamRound> rd_;
+    std::vector<char> live_;
+    std::vector<long long> T_;
+};
+
 }  // namespace at
 
 struct at_fine : at::ModelHandle {  // device, finalized, staged, allocs

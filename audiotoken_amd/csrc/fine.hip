@@ -8,6 +8,8 @@
 //   fine_gather_kernel   the rows the head needs (positions >= rel of every window of the pass), where a window has rel > 0
 //   fine_sample_kernel   one wave per position over its 1024 logits: the argmax or the inverse-CDF draw, written straight into the work array
 //   fine_finish_kernel   the T cells after the history of the rows that leave a slot, as [8][T]
+// The stream and the stream pool share fine_pool_handover_kernel / fine_pool_emit_kernel / fine_pool_shift_kernel, which take
+// their work by table: a stream of its own is the one-piece case.
 // A call enqueues every window of every row without looking at the device: the host knows the schedule from the lengths. No float is added atomically.
 // Both generators are one function (generate) and one loop (run_passes) over the passes of FineQueueSchedule (fine.h): at_fine_generate is
 // the queue with a slot per row. A pass's six code books are run_codebooks, which the stream's windows use as well. The handle's plumbing
@@ -644,18 +646,36 @@ namespace {
 
 constexpr int HANDOVER_BAD_ID = 4;   // status bit 2
 
-// The GPT's new ids into the work array: thread t = cell t. A frame's two ids are one 8-byte load (interleaved; code book 0 carries `offset`, code book 1
-// offset + codebook_size), its cell two 16-byte stores: channels 0 and 1, and 1024 ("nothing yet") in channels 2 to 7. A frame with an id outside its code
-// book (or past the fine model's 1024 ids) is reported in bit 2 of *status and not written. Cells [n, n + n_pad) get 1024 in all 8 channels: the padding
-// of a row shorter than the window. ones: NULL, or the attention's key mask [W], written here by the call's first launch.
-__global__ __launch_bounds__(256) void fine_handover_kernel(const int2* ids, int n, int n_pad, int offset, int codebook_size, int* work, float* ones, int W, int* status) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ones && t < W) ones[t] = 1.0f;
-    if (t >= n + n_pad) return;
-    int4* cell = reinterpret_cast<int4*>(work + (size_t)t * FINE_CODES);
+// The stream's three kernels take their work by table, by value: up to FINE_POOL_CHUNK pieces a launch (blockIdx.y or blockIdx.x = the piece), as FineRows
+// goes to the init kernel. A stream of its own is the one-piece case; a pool names a piece per stream of the call.
+//   hand-over  The GPT's new ids into the work array: thread t of piece e = cell cell[e] + t. A frame's two ids are one 8-byte load (interleaved; code book 0
+//              carries `offset`, code book 1 offset + codebook_size), its cell two 16-byte stores: channels 0 and 1, and 1024 ("nothing yet") in channels 2
+//              to 7. A frame with an id outside its code book (or past the fine model's 1024 ids) is reported in bit 2 of *status and not written. The aux[e]
+//              cells behind the frames get 1024 in all 8 channels: the padding of a row shorter than the window.
+//   emit       The frames that just turned final, cells [cell[e], cell[e] + len[e]), as int64 columns from out[at[e]] on, planes `stride` apart: what
+//              AcousticDecodeStream.push takes on the device. Two 16-byte loads a frame, eight 8-byte stores that are contiguous across the wave.
+//   shift      cells [cell[e], cell[e] + len[e]) = the cells aux[e] further on: one workgroup a piece, every cell read before any is written.
+constexpr int FINE_POOL_CHUNK = 128;
+struct FinePieces {
+    int n;
+    int cell[FINE_POOL_CHUNK];   // the piece's first cell in the state's work arrays
+    int len[FINE_POOL_CHUNK];    // hand-over: frames; emit: frames; shift: cells kept
+    int aux[FINE_POOL_CHUNK];    // hand-over: cells of padding behind the frames; shift: cells dropped
+    int at[FINE_POOL_CHUNK];     // hand-over: the first id in ids; emit: the first element in out
+};
+static_assert(sizeof(FinePieces) + 64 <= 4096, "the pool kernels' arguments must stay under the launch limit");
+
+// ones: NULL, or the key masks of the call's windows [n_ones], written by the call's first launch
+__global__ __launch_bounds__(256) void fine_pool_handover_kernel(FinePieces p, const int* ids, int offset, int codebook_size, int* work, float* ones, int n_ones, int* status) {
+    const int e = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ones && e == 0 && t < n_ones) ones[t] = 1.0f;
+    if (e >= p.n) return;
+    const int n = p.len[e];
+    if (t >= n + p.aux[e]) return;
+    int4* cell = reinterpret_cast<int4*>(work + ((size_t)p.cell[e] + t) * FINE_CODES);
     int c0 = FINE_VOCAB, c1 = FINE_VOCAB;
     if (t < n) {
-        const int2 id = ids[t];
+        const int2 id = reinterpret_cast<const int2*>(ids + p.at[e])[t];
         const int top = min(codebook_size, FINE_VOCAB);
         c0 = id.x - offset;
         c1 = id.y - offset - codebook_size;
@@ -668,26 +688,27 @@ __global__ __launch_bounds__(256) void fine_handover_kernel(const int2* ids, int
     cell[1] = make_int4(FINE_VOCAB, FINE_VOCAB, FINE_VOCAB, FINE_VOCAB);
 }
 
-// The frames that just turned final, cells [cell0, cell0 + n) of the work array, as columns [col0, col0 + n) of out, int64 [8][stride]: what
-// AcousticDecodeStream.push takes on the device. Thread t = frame t: two 16-byte loads, eight 8-byte stores that are contiguous across the wave.
-__global__ __launch_bounds__(256) void fine_emit_kernel(const int* work, int cell0, int n, long long* out, int stride, int col0) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)cell0 + t) * FINE_CODES);
+// frame t of piece e goes to out[at[e] + ch * stride + t]
+__global__ __launch_bounds__(256) void fine_pool_emit_kernel(FinePieces p, const int* work, long long* out, int stride) {
+    const int e = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= p.len[e]) return;
+    const int4* cell = reinterpret_cast<const int4*>(work + ((size_t)p.cell[e] + t) * FINE_CODES);
     const int4 lo = cell[0], hi = cell[1];
     const int ids[FINE_CODES] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
-    for (int ch = 0; ch < FINE_CODES; ++ch) out[(size_t)ch * stride + col0 + t] = ids[ch];
+    for (int ch = 0; ch < FINE_CODES; ++ch) out[(size_t)p.at[e] + (size_t)ch * stride + t] = ids[ch];
 }
 
-// work cells [0, n) = cells [shift, shift + n): one workgroup, every cell read before any is written (n is at most 2 W <= 2048: two cells a thread)
-__global__ __launch_bounds__(1024) void fine_stream_shift_kernel(int* work, int shift, int n) {
+// len is at most 2 W <= 2048: two cells a thread
+__global__ __launch_bounds__(1024) void fine_pool_shift_kernel(FinePieces p, int* work) {
+    const int e = blockIdx.x, n = p.len[e];
+    int* base = work + (size_t)p.cell[e] * FINE_CODES;
     int4 v[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int t = threadIdx.x + 1024 * i;
         if (t < n) {
-            const int4* src = reinterpret_cast<const int4*>(work + ((size_t)shift + t) * FINE_CODES);
+            const int4* src = reinterpret_cast<const int4*>(base + ((size_t)p.aux[e] + t) * FINE_CODES);
             v[i][0] = src[0]; v[i][1] = src[1];
         }
     }
@@ -696,17 +717,21 @@ __global__ __launch_bounds__(1024) void fine_stream_shift_kernel(int* work, int 
     for (int i = 0; i < 2; ++i) {
         const int t = threadIdx.x + 1024 * i;
         if (t < n) {
-            int4* dst = reinterpret_cast<int4*>(work + (size_t)t * FINE_CODES);
+            int4* dst = reinterpret_cast<int4*>(base + (size_t)t * FINE_CODES);
             dst[0] = v[i][0]; dst[1] = v[i][1];
         }
     }
 }
 
+// one piece: n frames of ids into cells [0, n + n_pad) of work; ones: NULL, or the attention's key mask [W], written by the call's first launch
 int launch_handover(const int32_t* ids, int n, int n_pad, int offset, int codebook_size, int* work, float* ones, int W, int32_t* status, hipStream_t stream) {
     const int mask = ones ? W : 0, span = n + n_pad > mask ? n + n_pad : mask;
     if (span <= 0) return 0;
-    hipLaunchKernelGGL(fine_handover_kernel, dim3((span + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const int2*>(ids), n, n_pad, offset, codebook_size, work,
-                       ones, W, status);
+    FinePieces p{};
+    p.n = 1;
+    p.len[0] = n;
+    p.aux[0] = n_pad;
+    hipLaunchKernelGGL(fine_pool_handover_kernel, dim3((span + 255) / 256, 1), dim3(256), 0, stream, p, ids, offset, codebook_size, work, ones, mask, status);
     AT_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -800,13 +825,21 @@ int at_fine_stream_push(at_fine_t* h, void* state_dev, size_t state_bytes, int64
             if (int rc = run_window((int)(T - W - rd.first), rd.j_first + rd.n_win, rd.last_rel)) return rc;
         const int n = (int)(rd.emit_to - rd.emit_from);
         if (n > 0) {
-            hipLaunchKernelGGL(fine_emit_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, s.work, (int)(rd.emit_from - rd.first), n,
-                               reinterpret_cast<long long*>(emit_dev), emit_stride, col);
+            FinePieces p{};
+            p.n = 1;
+            p.cell[0] = (int)(rd.emit_from - rd.first);
+            p.len[0] = n;
+            p.at[0] = col;
+            hipLaunchKernelGGL(fine_pool_emit_kernel, dim3((n + 255) / 256, 1), dim3(256), 0, stream, p, s.work, reinterpret_cast<long long*>(emit_dev), emit_stride);
             AT_CHECK_HIP(hipGetLastError());
             col += n;
         }
         if (rd.shift > 0) {
-            hipLaunchKernelGGL(fine_stream_shift_kernel, dim3(1), dim3(1024), 0, stream, s.work, rd.shift, rd.held + rd.take - rd.shift);
+            FinePieces p{};
+            p.n = 1;
+            p.aux[0] = rd.shift;
+            p.len[0] = rd.held + rd.take - rd.shift;
+            hipLaunchKernelGGL(fine_pool_shift_kernel, dim3(1), dim3(1024), 0, stream, p, s.work);
             AT_CHECK_HIP(hipGetLastError());
         }
     }
@@ -814,6 +847,178 @@ int at_fine_stream_push(at_fine_t* h, void* state_dev, size_t state_bytes, int64
     pos[1] = final;
     *n_emitted = (int)emitted;
     if (windows_run) *windows_run = n_win;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- the stream pool: many rows whose coarse frames arrive in pushes share the passes ----------------------------------------------
+namespace {
+
+// per stream 2 W cells [8]; shared, the activations of fine_slots windows
+FineState carve_pool(void* base, int streams, int fine_slots, int W, int E) {
+    FineState s{};
+    StateCarver c(base);
+    const size_t R = (size_t)fine_slots * W;
+    s.Lmax = fine_stream_cells(W);
+    s.work = c.take<int>((size_t)streams * s.Lmax * FINE_CODES);
+    s.ones = c.take<float>(R);
+    s.x = c.take<float>(R * E);
+    s.xn = c.take<float>(R * E);
+    s.qkv = c.take<float>(R * 3 * E);
+    s.h = c.take<float>(R * 4 * E);
+    s.logits = c.take<float>(R * FINE_VOCAB);
+    s.bytes = c.off;
+    return s;
+}
+
+// the pieces gathered for one kernel, launched FINE_POOL_CHUNK at a time
+struct FinePoolLaunch {
+    std::vector<FinePieces> chunks;
+    int span = 0;   // the longest piece, in threads
+    void add(long long cell, int len, int aux, long long at, int threads) {
+        if (chunks.empty() || chunks.back().n == FINE_POOL_CHUNK) chunks.push_back(FinePieces{});
+        FinePieces& c = chunks.back();
+        c.cell[c.n] = (int)cell; c.len[c.n] = len; c.aux[c.n] = aux; c.at[c.n] = (int)at; ++c.n;
+        span = threads > span ? threads : span;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+size_t at_fine_pool_state_bytes(const at_fine_t* h, int streams, int fine_slots) {
+    if (!(h && h->finalized)) { set_error("at_fine_pool_state_bytes: the model is not finalized"); return 0; }
+    if (!(streams >= 1 && streams <= FINE_MAX_POOL_STREAMS)) { set_error("at_fine_pool_state_bytes: streams must be 1 to 1024"); return 0; }
+    if (!(fine_slots >= 1 && fine_slots <= FINE_MAX_B)) { set_error("at_fine_pool_state_bytes: fine_slots must be 1 to 64"); return 0; }
+    return carve_pool(nullptr, streams, fine_slots, h->block, h->embd).bytes;
+}
+
+int at_fine_pool_push(at_fine_t* h, void* state_dev, size_t state_bytes, int streams, int fine_slots, int64_t* pos, int n, const int32_t* place,
+                      const int32_t* ids_dev, const int64_t* id_off, const int32_t* n_frames, const int32_t* final, int acoustic_offset, int codebook_size,
+                      float temperature, int greedy, const float* uniforms_dev, const int32_t* u_cell0, const int32_t* u_win0, const int32_t* u_windows,
+                      int64_t* emit_dev, int emit_stride, int32_t* n_emitted, int32_t* windows_run, int32_t* trace, int trace_cap, int32_t* n_passes,
+                      at_stream_t stream_, int32_t* status_dev) {
+    const char* who = "at_fine_pool_push";
+    AT_REQUIRE(h && h->finalized, "the model is not finalized");
+    AT_REQUIRE(streams >= 1 && streams <= FINE_MAX_POOL_STREAMS, "streams must be 1 to 1024");
+    AT_REQUIRE(fine_slots >= 1 && fine_slots <= FINE_MAX_B, "fine_slots must be 1 to 64");
+    AT_REQUIRE(state_dev != nullptr, "null state");
+    AT_REQUIRE(n >= 0 && n <= streams, "n (the call's streams) must be 0 to streams");
+    AT_REQUIRE(pos != nullptr, "null pointer");
+    AT_REQUIRE(n == 0 || (place && id_off && n_frames && final && u_cell0 && u_win0 && u_windows && n_emitted), "null pointer");
+    AT_REQUIRE(greedy == 0 || greedy == 1, "greedy must be 0 or 1");
+    AT_REQUIRE(greedy || (std::isfinite(temperature) && temperature > 0.0f), "temperature must be a positive finite number");
+    AT_REQUIRE(trace_cap >= 0 && (trace != nullptr || trace_cap == 0), "trace_cap must be 0 without a trace and never negative");
+    AT_REQUIRE(emit_stride >= 0, "emit_stride must not be negative");
+    AT_REQUIRE((int64_t)n * FINE_CODES * emit_stride <= INT32_MAX, "n * 8 * emit_stride must fit 31 bits: the pieces are addressed by int");
+    if (int rc = check_handover(ids_dev, 0, acoustic_offset, codebook_size)) return rc;
+    const int W = h->block;
+    // ---- every stream of the call, checked before any is changed: its place, its record, and a dry run of its schedule against the caller's arrays
+    std::vector<char> named((size_t)streams, 0);
+    std::vector<int64_t> T_before((size_t)n);
+    std::vector<long long> emitted((size_t)n, 0);
+    std::vector<int32_t> ran((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        const std::string at = std::string(who) + ": stream " + std::to_string(i) + " of the call: ";
+        if (place[i] < 0 || place[i] >= streams || named[place[i]]) { set_error(at + "its place must be 0 to streams - 1 and named once"); return -1; }
+        named[place[i]] = 1;
+        const int64_t* ps = pos + 2 * (size_t)place[i];
+        if (final[i] != 0 && final[i] != 1) { set_error(at + "final must be 0 or 1"); return -1; }
+        if (n_frames[i] < 0 || (n_frames[i] > 0 && ids_dev == nullptr)) { set_error(at + "n_frames must not be negative, and frames need a pointer"); return -1; }
+        if (id_off[i] < 0 || (id_off[i] & 1)) { set_error(at + "id_off must be even and not negative: a frame is one 8-byte load"); return -1; }
+        if (id_off[i] + 2 * (int64_t)n_frames[i] > INT32_MAX) { set_error(at + "its ids must lie below 2^31 in ids_dev"); return -1; }
+        if (ps[1] != 0) { set_error(at + "the stream is finished: a push after the final call"); return -1; }
+        if (ps[0] < 0 || ps[0] + n_frames[i] > FINE_MAX_T) { set_error(at + "a stream takes at most 262144 frames"); return -1; }
+        if (final[i] && ps[0] + n_frames[i] < 1) { set_error(at + "a final call with nothing pushed"); return -1; }
+        if (u_cell0[i] < 0 || u_win0[i] < 0 || u_windows[i] < 0) { set_error(at + "u_cell0, u_win0 and u_windows must not be negative"); return -1; }
+        T_before[i] = ps[0];
+        int j_lo = -1, j_hi = -1;
+        FineStreamSchedule dry(ps[0], n_frames[i], final[i] != 0, W);
+        FineStreamRound rd;
+        while (dry.next(&rd)) {
+            const int m = rd.n_win + (rd.last_window ? 1 : 0);
+            if (m > 0) { if (j_lo < 0) j_lo = rd.j_first; j_hi = rd.j_first + m; }
+            ran[i] += m;
+            emitted[i] += rd.emit_to - rd.emit_from;
+        }
+        if (!(greedy || ran[i] == 0 || (uniforms_dev != nullptr && j_lo >= u_win0[i] && j_hi <= u_win0[i] + u_windows[i]))) {
+            set_error(at + "the uniforms do not cover the windows this call runs");
+            return -1;
+        }
+        if (!(emitted[i] == 0 || (emit_dev != nullptr && emitted[i] <= emit_stride))) { set_error(at + "emit_dev must hold the frames that turn final in this call"); return -1; }
+    }
+    const FineState s = carve_pool(state_dev, streams, fine_slots, W, h->embd);
+    AT_REQUIRE(state_bytes >= s.bytes, "state too small: at_fine_pool_state_bytes(h, streams, fine_slots)");
+    if (n_passes) *n_passes = 0;
+    if (n == 0) return 0;
+    // ---- nothing above touched the device or the host record
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    hipStream_t stream = (hipStream_t)stream_;
+    const FineSampleArgs sa = sample_args(s, W, greedy, temperature, uniforms_dev, nullptr, nullptr);
+    FinePoolSchedule schedule(T_before.data(), n_frames, final, n, W, fine_slots);
+    std::vector<int> taken((size_t)n, 0), col((size_t)n, 0);
+    bool first = true;
+    while (schedule.next_round()) {
+        FinePoolLaunch handover, emit, shift;
+        for (int i = 0; i < n; ++i) {
+            const FineStreamRound* rd = schedule.round(i);
+            if (!rd) continue;
+            const long long base = (long long)place[i] * s.Lmax;
+            if (rd->take > 0 || rd->pad > 0) handover.add(base + rd->held, rd->take, rd->pad, id_off[i] + 2 * (long long)taken[i], rd->take + rd->pad);
+            taken[i] += rd->take;
+            const int m = (int)(rd->emit_to - rd->emit_from);
+            if (m > 0) {
+                emit.add(base + (rd->emit_from - rd->first), m, 0, (long long)i * FINE_CODES * emit_stride + col[i], m);
+                col[i] += m;
+            }
+            if (rd->shift > 0) shift.add(base, rd->held + rd->take - rd->shift, rd->shift, 0, 0);
+        }
+        // the hand-over; the call's first launch also writes the key masks, so it happens even when no stream hands anything over
+        if (first && handover.chunks.empty()) handover.chunks.push_back(FinePieces{});
+        for (const FinePieces& c : handover.chunks) {
+            const int n_ones = first ? fine_slots * W : 0, span = handover.span > n_ones ? handover.span : n_ones;
+            hipLaunchKernelGGL(fine_pool_handover_kernel, dim3((span + 255) / 256, c.n > 0 ? c.n : 1), dim3(256), 0, stream, c, ids_dev, acoustic_offset, codebook_size,
+                               s.work, first ? s.ones : nullptr, n_ones, status_dev);
+            AT_CHECK_HIP(hipGetLastError());
+            first = false;
+        }
+        FinePoolPass ps;
+        while (schedule.next(&ps)) {
+            FinePass p{};
+            p.n = ps.n;
+            for (int w = 0; w < ps.n; ++w) {
+                const int i = ps.stream[w];
+                p.cell0[w] = (int)((long long)place[i] * s.Lmax + ps.cell[w]);
+                p.draw[w] = u_cell0[i] + ps.j[w] - u_win0[i];
+                p.rel[w] = ps.rel[w];
+                p.head_off[w + 1] = p.head_off[w] + W - ps.rel[w];
+            }
+            if (int rc = run_codebooks(h, s, p, sa, stream)) return rc;
+            const int at = schedule.passes() - 1;
+            if (at < trace_cap) {   // a trace too small loses its tail, the run goes on
+                int32_t* row = trace + 3 * (size_t)at;
+                row[0] = schedule.rounds() - 1; row[1] = ps.wave; row[2] = ps.n;
+            }
+        }
+        for (const FinePieces& c : emit.chunks) {
+            hipLaunchKernelGGL(fine_pool_emit_kernel, dim3((emit.span + 255) / 256, c.n), dim3(256), 0, stream, c, s.work, reinterpret_cast<long long*>(emit_dev), emit_stride);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+        for (const FinePieces& c : shift.chunks) {
+            hipLaunchKernelGGL(fine_pool_shift_kernel, dim3(c.n), dim3(1024), 0, stream, c, s.work);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        pos[2 * (size_t)place[i]] += n_frames[i];
+        pos[2 * (size_t)place[i] + 1] = final[i];
+        n_emitted[i] = (int)emitted[i];
+        if (windows_run) windows_run[i] = ran[i];
+    }
+    if (n_passes) *n_passes = schedule.passes();
     return 0;
 }
 

@@ -209,6 +209,125 @@ class GptStreamSchedule {
     int S_, H_;
 };
 
+// ---- the stream pool's scheduler: pure host code, shared by at_gpt_pool_push and tools/audio_stream_pool_args.hip ---------------------------
+// One call serves n streams, in ascending stream id; each has its own GptStreamSchedule. A round is global: round g of the call is round g of every stream
+// that still has one (copy-in, then the round's ticks, then the shift). In a round a stream's windows form a chain (its non-final windows in order, then the
+// final one when the stream is flushed and this is its last round), and the chains are 20's sources: waiting streams take free cache rows in ascending
+// stream id, every running row steps, windows are admitted in slot order while the tick's list stays within tick_tokens, and a row whose stream's chain is
+// complete is handed on. A round ends when every chain of it is complete: the shift must not overtake a window that still reads the ring, so no row is
+// held across a round's end. The flags are polled every GPT_CHECK_EVERY ticks of the call while some row is in a final window, and never otherwise.
+constexpr int GPT_MAX_POOL_STREAMS = 1024;
+struct GptPoolTick : GptQueueTick {
+    int src_pos[GPT_MAX_B];   // start j: the source position of its stream's ring's first id in this round (k_first * H)
+};
+class GptPoolSchedule {
+  public:
+    // the arrays must outlive the schedule; every argument has been validated by the caller (tick_tokens >= slots + the longest prompt)
+    GptPoolSchedule(const int64_t* n_before, const int32_t* n_new, const int32_t* final, int n, int S, int H, int r, int max_new, int block, int slots, int tick_tokens)
+        : n_(n), S_(S), H_(H), r_(r), max_new_(max_new), block_(block), slots_(slots), tick_tokens_(tick_tokens), rd_(n), live_(n, 0), placement_((size_t)n * 3, -1) {
+        sched_.reserve(n);
+        for (int i = 0; i < n; ++i) sched_.emplace_back(n_before[i], n_new[i], final[i] != 0, S, H);
+        for (int j = 0; j < GPT_MAX_B; ++j) slot_[j] = Slot{};
+    }
+    // The next round, or false when no stream has one left. round(i) is stream i's part of it, NULL when it has none.
+    bool next_round() {
+        bool any = false;
+        for (int i = 0; i < n_; ++i) {
+            live_[i] = sched_[i].next(&rd_[i]) ? 1 : 0;
+            any = any || live_[i];
+        }
+        next_src_ = 0;
+        if (any) ++n_rounds_;
+        return any;
+    }
+    const GptStreamRound* round(int i) const { return live_[i] ? &rd_[i] : nullptr; }
+    // The next tick of the round, or false when every chain of the round is complete
+    bool next(GptPoolTick* t) {
+        *t = GptPoolTick{};
+        tick_ = n_ticks_;
+        bool any = false;
+        for (int j = 0; j < slots_; ++j) {
+            Slot& s = slot_[j];
+            if (s.src < 0) {
+                while (next_src_ < n_ && chain(next_src_) == 0) ++next_src_;
+                if (next_src_ < n_) {
+                    s = Slot{};
+                    s.src = next_src_++;
+                    placement_[3 * (size_t)s.src] = j;
+                }
+            }
+            any = any || s.src >= 0;
+        }
+        if (!any) return false;
+        for (int j = 0; j < slots_; ++j)
+            if (slot_[j].src >= 0 && slot_[j].running) t->step_slot[t->n_step++] = j;
+        for (int j = 0; j < slots_; ++j) {
+            Slot& s = slot_[j];
+            if (s.src < 0 || s.running) continue;
+            const GptStreamRound& rd = rd_[s.src];
+            const bool last = s.w == rd.n_win;   // past the non-final windows: the final one
+            const int k = rd.k_first + s.w;
+            const GptWindow w = gpt_window(last ? k * H_ + rd.final_ids : k * H_ + S_ + 1, k, S_, H_, r_, max_new_, block_);
+            if (t->tokens() + w.P > tick_tokens_) break;   // it waits, and so does every slot after it
+            t->src_pos[t->n_start] = rd.k_first * H_;
+            t->start[t->n_start++] = GptQueueStart{j, s.src, k, last ? 1 : 0, w.n_ids, w.P};
+            t->prefill_tokens += w.P;
+            s.running = true;
+            s.final_window = last;
+            s.budget = w.budget;
+            s.t = 0;
+            if (placement_[3 * (size_t)s.src + 1] < 0) placement_[3 * (size_t)s.src + 1] = tick_;
+        }
+        bool in_final = false;
+        auto sampled = [&](int j) {
+            Slot& s = slot_[j];
+            if (++s.t < s.budget) { in_final = in_final || s.final_window; return; }
+            s.running = false;
+            if (++s.w >= chain(s.src)) retire(j);   // the chain is complete: the row is handed on
+        };
+        for (int i = 0; i < t->n_step; ++i) sampled(t->step_slot[i]);
+        for (int i = 0; i < t->n_start; ++i) sampled(t->start[i].slot);
+        ++n_ticks_;
+        t->poll = in_final && n_ticks_ % GPT_CHECK_EVERY == 0;
+        return true;
+    }
+    // after a tick with poll set: done[j] of every slot as the device has it now
+    void seen(const int32_t* done) {
+        for (int j = 0; j < slots_; ++j)
+            if (slot_[j].src >= 0 && slot_[j].running && slot_[j].final_window && done[j] != GPT_RUNNING) retire(j);
+    }
+    // the dry run's stand-in for the device: the flag of a slot whose final window ends after final_steps[stream] sampler launches
+    void seen_by_steps(const int32_t* final_steps) {
+        int32_t done[GPT_MAX_B];
+        for (int j = 0; j < slots_; ++j) {
+            const Slot& s = slot_[j];
+            done[j] = s.src >= 0 && s.running && s.final_window && s.t >= final_steps[s.src] ? GPT_FINISH_STOP : GPT_RUNNING;
+        }
+        seen(done);
+    }
+    int ticks() const { return n_ticks_; }
+    int rounds() const { return n_rounds_; }
+    const std::vector<int32_t>& placement() const { return placement_; }   // [n][3]: the slot of its last chain, its first tick, its last tick seen (-1: no window)
+
+  private:
+    struct Slot {
+        int src = -1, w = 0, t = 0, budget = 0;   // w: the window's index in the stream's chain of this round
+        bool running = false, final_window = false;
+    };
+    int chain(int i) const { return live_[i] ? rd_[i].n_win + (rd_[i].final_window ? 1 : 0) : 0; }
+    void retire(int j) {
+        placement_[3 * (size_t)slot_[j].src + 2] = tick_;
+        slot_[j] = Slot{};
+    }
+    int n_, S_, H_, r_, max_new_, block_, slots_, tick_tokens_;
+    int next_src_ = 0, n_ticks_ = 0, n_rounds_ = 0, tick_ = 0;
+    std::vector<GptStreamSchedule> sched_;
+    std::vector<GptStreamRound> rd_;
+    std::vector<char> live_;
+    Slot slot_[GPT_MAX_B];
+    std::vector<int32_t> placement_;
+};
+
 struct GptLayer {
     const float *ln1 = nullptr, *qkv = nullptr, *proj = nullptr, *ln2 = nullptr, *fc = nullptr, *fc_proj = nullptr;
 };

@@ -6,6 +6,7 @@
 //   at_gpt_generate_long   lockstep passes: window k of every row that has one begins, then those rows step
 //   at_gpt_generate_queue  GptQueueSchedule's ticks: any mix of rows that step and windows that begin
 //   at_gpt_stream_push     one source whose ids arrive in pushes: GptStreamSchedule's rounds of windows
+//   at_gpt_pool_push       many such sources in one call: GptPoolSchedule's rounds, each round the queue's ticks over the streams' windows
 // Nothing waits for the host between those looks: the rows' lengths, last tokens, step counters and finish flags live on the device.
 // The host side: the handle's plumbing and the state carver are model_handle.h's; the windowed entry points fill one GenRequest, which generate_long and
 // generate_queue take and check_request checks; the lockstep generators' step loop is run_steps (at_gpt_generate, a pass of the long form, a stream window).
@@ -69,6 +70,9 @@ struct TickPlan {
     unsigned short pv[GPT_MAX_B];         //          after a voice prompt of pv[j] ids (0: none),
     short entry[GPT_MAX_B];               //          entry[j] of the prompt table
     unsigned long long final_mask;        // bit j: start j is its source's last window
+    // Per-row origins, all 0 outside a stream pool: start j's source id c is q.src[src[j] * src_stride + src_org[j] + c], and element 0
+    // of its row of out_ids (and logits_out) and of its row of the uniforms lie at stream positions out_org[j] and u_org[j]
+    int src_org[GPT_MAX_B], out_org[GPT_MAX_B], u_org[GPT_MAX_B];
     void start(int slot_, int src_, int k_, int P, bool final_window, int pv_ = 0, int entry_ = 0) {
         const int j = n_start++;
         if (j == 0) off[0] = steps.n;
@@ -95,6 +99,8 @@ TickPlan lockstep_steps(int B) {
 // A start with a voice prompt (p.pv[j] ids of table entry p.entry[j]) walks the concatenated source: index c below pv is the prompt's id,
 // above it src[c - pv]; a carry id at stream position sp below r pv is the prompt's code (sp & 1 its code book, sp >> 1 its frame; outside
 // [0, codebook_size) clamped, bit 1 of *status), above it the row's own out_ids[sp - r pv]. The sampler's base is the result position.
+// A start's origins (p.src_org, p.out_org, p.u_org) move where its row's source ids, output and draws begin; they are 0 everywhere but in a
+// stream pool.
 static_assert(sizeof(TickPlan) + sizeof(Rules) + sizeof(GptState) + 4 * sizeof(void*) <= 4096, "gpt_begin_kernel's arguments must stay under the launch limit");
 __global__ void gpt_begin_kernel(TickPlan p, Rules q, GptState s, const int* out_ids, int out_stride, int* out_len, int* finish) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x, i = p.steps.n + t;
@@ -106,7 +112,7 @@ __global__ void gpt_begin_kernel(TickPlan p, Rules q, GptState s, const int* out
         int id;
         if (pos < n_src) {
             const int c = k * q.H + pos;
-            id = c < pv ? q.vp_sem[(size_t)p.entry[j] * q.vp_stride + c] : q.src[(size_t)b * q.src_stride + c - pv];
+            id = c < pv ? q.vp_sem[(size_t)p.entry[j] * q.vp_stride + c] : q.src[(int64_t)b * q.src_stride + p.src_org[j] + c - pv];
             if (!q.raw) {
                 if (id < 0 || id >= q.semantic_vocab) {
                     if (q.status) atomicOr(q.status, 1);
@@ -126,7 +132,7 @@ __global__ void gpt_begin_kernel(TickPlan p, Rules q, GptState s, const int* out
                 }
                 id += q.acoustic_offset + (sp & 1) * q.codebook_size;
             } else {
-                id = out_ids[(size_t)b * out_stride + sp - q.r * pv];
+                id = out_ids[(int64_t)b * out_stride + sp - q.r * pv - p.out_org[j]];
             }
         }
         s.tok_row[i] = p.slot[j];
@@ -149,6 +155,8 @@ __global__ void gpt_begin_kernel(TickPlan p, Rules q, GptState s, const int* out
         w.budget = last ? min(q.max_new, q.block - P) : q.r * q.S - carry;
         w.stop_token = last ? q.stop_token : -1;
         w.final_window = last ? 1 : 0;
+        w.out_org = p.out_org[t];
+        w.u_org = p.u_org[t];
         w.allow[0] = last ? q.last[0] : q.mid[0];
         w.allow[1] = last ? q.last[1] : q.mid[1];
         s.rows[slot] = w;
@@ -747,6 +755,228 @@ int at_gpt_stream_push(at_gpt_t* h, void* state_dev, size_t state_bytes, int64_t
     pos[0] += n_new;
     pos[1] = final;
     if (windows_run) *windows_run = ran;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- the stream pool: many streams whose ids arrive in pushes share the cache rows and the ticks --------------------------------------
+namespace {
+
+// Behind the queue's state (slots cache rows, tick_tokens token rows), per stream: its source ring (2 S ids) and its carry. Nothing else is kept per stream.
+struct GptPoolState {
+    GptState g;
+    int *src, *carry;   // [streams][2 S], [streams][r (S - H) + 1]
+    int carry_stride;
+    size_t bytes;
+};
+GptPoolState carve_pool(void* base, const at_gpt* h, int streams, int slots, int max_len, int tick_tokens, int S, int H, int r) {
+    GptPoolState st{};
+    st.g = carve_state(base, slots, max_len, tick_tokens, h->vocab, h->n_layer);
+    StateCarver c(base, st.g.bytes);
+    st.carry_stride = r * (S - H) + 1;
+    st.src = c.take<int>((size_t)streams * 2 * S);
+    st.carry = c.take<int>((size_t)streams * st.carry_stride);
+    st.bytes = c.off;
+    return st;
+}
+
+// Up to GPT_POOL_CHUNK streams' pieces of one launch, by value: no table on the device that could disagree with the host's record
+constexpr int GPT_POOL_CHUNK = 128;
+struct PoolPieces {
+    int n;
+    int dst[GPT_POOL_CHUNK], src[GPT_POOL_CHUNK], len[GPT_POOL_CHUNK];   // piece e: len[e] ids from index src[e] of one array to index dst[e] of another (or, the shift, the same)
+    void add(int64_t d, int64_t s, int l) { dst[n] = (int)d; src[n] = (int)s; len[n] = l; ++n; }
+};
+// to[dst[e] + t] = from[src[e] + t]: the copy-in behind each ring's held ids, and the carries into and out of the call's pieces. The two arrays are distinct.
+__global__ __launch_bounds__(256) void gpt_pool_copy_kernel(PoolPieces p, int* to, const int* from) {
+    const int e = blockIdx.x;
+    for (int t = threadIdx.x; t < p.len[e]; t += 256) to[p.dst[e] + t] = from[p.src[e] + t];
+}
+// ring e: buf[dst[e] + t] = buf[src[e] + t] for t < len[e] <= 2 S <= 1024: one workgroup a ring, every id read before any is written
+__global__ __launch_bounds__(1024) void gpt_pool_shift_kernel(PoolPieces p, int* buf) {
+    const int e = blockIdx.x, t = threadIdx.x, n = p.len[e];
+    const int v = t < n ? buf[p.src[e] + t] : 0;
+    __syncthreads();
+    if (t < n) buf[p.dst[e] + t] = v;
+}
+// the pieces gathered for one kernel, launched GPT_POOL_CHUNK at a time
+struct PoolLaunch {
+    std::vector<PoolPieces> chunks;
+    void add(int64_t d, int64_t s, int l) {
+        if (l <= 0) return;
+        if (chunks.empty() || chunks.back().n == GPT_POOL_CHUNK) chunks.push_back(PoolPieces{});
+        chunks.back().add(d, s, l);
+    }
+    int copy(int* to, const int* from, hipStream_t stream) const {
+        for (const PoolPieces& c : chunks) {
+            hipLaunchKernelGGL(gpt_pool_copy_kernel, dim3(c.n), dim3(256), 0, stream, c, to, from);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+        return 0;
+    }
+    int shift(int* buf, hipStream_t stream) const {
+        for (const PoolPieces& c : chunks) {
+            hipLaunchKernelGGL(gpt_pool_shift_kernel, dim3(c.n), dim3(1024), 0, stream, c, buf);
+            AT_CHECK_HIP(hipGetLastError());
+        }
+        return 0;
+    }
+};
+
+int check_pool_capacity(const char* who, const at_gpt* h, int streams, int slots, int max_len, int tick_tokens, int S, int H, int r, int max_new) {
+    const std::string w(who);
+    if (!(h && h->finalized)) { set_error(w + ": the model is not finalized"); return -1; }
+    if (!(streams >= 1 && streams <= GPT_MAX_POOL_STREAMS)) { set_error(w + ": streams must be 1 to 1024"); return -1; }
+    if (!(slots >= 1 && slots <= GPT_MAX_B)) { set_error(w + ": slots must be 1 to 64"); return -1; }
+    if (check_geometry(h, Geometry{S, H, r})) return -1;
+    // a non-final window fills S + 1 + r S positions, a final one its prompt and at most max_new more (max_new < 0: the size query, which cannot know it)
+    const int final_len = S + 1 + r * (S - H) + (max_new < 0 ? 0 : max_new);
+    const int need = std::max(S + 1 + r * S, std::min(h->block, final_len));
+    if (!(max_len >= need && max_len <= h->block)) { set_error(w + ": max_len must hold the longest window with its new ids and not exceed the block size"); return -1; }
+    if (!(tick_tokens >= slots + max_len && tick_tokens <= GPT_MAX_TICK_TOKENS)) {
+        set_error(w + ": tick_tokens must be slots + max_len to " + std::to_string(GPT_MAX_TICK_TOKENS));
+        return -1;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t at_gpt_pool_state_bytes(const at_gpt_t* h, int streams, int slots, int max_len, int tick_tokens, int S, int H, int r) {
+    if (check_pool_capacity("at_gpt_pool_state_bytes", h, streams, slots, max_len, tick_tokens, S, H, r, -1)) return 0;
+    return carve_pool(nullptr, h, streams, slots, max_len, tick_tokens, S, H, r).bytes;
+}
+
+int at_gpt_pool_push(at_gpt_t* h, void* state_dev, size_t state_bytes, int streams, int slots, int max_len, int tick_tokens, int64_t* pos, int n,
+                     const int32_t* place, const int32_t* ids_dev, const int32_t* n_new, const int32_t* final, int S, int H, int r, int semantic_offset,
+                     int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                     const float* uniforms_dev, int u_stride, const int64_t* u_pos0, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
+                     int32_t* finish_dev, float* logits_out_dev, int32_t* windows_run, int32_t* trace, int trace_cap, int32_t* n_ticks, int32_t* n_rounds,
+                     int32_t* placement, at_stream_t stream_, int32_t* status_dev) {
+    const char* who = "at_gpt_pool_push";
+    AT_REQUIRE(max_new >= 1 && max_new <= GPT_MAX_BLOCK, "max_new must be 1 to 1024");
+    if (int rc = check_pool_capacity(who, h, streams, slots, max_len, tick_tokens, S, H, r, max_new)) return rc;
+    AT_REQUIRE(state_dev != nullptr, "null state");
+    AT_REQUIRE(n >= 0 && n <= streams, "n (the call's streams) must be 0 to streams");
+    AT_REQUIRE(pos != nullptr, "null pointer");
+    AT_REQUIRE(n == 0 || (place && n_new && final && u_pos0 && uniforms_dev && out_ids_dev && out_len_dev && finish_dev), "null pointer");
+    AT_REQUIRE(trace_cap >= 0 && (trace != nullptr || trace_cap == 0), "trace_cap must be 0 without a trace and never negative");
+    AT_REQUIRE(u_stride >= 0 && out_stride >= 0, "u_stride and out_stride must not be negative");
+    AT_REQUIRE((int64_t)n * out_stride <= INT32_MAX, "n * out_stride must fit 31 bits: the pieces and the origins are addressed by int");
+    Rules q{};
+    GenRequest rq{who, h, {ids_dev, 1, nullptr, n}, {S, H, r}, {semantic_offset, semantic_vocab, infer_token, acoustic_offset, codebook_size, stop_token},
+                  {max_new, temperature, top_k, uniforms_dev, u_stride}, {out_ids_dev, out_stride, out_len_dev, finish_dev, logits_out_dev}, {state_dev, state_bytes, max_len},
+                  stream_, status_dev};
+    if (int rc = check_long_rules(rq, &q)) return rc;
+    // ---- every stream of the call, checked before any is changed: its place, its record, and what its windows need of the caller's arrays
+    const int block = h->block, carry = r * (S - H);
+    std::vector<char> named((size_t)streams, 0);
+    std::vector<int64_t> n_before((size_t)n), p_base((size_t)n);
+    std::vector<int> k0((size_t)n), k1((size_t)n);
+    int64_t total_new = 0;
+    for (int i = 0; i < n; ++i) {
+        const std::string at = std::string(who) + ": stream " + std::to_string(i) + " of the call: ";
+        if (place[i] < 0 || place[i] >= streams || named[place[i]]) { set_error(at + "its place must be 0 to streams - 1 and named once"); return -1; }
+        named[place[i]] = 1;
+        const int64_t* ps = pos + 2 * (size_t)place[i];
+        if (final[i] != 0 && final[i] != 1) { set_error(at + "final must be 0 or 1"); return -1; }
+        if (n_new[i] < 0) { set_error(at + "n_new must not be negative"); return -1; }
+        if (ps[1] != 0) { set_error(at + "the stream is finished: a push after the final call"); return -1; }
+        if (ps[0] < 0 || ps[0] + n_new[i] > GPT_MAX_SOURCE) { set_error(at + "a stream takes at most 65536 ids"); return -1; }
+        if (final[i] && ps[0] + n_new[i] < 1) { set_error(at + "a final call with nothing pushed"); return -1; }
+        if (u_pos0[i] < 0 || u_pos0[i] > INT32_MAX) { set_error(at + "u_pos0 must not be negative and must fit 31 bits"); return -1; }
+        n_before[i] = ps[0];
+        k0[i] = gpt_stream_windows_run(ps[0], S, H);
+        k1[i] = gpt_stream_windows_run(ps[0] + n_new[i], S, H);
+        p_base[i] = k0[i] > 0 ? (int64_t)r * k0[i] * H : 0;   // the stream position of out_ids_dev[i][0]
+        total_new += n_new[i];
+        if (k1[i] > k0[i] || final[i]) {
+            const int64_t N = ps[0] + n_new[i];
+            const GptWindow first = gpt_window((int)(final[i] && k0[i] == k1[i] ? N : (int64_t)k0[i] * H + S + 1), k0[i], S, H, r, max_new, block);
+            const GptWindow last = gpt_window((int)(final[i] ? N : (int64_t)(k1[i] - 1) * H + S + 1), final[i] ? k1[i] : k1[i] - 1, S, H, r, max_new, block);
+            const int64_t end = (int64_t)last.stream_base + last.budget;
+            if (!(first.stream_base >= u_pos0[i] && end <= u_pos0[i] + u_stride)) { set_error(at + "the uniforms do not cover the stream positions this call draws"); return -1; }
+            if (end - p_base[i] > out_stride) { set_error(at + "out_stride must hold the carry and the ids this call can produce"); return -1; }
+        }
+    }
+    AT_REQUIRE(total_new == 0 || ids_dev != nullptr, "ids need a pointer");
+    const GptPoolState st = carve_pool(state_dev, h, streams, slots, max_len, tick_tokens, S, H, r);
+    AT_REQUIRE(state_bytes >= st.bytes, "state too small: at_gpt_pool_state_bytes(h, streams, slots, max_len, tick_tokens, S, H, r)");
+    if (n_ticks) *n_ticks = 0;
+    if (n_rounds) *n_rounds = 0;
+    if (n == 0) return 0;
+    // ---- nothing above touched the device or the host record
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    hipStream_t stream = (hipStream_t)stream_;
+    const SampleArgs sa = generation_args(h, st.g, rq.samp, rq.out);
+    q.src = st.src;
+    q.src_stride = 0;   // a stream's ring is found by its start's origin, not by its row of the call
+    // each piece begins with the carry its stream's first window of the call reads
+    PoolLaunch carry_in;
+    for (int i = 0; i < n; ++i)
+        if ((k1[i] > k0[i] || final[i]) && k0[i] > 0) carry_in.add((int64_t)i * out_stride, (int64_t)place[i] * st.carry_stride, carry);
+    if (int rc = carry_in.copy(out_ids_dev, st.carry, stream)) return rc;
+    GptPoolSchedule schedule(n_before.data(), n_new, final, n, S, H, r, max_new, block, slots, tick_tokens);
+    std::vector<int64_t> taken((size_t)n, 0);
+    std::vector<int32_t> ran((size_t)n, 0);
+    int64_t id_off = 0;
+    std::vector<int64_t> id0((size_t)n);
+    for (int i = 0; i < n; ++i) { id0[i] = id_off; id_off += n_new[i]; }
+    while (schedule.next_round()) {
+        PoolLaunch copy_in, shift;
+        for (int i = 0; i < n; ++i) {
+            const GptStreamRound* rd = schedule.round(i);
+            if (!rd) continue;
+            const int64_t ring = (int64_t)place[i] * 2 * S;
+            copy_in.add(ring + rd->held, id0[i] + taken[i], rd->take);
+            taken[i] += rd->take;
+            ran[i] += rd->n_win + (rd->final_window ? 1 : 0);
+            if (rd->n_win > 0 && !rd->final_window) shift.add(ring, ring + (int64_t)rd->n_win * H, rd->held + rd->take - rd->n_win * H);
+        }
+        if (int rc = copy_in.copy(st.src, ids_dev, stream)) return rc;
+        GptPoolTick t;
+        while (schedule.next(&t)) {
+            TickPlan p{};
+            p.steps.n = p.R = t.n_step;
+            for (int j = 0; j < t.n_step; ++j) p.steps.slot[j] = (unsigned char)t.step_slot[j];
+            for (int j = 0; j < t.n_start; ++j) {
+                const GptQueueStart& s0 = t.start[j];
+                p.src_org[j] = (int)((int64_t)place[s0.src] * 2 * S - t.src_pos[j]);
+                p.out_org[j] = (int)p_base[s0.src];
+                p.u_org[j] = (int)u_pos0[s0.src];
+                p.start(s0.slot, s0.src, s0.k, s0.P, s0.final_window != 0);
+            }
+            if (int rc = run_tick(h, st.g, p, q, sa, stream)) return rc;
+            const int at = schedule.ticks() - 1;
+            if (at < trace_cap) {   // a trace too small loses its tail, the run goes on
+                int32_t* row = trace + 5 * (size_t)at;
+                row[0] = t.n_step; row[1] = t.n_start; row[2] = t.prefill_tokens; row[3] = t.route(); row[4] = schedule.rounds() - 1;
+            }
+            if (t.poll) {   // the host's only look at the device: some row is in a final window, and when that ends only the device knows
+                AT_CHECK_HIP(hipMemcpyAsync(h->flags_host, st.g.done, slots * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                AT_CHECK_HIP(hipStreamSynchronize(stream));
+                schedule.seen(h->flags_host);
+            }
+        }
+        if (int rc = shift.shift(st.src, stream)) return rc;
+    }
+    // the carry of each stream's next call: the last r (S - H) ids of what it has produced
+    PoolLaunch carry_out;
+    for (int i = 0; i < n; ++i)
+        if (k1[i] > k0[i] && !final[i]) carry_out.add((int64_t)place[i] * st.carry_stride, (int64_t)i * out_stride + (int64_t)r * k1[i] * H - p_base[i], carry);
+    if (int rc = carry_out.copy(st.carry, out_ids_dev, stream)) return rc;
+    for (int i = 0; i < n; ++i) {
+        pos[2 * (size_t)place[i]] += n_new[i];
+        pos[2 * (size_t)place[i] + 1] = final[i];
+        if (windows_run) windows_run[i] = ran[i];
+    }
+    if (n_ticks) *n_ticks = schedule.ticks();
+    if (n_rounds) *n_rounds = schedule.rounds();
+    if (placement) std::memcpy(placement, schedule.placement().data(), (size_t)n * 3 * sizeof(int32_t));
     return 0;
 }
 

@@ -11,8 +11,10 @@ struct Allow {
 };
 // The sampler's rule for one cache row while a window runs in it: which row of the caller's arrays it is, where in that row's stream its step 0 lies (out_ids,
 // uniforms and logits_out are indexed by stream position), how many steps it has, what it may produce on even / odd steps and which id stops it (-1: none).
+// out_org / u_org: the stream position of element 0 of the row's out_ids (and logits_out) and of its uniforms: 0 everywhere but in a stream pool
+// (DESIGN.md 26), whose streams stand at different positions in one call.
 struct SampleRow {
-    int out_row, base, budget, stop_token, final_window;
+    int out_row, base, budget, stop_token, final_window, out_org, u_org;
     Allow allow[2];
 };
 

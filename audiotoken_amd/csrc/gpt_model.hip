@@ -320,10 +320,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     const SampleRow* pr = generating ? a.rows + b : nullptr;
     if (pr && step >= pr->budget) return;
     // where the step's id, draw and logits live: the caller's row and the stream position
-    const int orow = pr ? pr->out_row : b, pos = (pr ? pr->base : 0) + step;
+    const int orow = pr ? pr->out_row : b, pos = (pr ? pr->base : 0) + step, out_at = pos - (pr ? pr->out_org : 0), u_at = pos - (pr ? pr->u_org : 0);
     const Allow allow = pr ? pr->allow[step & 1] : a.allow;
     if (generating && a.logits_out) {
-        float* dst = a.logits_out + ((size_t)orow * a.out_stride + pos) * V;
+        float* dst = a.logits_out + ((size_t)orow * a.out_stride + out_at) * V;
         for (int i = tid; i < V; i += SAMPLE_THREADS) dst[i] = z[i];
     }
     // ---- the k-th largest tempered value, exactly: radix select over the order keys, 8 bits a pass, and the maximum on the way
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
     // weights are scanned (shuffle scan), the groups chain through a carry, the waves' totals are added in wave order. The first walk gives the waves' totals and S,
     // the second the running sums, its carry starting from the total of the waves before.
     const int per_wave = ((V + SAMPLE_THREADS / 64 - 1) / (SAMPLE_THREADS / 64) + 63) / 64 * 64, first = wave * per_wave;
-    const float u = a.uniforms[(size_t)orow * a.u_stride + pos];
+    const float u = a.uniforms[(size_t)orow * a.u_stride + u_at];
     float before = 0.f, target = 0.f;
     bool found = false;
     int top = -1;
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void gpt_sample_kernel(SampleArgs a
         a.done[b] = a.finish[orow] = GPT_FINISH_STOP;
         return;
     }
-    a.out_ids[(size_t)orow * a.out_stride + pos] = tok;
+    a.out_ids[(size_t)orow * a.out_stride + out_at] = tok;
     a.out_len[orow] = pos + 1;
     a.cur[b] = tok;
     const int total = a.len[b] + 1;

@@ -561,6 +561,12 @@ class SemanticToAcoustic(LibHandle):
         out.ticks, out.placement = queue.get("ticks"), queue.get("placement")
         return out
 
+    def stream_pool(self, streams: int = 64, slots: int = 16, **kw):
+        """Stage 1 of a stream pool: a ``semantic_pool.GptStreamPool`` on this model. Up to ``streams`` live streams, which start, push and
+        finish on their own, share ``slots`` cache rows; each follows ``to_acoustic_long``'s schedule on its own source with its own draws."""
+        from .semantic_pool import GptStreamPool
+        return GptStreamPool(self, streams=streams, slots=slots, **kw)
+
     def score_rows(self, seqs: Sequence[np.ndarray], score_from: Sequence[int], temperature: float = 1.0, allow=None, rows: int = MAX_SLOTS,
                    pass_tokens: Optional[int] = None, head_rows: int = 1024, max_len: Optional[int] = None, return_logits: bool = False):
         """``at_gpt_score`` as it is (include/audiotoken_hip.h): ``seqs`` 1 to 65536 int id arrays over the model's own vocabulary, row b

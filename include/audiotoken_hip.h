@@ -906,6 +906,49 @@ int at_fine_stream_push(at_fine_t* h, void* state_dev, size_t state_bytes, int64
 int at_op_fine_handover(const int32_t* ids_dev, int n_frames, int n_pad, int acoustic_offset, int codebook_size, int32_t* work_dev, at_stream_t stream,
                         int32_t* status_dev);
 
+/* ---- semantic-to-audio stream pools: live streams share the GPT's ticks and the fine stage's passes ------------------------------
+ * A pool's device state is caller-owned: the shared part of at_gpt_generate_queue / at_fine_generate_queue (`slots` cache rows and `tick_tokens` token
+ * rows; the activations of `fine_slots` windows) and per stream only what outlives a call. `pos` is the pool's HOST record, int64 [streams][2], row
+ * `place` = {items pushed so far, 1 after the final call} of the stream in that place; the caller zeroes a row to start a stream there and a call that
+ * succeeds updates the rows it names. One call serves n of the streams, named by place[n] (HOST, distinct) and listed in ascending stream id, which is
+ * the order in which they take free rows; every other call array is indexed by the call's streams, 0 .. n - 1. A call is checked whole before the
+ * device or the record is touched: a refused call leaves every stream as it was. All launches go on `stream`; not re-entrant per handle.
+ *
+ * at_gpt_pool_push: stream i of the call pushes n_new[i] (HOST, >= 0) ids, ids_dev holding all of them back to back in the call's order, and
+ * final[i] = 1 (HOST) runs its remaining window as the final one. Per stream the windows, their rules and the meaning of its piece are
+ * at_gpt_stream_push's: out_ids_dev [n][out_stride], row i starting at stream position r k0 H of stream i (its carry first when k0 > 0);
+ * uniforms_dev [n][u_stride], the draw of stream position p of stream i being uniforms_dev[i][p - u_pos0[i]] (u_pos0 HOST int64 [n]);
+ * out_len_dev / finish_dev device int32 [n] (finish must be zeroed by the caller; out_len counts the whole stream and is written when an id is);
+ * logits_out_dev NULL or [n][out_stride][V], indexed as out_ids_dev. The streams' windows share `slots` cache rows by at_gpt_generate_queue's tick
+ * (GptPoolSchedule in csrc/gpt.h). The rings hold 2 S ids per stream, so a long push is absorbed in rounds that are global to the call: one copy-in,
+ * the round's ticks, one shift. HOST outputs, each nullable: windows_run [n]; trace [trace_cap][5] = a tick's step tokens, windows started, prefill
+ * tokens, route (1: the GEMM) and round; n_ticks; n_rounds; placement [n][3] = the cache row of the stream's last chain, its first and last tick (-1:
+ * it ran no window). n * out_stride and every u_pos0 must fit 31 bits. max_len must hold max(S + 1 + r S, min(block, S + 1 + r (S - H) + max_new)) positions, tick_tokens at least slots + max_len.
+ * The host looks at the device only while some row is in a final window (the rows' flags, every 16 ticks). at_gpt_set_truncation applies. */
+size_t at_gpt_pool_state_bytes(const at_gpt_t* h, int streams, int slots, int max_len, int tick_tokens, int S, int H, int r);
+int at_gpt_pool_push(at_gpt_t* h, void* state_dev, size_t state_bytes, int streams, int slots, int max_len, int tick_tokens, int64_t* pos, int n,
+                     const int32_t* place, const int32_t* ids_dev, const int32_t* n_new, const int32_t* final, int S, int H, int r, int semantic_offset,
+                     int semantic_vocab, int infer_token, int acoustic_offset, int codebook_size, int stop_token, int max_new, float temperature, int top_k,
+                     const float* uniforms_dev, int u_stride, const int64_t* u_pos0, int32_t* out_ids_dev, int out_stride, int32_t* out_len_dev,
+                     int32_t* finish_dev, float* logits_out_dev, int32_t* windows_run, int32_t* trace, int trace_cap, int32_t* n_ticks, int32_t* n_rounds,
+                     int32_t* placement, at_stream_t stream, int32_t* status_dev);
+/* at_fine_pool_push: stream i of the call hands over n_frames[i] (HOST, >= 0) new coarse frames, the 2 n_frames[i] interleaved ids from
+ * ids_dev[id_off[i]] on (id_off HOST int64 [n], even; ids_dev 8-byte aligned; at_gpt_pool_push's out_ids_dev with id_off[i] = i out_stride + the carry is
+ * such an array), and final[i] = 1 (HOST) ends it. Per stream the windows, their draws and what turns final are at_fine_stream_push's. The state
+ * (at_fine_pool_state_bytes) holds 2 W cells [8] per stream and the activations of fine_slots windows. Per round, for all streams of the call: one
+ * hand-over launch (status bit 2 as at_fine_stream_push), the runnable windows in waves (wave w: the w-th runnable window of every stream that has one, in
+ * passes of up to fine_slots windows; two windows of one stream never share a pass), one emit launch, one shift launch; a launch takes up to 128 streams.
+ * The draw of window j of stream i, code book 2 + c, buffer position t is uniforms_dev[((u_cell0[i] + j - u_win0[i]) * 6 + c) * W + t] (all three HOST
+ * int32 [n]); a window outside [u_win0[i], u_win0[i] + u_windows[i]) is refused. emit_dev: device int64 [n][8][emit_stride], stream i's final frames in
+ * order from column 0 (n * 8 * emit_stride must fit 31 bits); n_emitted (HOST int32 [n], not NULL) their counts. HOST outputs, nullable: windows_run [n]; trace [trace_cap][3] = a pass's round,
+ * wave and windows; n_passes. Nothing is polled: the schedule is known from the counts. */
+size_t at_fine_pool_state_bytes(const at_fine_t* h, int streams, int fine_slots);
+int at_fine_pool_push(at_fine_t* h, void* state_dev, size_t state_bytes, int streams, int fine_slots, int64_t* pos, int n, const int32_t* place,
+                      const int32_t* ids_dev, const int64_t* id_off, const int32_t* n_frames, const int32_t* final, int acoustic_offset, int codebook_size,
+                      float temperature, int greedy, const float* uniforms_dev, const int32_t* u_cell0, const int32_t* u_win0, const int32_t* u_windows,
+                      int64_t* emit_dev, int emit_stride, int32_t* n_emitted, int32_t* windows_run, int32_t* trace, int trace_cap, int32_t* n_passes,
+                      at_stream_t stream, int32_t* status_dev);
+
 #ifdef __cplusplus
 }
 #endif
