@@ -143,6 +143,9 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "at_hubert_encode_checked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "at_hubert_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "at_op_hub_conv0": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "at_op_hub_frame_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "at_hubert_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "at_hubert_get_option": (C.c_int, [C.c_void_p, C.c_char_p]),
     "at_hubert_profile": (C.c_int, [C.c_void_p, C.c_int]),

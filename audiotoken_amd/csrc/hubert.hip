@@ -7,7 +7,7 @@
 //   feature-extractor convs [512][Cin][k] -> [512][k*Cin] (tap-major, channels-last windows); conv 0 keeps [512][10]
 //   positional conv (weight-norm folded by the caller) [768][48][128], groups 16 -> 16 x [48][128*48]
 //   q,k,v Linear -> one [2304][768]
-// The encode entry point is checks, plan, the Call struct, then one call per stage: feature_extractor, projection_posconv, transformer_layer per
+// The encode entry point is checks, plan, the Call struct (make_call; the test tap at_hubert_features stops after the first stage), then one call per stage: feature_extractor, projection_posconv, transformer_layer per
 // layer, quantise. Every split GEMM, the windowed conv chain included, goes through split_gemm_args (semantic_handle.h), which owns the f16x2 scale rule.
 #include <string>
 #include <vector>
@@ -307,6 +307,25 @@ struct Call {
     SplitCtx ctx_of(int li) const { return SplitCtx{scheme_of(h->arith_of(li)), h->range.layer_row(li)}; }
 };
 
+// The Call of one entry into the model: shapes from the plan, every buffer a slice of the caller's workspace (make_plan's offsets)
+Call make_call(at_hubert* h, const Plan& p, int B, int N, int n_layers, void* workspace, hipStream_t stream, int32_t* status_dev) {
+    float* ws = (float*)workspace;
+    Call c{};
+    c.h = h; c.p = &p; c.stream = stream; c.B = B; c.N = N; c.T = p.L[7]; c.n_layers = n_layers;
+    c.M = (long long)B * c.T; c.Mpad = (long long)p.Mpad;
+    c.status = reinterpret_cast<int*>(status_dev);
+    c.split = h->arith != ARITH_F32;
+    c.ln_pieces = c.split && h->ln_split;
+    c.conv_a = ws + p.off_a; c.conv_b = ws + p.off_b; c.part = ws + p.off_part; c.ss = ws + p.off_ss;
+    c.fmask = ws + p.off_fmask; c.x = ws + p.off_x; c.t1 = ws + p.off_t1; c.pos = ws + p.off_pos; c.big = ws + p.off_big;
+    c.conv_sa = reinterpret_cast<piece_t*>(ws + p.off_sa);
+    c.conv_sb = reinterpret_cast<piece_t*>(ws + p.off_sb);
+    c.xs = reinterpret_cast<piece_t*>(ws + p.off_xs);
+    c.bigs = reinterpret_cast<piece_t*>(ws + p.off_bigs);
+    c.kvs = reinterpret_cast<piece_t*>(ws + p.off_kvs);
+    return c;
+}
+
 int linear(const Call& c, const float* X, int K, const float* W, const float* bias, float* C, int N, int epi, const float* R, const float* row_mask, int ldc) {
     GemmArgs a;
     a.X = X; a.Tin = (int)c.M; a.Cin = K; a.ldx = K;
@@ -510,20 +529,7 @@ int at_hubert_encode_checked(at_hubert_t* h, const float* wav, const float* mask
     AT_REQUIRE(kRangeLayer0 + n_layers <= kRangeRows, "more transformer layers than range-table rows");
     if (int rc = h->range.reset(stream)) return rc;
 
-    float* ws = (float*)workspace;
-    Call c{};
-    c.h = h; c.p = &p; c.stream = stream; c.B = B; c.N = N; c.T = p.L[7]; c.n_layers = n_layers;
-    c.M = (long long)B * c.T; c.Mpad = (long long)p.Mpad;
-    c.status = reinterpret_cast<int*>(status_dev);
-    c.split = h->arith != ARITH_F32;
-    c.ln_pieces = c.split && h->ln_split;
-    c.conv_a = ws + p.off_a; c.conv_b = ws + p.off_b; c.part = ws + p.off_part; c.ss = ws + p.off_ss;
-    c.fmask = ws + p.off_fmask; c.x = ws + p.off_x; c.t1 = ws + p.off_t1; c.pos = ws + p.off_pos; c.big = ws + p.off_big;
-    c.conv_sa = reinterpret_cast<piece_t*>(ws + p.off_sa);
-    c.conv_sb = reinterpret_cast<piece_t*>(ws + p.off_sb);
-    c.xs = reinterpret_cast<piece_t*>(ws + p.off_xs);
-    c.bigs = reinterpret_cast<piece_t*>(ws + p.off_bigs);
-    c.kvs = reinterpret_cast<piece_t*>(ws + p.off_kvs);
+    const Call c = make_call(h, p, B, N, n_layers, workspace, stream, status_dev);
 
     if (int rc = feature_extractor(c, wav)) return rc;
     if (int rc = projection_posconv(c, mask)) return rc;
@@ -534,6 +540,28 @@ int at_hubert_encode_checked(at_hubert_t* h, const float* wav, const float* mask
     if (hidden_out) AT_CHECK_HIP(hipMemcpyAsync(hidden_out, c.x, (size_t)c.M * kHid * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (tokens)
         if (int rc = quantise(c, tokens)) return rc;
+    return 0;
+}
+
+// Test tap: the conv features alone. The same feature_extractor() the encode runs, on the handle's current arithmetic, over the same plan and
+// workspace slices (make_call); feats() copied out. status_dev: the front end's range sites (row 0 of the table) only.
+int at_hubert_features(at_hubert_t* h, const float* wav, int B, int N, float* feats_out, void* workspace, size_t workspace_bytes, at_stream_t stream_,
+                       int32_t* status_dev) {
+    AT_REQUIRE(h && h->finalized, "model not finalized");
+    DeviceGuard guard(h->device);
+    AT_REQUIRE(guard.ok, "cannot select the handle's device");
+    AT_REQUIRE(wav && feats_out && workspace, "null pointer");
+    const Plan p = make_plan(B, N);
+    AT_REQUIRE(B >= 1 && p.L[7] >= 1, "clip too short (needs at least 400 samples)");
+    AT_REQUIRE(workspace_bytes >= p.total_floats * sizeof(float), "workspace too small");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (status_dev) AT_CHECK_HIP(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
+    if (int rc = h->range.reset(stream)) return rc;
+    const Call c = make_call(h, p, B, N, 0, workspace, stream, status_dev);
+    if (int rc = feature_extractor(c, wav)) return rc;
+    if (status_dev)
+        if (int rc = launch_range_combine(h->range.dev, kRangeLayer0 * (int)H_NSITES, c.status, stream)) return rc;
+    AT_CHECK_HIP(hipMemcpyAsync(feats_out, c.feats(), (size_t)c.M * kCd * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return 0;
 }
 

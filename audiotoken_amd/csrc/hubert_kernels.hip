@@ -1,6 +1,7 @@
 // Kernels specific to the semantic_s tokenizer (HuBERT-base): first feature-extractor conv (Cin = 1) and the
 // per-channel GroupNorm + GELU that follows it (HF modeling_hubert.py:154-176). Everything else (strided convs,
 // grouped positional conv, Linear, attention, LayerNorm, k-means assignment) reuses the shared kernels.
+#include "../../include/audiotoken_hip.h"
 #include "gemm_core.h"
 #include "hubert_kernels.h"
 #include "split_scheme.h"
@@ -251,3 +252,33 @@ int launch_hub_frame_mask(const float* smask, float* fmask, int B, int N, int T,
 }
 
 }  // namespace at
+
+// ---- operator-level test taps (at_op_* in include/audiotoken_hip.h): the launchers above on caller-owned buffers, no model handle ---------------------
+// the float64 moment partials [B][chunks of 4096 frames][65] rounded up to 256 bytes, then scale / shift [B][512][2] fp32
+static size_t hub_conv0_workspace_bytes(int B, int T0) {
+    const size_t part = ((size_t)B * at::hub_ws_nchunk(T0) * at::WS_NMOM * sizeof(double) + 255) / 256 * 256;
+    return part + (size_t)B * 512 * 2 * sizeof(float);
+}
+
+extern "C" {
+
+int at_op_hub_conv0(const float* wav, const float* w, const float* gamma, const float* beta, float* out, int B, int N, void* workspace,
+                    size_t workspace_bytes, at_stream_t stream) {
+    AT_REQUIRE(wav && w && gamma && beta && out && workspace, "null pointer");
+    AT_REQUIRE(B >= 1 && N >= 10, "bad arguments: B >= 1, N >= 10 (one conv window)");
+    AT_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "workspace must be 16-byte aligned");
+    const int T0 = (N - 10) / 5 + 1;
+    const size_t need = hub_conv0_workspace_bytes(B, T0);
+    AT_REQUIRE(workspace_bytes >= need, "workspace too small: round_up(B * ceil(T0 / 4096) * 520, 256) + B * 4096 bytes, T0 = (N - 10) / 5 + 1");
+    float* part = static_cast<float*>(workspace);                                                       // the moment partials, as doubles
+    float* ss = reinterpret_cast<float*>(static_cast<char*>(workspace) + need - (size_t)B * 512 * 2 * sizeof(float));
+    return at::launch_hub_conv0_gn_gelu(wav, w, gamma, beta, part, ss, out, B, N, T0, (hipStream_t)stream);
+}
+
+int at_op_hub_frame_mask(const float* smask, float* fmask, int B, int N, int T, at_stream_t stream) {
+    AT_REQUIRE(fmask != nullptr, "null pointer");
+    AT_REQUIRE(B >= 1 && N >= 1 && T >= 1, "bad arguments: B, N, T >= 1");
+    return at::launch_hub_frame_mask(smask, fmask, B, N, T, (hipStream_t)stream);
+}
+
+}  // extern "C"

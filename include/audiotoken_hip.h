@@ -327,6 +327,11 @@ int at_hubert_encode(at_hubert_t* h, const float* wav, const float* mask, int B,
  * "f16x2" arithmetic) and the "arith" option (0 f32 MFMA, 1 bf16x3, 2 f16x2 = default; also covers the six 512->512 feature-extractor convs). */
 int at_hubert_encode_checked(at_hubert_t* h, const float* wav, const float* mask, int B, int N, int n_layers, int16_t* tokens, int* T_out,
                              float* hidden_out, void* workspace, size_t workspace_bytes, at_stream_t stream, int32_t* status_dev);
+/* Test tap: the conv feature encoder alone — the stage at_hubert_encode_checked runs first, on the handle's current "arith", over the same workspace
+ * layout (at_hubert_workspace_bytes(h, B, N)). feats_out device float32 [B][T][512] = the seventh conv's GELU output, T = at_hubert_num_tokens(N).
+ * status_dev: nullable device word, the OR of the front end's range sites (bit 1 = fp16 range overflow). */
+int at_hubert_features(at_hubert_t* h, const float* wav, int B, int N, float* feats_out, void* workspace, size_t workspace_bytes, at_stream_t stream,
+                       int32_t* status_dev);
 int at_hubert_set_option(at_hubert_t* h, const char* name, int value);
 int at_hubert_get_option(const at_hubert_t* h, const char* name);
 int at_hubert_profile(at_hubert_t* h, int enable);
@@ -558,6 +563,16 @@ int at_op_rvq_encode(const float* x, int64_t rows, int T, const float* codebooks
  * bytes; status_dev nullable (bit 1 = fp16 range overflow of the residual). */
 int at_op_rvq_encode_split(const float* x, int64_t rows, int T, const float* codebooks, const float* e2, int n_q, int16_t* codes, int scheme,
                            float cb_max_abs, void* workspace, size_t workspace_bytes, int32_t* status_dev, at_stream_t stream);
+
+/* The first HuBERT feature-extractor layer in its fp32-output form (csrc/hubert_kernels.hip; HF modeling_hubert.py:154-176), for the parity tests:
+ * conv1d(1 -> 512, k 10, stride 5, valid, no bias) -> GroupNorm(512 groups, eps 1e-5, affine) over the T0 = (N - 10) / 5 + 1 frames -> GELU(erf).
+ * wav [B][N], w [512][10], gamma / beta [512], out [B][T0][512], any N >= 10. workspace (16-byte aligned) >= round_up(B * ceil(T0 / 4096) * 520, 256)
+ * + B * 4096 bytes: the float64 waveform-moment partials and the per-channel scale / shift. */
+int at_op_hub_conv0(const float* wav, const float* w, const float* gamma, const float* beta, float* out, int B, int N, void* workspace,
+                    size_t workspace_bytes, at_stream_t stream);
+/* HuBERT's frame-level mask (HF modeling_hubert.py:664-693): fmask [B][T] = 1 for t < out_len(sum of the clip's sample mask), else 0, out_len = the
+ * chained floor((L - k) / s) + 1 of the seven convs. smask [B][N] of 0 / 1 values, or NULL = every sample valid (out_len(N)). */
+int at_op_hub_frame_mask(const float* smask, float* fmask, int B, int N, int T, at_stream_t stream);
 
 /* LayerNorm over the last dim (eps 1e-5); gamma/beta NULL = non-affine; rows with row_mask 0 are zeroed. */
 int at_op_layernorm(const float* x, const float* gamma, const float* beta, const float* row_mask, float* y, int64_t rows, int D,

@@ -49,6 +49,59 @@ def test_gemm_dual_second_source_width_must_be_a_multiple_of_4():
     assert lib.at_op_attention_f32(4096, 4096, None, 4096, 1, 1, 65, None) == -1 and "bad arguments" in _cabi.last_error()
 
 
+def test_hubert_front_taps_refuse_bad_arguments_before_any_launch():
+    """at_hubert_features, at_op_hub_conv0 and at_op_hub_frame_mask: every refusal below happens in the argument checks (status -1, message set), so this
+    runs without a device; the addresses are never dereferenced."""
+    lib = _cabi.load()
+    assert lib.at_hubert_features(None, 4096, 1, 400, 4096, 4096, 1 << 30, None, None) == -1 and "not finalized" in _cabi.last_error()
+    ok = dict(wav=4096, w=8192, gamma=12288, beta=16384, out=20480, B=2, N=403, ws=1 << 20, nbytes=1280 + 2 * 4096)
+
+    def conv0(**kw):
+        a = dict(ok, **kw)
+        return lib.at_op_hub_conv0(a["wav"], a["w"], a["gamma"], a["beta"], a["out"], a["B"], a["N"], a["ws"], a["nbytes"], None)
+
+    for name in ("wav", "w", "gamma", "beta", "out", "ws"):
+        assert conv0(**{name: None}) == -1 and "null pointer" in _cabi.last_error(), name
+    assert conv0(N=9) == -1 and "N >= 10" in _cabi.last_error()
+    assert conv0(B=0) == -1 and "B >= 1" in _cabi.last_error()
+    assert conv0(ws=(1 << 20) + 8) == -1 and "16-byte aligned" in _cabi.last_error()
+    # T0 = 79: one chunk of 65 doubles per clip = 1040 bytes -> 1280, + 2 x 4096 for scale / shift; one byte less is refused
+    assert conv0(nbytes=1280 + 8192 - 1) == -1 and "workspace too small" in _cabi.last_error()
+    # T0 = 4097 takes a second chunk of moment partials: what was enough for T0 = 4096 no longer is
+    enough_4096 = (2 * 1 * 520 + 255) // 256 * 256 + 8192
+    assert conv0(N=5 * 4097 + 5, nbytes=enough_4096) == -1 and "workspace too small" in _cabi.last_error()
+    assert lib.at_op_hub_frame_mask(4096, None, 2, 400, 1, None) == -1 and "null pointer" in _cabi.last_error()
+    for B, N, T in ((0, 400, 1), (2, 0, 1), (2, 400, 0)):
+        assert lib.at_op_hub_frame_mask(4096, 8192, B, N, T, None) == -1 and "B, N, T >= 1" in _cabi.last_error()
+
+
+@pytest.mark.gpu
+def test_hubert_features_argument_validation(cuda_device):
+    """at_hubert_features on a finalized handle: null pointers, a clip below 400 samples and a short workspace are refused with a message, nothing is
+    written, and the handle serves the next call."""
+    from audiotoken_amd.configs import HubertEncoderConfig
+    from audiotoken_amd.hubert import HubertEncoder
+    enc = HubertEncoder(HubertEncoderConfig(output_layer=0), device="cuda:0", quantize=False, weights=W.synth_hubert_weights(0, 2, False))
+    lib, h = enc.lib, enc.handle
+    B, N = 2, 405
+    wav = torch.zeros(B, N, device="cuda")
+    feats = torch.full((B, 1, 512), float("nan"), device="cuda")
+    nbytes = lib.at_hubert_workspace_bytes(h, B, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    st = _cabi.current_stream_handle(torch.device("cuda:0"))
+    assert lib.at_hubert_features(h, None, B, N, feats.data_ptr(), ws.data_ptr(), nbytes, st, None) == -1 and "null pointer" in _cabi.last_error()
+    assert lib.at_hubert_features(h, wav.data_ptr(), B, N, None, ws.data_ptr(), nbytes, st, None) == -1 and "null pointer" in _cabi.last_error()
+    assert lib.at_hubert_features(h, wav.data_ptr(), B, N, feats.data_ptr(), None, nbytes, st, None) == -1 and "null pointer" in _cabi.last_error()
+    assert lib.at_hubert_features(h, wav.data_ptr(), B, 399, feats.data_ptr(), ws.data_ptr(), nbytes, st, None) == -1 and "too short" in _cabi.last_error()
+    assert lib.at_hubert_features(h, wav.data_ptr(), 0, N, feats.data_ptr(), ws.data_ptr(), nbytes, st, None) == -1 and "too short" in _cabi.last_error()
+    assert lib.at_hubert_features(h, wav.data_ptr(), B, N, feats.data_ptr(), ws.data_ptr(), nbytes - 1, st, None) == -1 and "workspace" in _cabi.last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(feats).all()), "a refused call must not write features"
+    assert lib.at_hubert_features(h, wav.data_ptr(), B, N, feats.data_ptr(), ws.data_ptr(), nbytes, st, None) == 0, _cabi.last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(feats).all())
+
+
 @pytest.mark.gpu
 def test_encode_argument_validation(cuda_device):
     from audiotoken_amd.configs import AcousticEncoderConfig
